@@ -2,16 +2,24 @@
 """Headline benchmark: frame-sequences/s, forward + backward, T=6, 900x1600, B=2 per GPU, bf16.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py ... --full                             (+ the side measurements, see below)
+    python bench.py ... --dump-outputs DIR                 (+ the timed step's outputs as DIR/<name>.npy, see there)
 
 One "step" = one pass of the hot path over one synthetic batch: model(data) (backbone, encoder,
 decoder, matcher + set loss, post-processing / AP bookkeeping, exactly the reference's forward,
 future_od/models/st_detr.py:98-167) + loss.backward() (+ the gradient all-reduce when N > 1) +
 gradient clipping and the AdamW update (reference future_od/trainer.py:171-189).  Inputs are resident in
 HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what takes runs of its own: the
+per-entry-point profile and `roofline` of the step (`--no-roofline`), the as-shipped K=2 and fp32 lines (`also`,
+`--no-extras`), the bf16 line beside an fp8 one (`vs_bf16_attention`), the data-parallel diagnostics (`ddp`) and the
+CPU baseline (`--no-cpu-baseline`).
 """
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -193,15 +201,99 @@ def cpu_baseline(num_images, cores, budget_s=150.0):
                                        f"1 warm-up + 3 timed, median {1e3 * statistics.median(t1):.0f} ms"}}
 
 
+DUMP_SAMPLE = 1 << 20     # --dump-outputs: elements kept of a larger array (a fixed, seeded sample)
+DUMP_LIMIT = 64 << 20     # bytes in all
+
+
+def _sample_index(n, seed):
+    import numpy as np
+    return np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLE, replace=False))
+
+
+def snapshot_state(opt):
+    """The trainable state a training step starts from: parameters, AdamW moments, step count."""
+    params = [p for grp in opt.param_groups for p in grp["params"]]
+    return {"params": [(p, p.detach().clone()) for p in params],
+            "moments": {p: (st["exp_avg"].clone(), st["exp_avg_sq"].clone())
+                        for p, st in opt.state.items() if "exp_avg" in st},
+            "step_no": getattr(opt, "_step_no", 0)}
+
+
+def restore_state(opt, snap):
+    """Put the state of `snapshot_state` back in place (the same tensors: a captured step keeps replaying on them)."""
+    from future_od.native import functional as Fn
+    with torch.no_grad():
+        for p, saved in snap["params"]:
+            p.copy_(saved)
+        for p, st in opt.state.items():
+            if "exp_avg" in st:
+                old = snap["moments"].get(p)
+                if old is None:                          # created by a later step: back to "never stepped"
+                    st["exp_avg"].zero_()
+                    st["exp_avg_sq"].zero_()
+                else:
+                    st["exp_avg"].copy_(old[0])
+                    st["exp_avg_sq"].copy_(old[1])
+    opt._step_no = snap["step_no"]
+    if getattr(opt, "_dev_step", None) is not None:
+        opt._dev_step.fill_(float(snap["step_no"]))
+    Fn.PREP.mark_stale()
+
+
+def dump_outputs(dirname, outs, model):
+    """What one timed step returned -- (post-processed detections, loss, loss terms, AP bookkeeping), every tensor in
+    it -- as DIR/<name>.npy (float64 for float64 and integer tensors, float32 otherwise), plus a fixed, seeded sample
+    of the parameters' gradients (the step's backward pass)."""
+    import numpy as np
+    arrays = {}
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            arrays[name] = v.detach()
+        elif isinstance(v, dict):
+            for k, x in v.items():
+                walk(f"{name}.{k}", x)
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk(f"{name}.{i}", x)
+        elif isinstance(v, (bool, int, float)):
+            arrays[name] = torch.tensor(float(v), dtype=torch.float64)
+
+    for name, v in zip(("post", "loss", "stats", "od"), outs):
+        walk(name, v)
+    params = [p for p in model.parameters() if p.requires_grad]
+    if any(p.grad is not None for p in params):
+        flat = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                          for p in params])
+        arrays["grads_sample"] = flat[torch.from_numpy(_sample_index(flat.numel(), 0)).to(flat.device)]
+        del flat
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        a = t.to("cpu", torch.float64 if wide else torch.float32).numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[_sample_index(a.size, 1)]
+            name += ".sample"
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB"
+        np.save(os.path.join(dirname, re.sub(r"[^A-Za-z0-9_.-]", "_", name) + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--num-images", type=int, default=5, help="decoder cross-attention blocks K (5 = all past frames live)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the K=2 / fp32 side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements (profile + roofline, K=2 / fp32 lines, bf16 beside fp8, data-parallel "
+                         "diagnostics, CPU baseline); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the profile / roofline leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the K=2 / fp32 side measurements")
     ap.add_argument("--no-graph", action="store_true",
                     help="N=1 only: launch every kernel from Python (the default replays the step as one hipGraph)")
     ap.add_argument("--dtype", default="bf16")
@@ -260,9 +352,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(num_images, dtype, steps, warmup, profile):
+    def measure(num_images, dtype, steps, warmup, profile, dump=None):
         """Build the model, run `warmup` untimed and exactly `steps` timed steps between fences; returns
-        (seconds over the timed steps -- max over ranks, final loss, profiler summary or None, profiled steps)."""
+        (seconds over the timed steps -- max over ranks, final loss, profiler summary or None, profiled steps).
+        `dump`: directory for the outputs of the timed step (rank 0), see below."""
         # data parallel + graphs: the bare model (GraphedStep averages the gradients itself between its two graphs);
         # data parallel, eager: the FodDataParallel wrapper with its side-stream reducer
         model, detr = build(a, device, distributed and not use_graph, num_images, dtype)
@@ -271,26 +364,27 @@ def main():
             model.train()
         opt = FusedAdamW(model.parameters(), lr=detr.lr, weight_decay=detr.weight_decay, max_norm=detr.max_norm)
         data = make_batch(BATCH_PER_GPU, T_FRAMES, HEIGHT, WIDTH, seed=1234 + rank, device=device)
+        snap = snapshot_state(opt) if dump and not a.forward_only else None
 
         def step():
             opt.zero_grad()
             out, _state, loss, stats, od = model(data=data, distributed=distributed)
             loss.backward()
             opt.step()
-            return loss
+            return out, loss, stats, od
 
         if a.forward_only:
             def step():                                  # noqa: F811  (the evaluation pass of the reference's Trainer)
                 with torch.no_grad():
                     out, _state, loss, stats, od = model(data=data, distributed=distributed)
-                return loss
+                return out, loss, stats, od
 
         eager_step = step
         if use_graph and a.forward_only:
             from future_od.graph import GraphedForward
             fwd = GraphedForward(model)
             fwd(data)
-            step = lambda: fwd(data)[1]
+            step = lambda: fwd(data)
         elif use_graph:
             # the same step -- same kernels, same order -- captured once and replayed (future_od/graph.py); the
             # capture and its eager warm-up steps happen before the timed region
@@ -299,20 +393,21 @@ def main():
             if distributed:
                 graphed.broadcast_parameters()
             graphed(data)
-            step = lambda: graphed(data)[1]
+            step = lambda: graphed(data)
 
         for _ in range(warmup):
             step()
         fence()
         t0 = time.perf_counter()
         for _ in range(steps):
-            loss = step()
+            outs = step()
         fence()
         dt = time.perf_counter() - t0
         t = torch.tensor([dt], device=device)
         if distributed:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+        loss = outs[1]
         # the device-side matcher reports a non-finite cost matrix one step late through a per-device status word: look at
         # it HERE, so that a run of this model that went non-finite (the random-init model at lr 1e-4 does in some runs,
         # DESIGN.md 5) is reported on ITS line instead of raising inside the next model built in this process
@@ -413,7 +508,23 @@ def main():
                                          "the backbone's backward",
                                  "arena_flushes": st["arena_flushes"], "arena_bytes_in_place": 4 * st["arena_elems"],
                                  "straggler_tensors": st["stragglers"]})
-        del model, opt, data
+        if dump:
+            # the timed path once more, untimed, from the state the first step started from (built weights, no AdamW
+            # moments): a training step's inputs include the parameters, and after many steps those carry the
+            # run-to-run rounding of the device's atomic reductions (amplified by AdamW's early near-sign updates and
+            # the matcher's discrete choices); from a fixed state the outputs agree between runs to rounding
+            if snap is not None:
+                restore_state(opt, snap)
+            outs = step()
+            fence()
+            try:
+                from future_od.models.set_criterion import _lap_status
+                _lap_status(torch.device(device)).check(wait=True)
+            except Exception as e:                           # noqa: BLE001
+                MATCHER_EVENTS.append(f"--dump-outputs step: {e}")
+            if rank == 0:
+                dump_outputs(dump, outs, getattr(model, "module", model))
+        del model, opt, data, outs, loss, snap
         import gc
         gc.collect()
         torch.cuda.empty_cache()
@@ -424,7 +535,8 @@ def main():
     # the all-reduces overlapped with the backbone's backward (future_od/parallel.py)
     use_graph = not a.no_graph
     ddp_info, eager_leg_info = {}, {}
-    dt, final_loss, summ, nprof, replay = measure(a.num_images, a.dtype, a.steps, a.warmup, not a.no_roofline)
+    dt, final_loss, summ, nprof, replay = measure(a.num_images, a.dtype, a.steps, a.warmup, a.full and not a.no_roofline,
+                                                  a.dump_outputs)
     seqs = BATCH_PER_GPU * world * a.steps
     value = seqs / dt
 
@@ -514,7 +626,7 @@ def main():
                                       for k, v in top[:14]}
     # for the record (N = 1, headline only): the reference's AS-SHIPPED model (num_images = 2: 3 of 5 past frames are
     # dead work and skipped) and the fp32-MFMA parity mode, same step definition, driver-timed like the main line
-    if world == 1 and a.workload == "headline" and a.num_images == 5 and not a.no_extras and not a.rehearse:
+    if a.full and world == 1 and a.workload == "headline" and a.num_images == 5 and not a.no_extras and not a.rehearse:
         extras = {}
         for key, (k_img, dtp) in {"headline-k2": (2, a.dtype), "headline-fp32": (5, "fp32")}.items():
             if dtp == a.dtype and k_img == a.num_images:
@@ -525,9 +637,10 @@ def main():
                            "steps": st, "warmup": 2, "num_images": k_img, "dtype": dtp, "final_loss": eloss}
         result["also"] = extras
     if a.attn_dtype != "bf16":
+        result["dtype"] = f"{a.dtype} (attention QK^T / PV: MX-fp8 e4m3, {a.attn_dtype})"
+    if a.full and a.attn_dtype != "bf16":
         # BASELINE.json configs[4] asks for fp8 "vs bf16": the same workload with the bf16 attention kernels, same process,
         # same box, and the attention entries' device time per replayed step for both
-        result["dtype"] = f"{a.dtype} (attention QK^T / PV: MX-fp8 e4m3, {a.attn_dtype})"
         attn_keys = ("fod_attn_fwd_fp8", "fod_attn_quant_fp8", "fod_attn_fwd", "fod_attn_bwd")
         mine = {k: v for k, v in (replay[0].items() if replay else []) if k in attn_keys}
         fp8_mode, a.attn_dtype = a.attn_dtype, "bf16"
@@ -541,7 +654,7 @@ def main():
             "throughput_ratio_fp8_over_bf16": value / (BATCH_PER_GPU * world * a.steps / bdt)}
     if distributed:
         dist.barrier()
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(a.num_images, min(os.cpu_count() or 1, 64))
     if rank == 0:
         print(json.dumps(result))

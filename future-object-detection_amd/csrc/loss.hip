@@ -240,6 +240,12 @@ __global__ void post_proc_kernel(const float* __restrict__ logits, const float* 
   boxes_px[r * 4 + 3] = cy + 0.5f * h;
 }
 
+// The annotation counts start from zero in a kernel of their own, not through hipMemsetAsync: captured into a
+// hipGraph, that memset node left stale host-pointer values in the buffer on every replay after the first.
+__global__ __launch_bounds__(64) void od_map_zero_kernel(unsigned long long* __restrict__ p, int n) {
+  for (int i = threadIdx.x; i < n; i += 64) p[i] = 0ull;
+}
+
 // One wave per (sample, class, threshold): rank the class scores, walk the top-K in order and
 // greedily claim the best still-free annotation (od_map.py:267-277).  f32 ops in the reference's
 // order, no FMA contraction, so >= threshold decisions agree with the CPU path.
@@ -514,11 +520,8 @@ extern "C" int fod_od_map(const float* scores, const float* boxes, const float* 
   FOD_REQUIRE(B > 0 && M > 0 && M <= OD_MAX_M && N > 0 && N <= OD_MAX_N && C1 > 0 && T > 0 && T <= 65535,
               "od_map: bad extents B=%d M=%d N=%d C1=%d T=%d", B, M, N, C1, T);
   const int K = M < 50 ? M : 50;
-  hipError_t e = hipMemsetAsync(num_annos, 0, sizeof(int64_t) * C1 * 4, stream);
-  if (e != hipSuccess) {
-    fod_set_error("od_map: memset: %s", hipGetErrorString(e));
-    return FOD_ERR_RUNTIME;
-  }
+  hipLaunchKernelGGL(od_map_zero_kernel, dim3(1), dim3(64), 0, stream, (unsigned long long*)num_annos, C1 * 4);
+  FOD_LAUNCH_CHECK();
   hipLaunchKernelGGL(od_map_kernel, dim3(B, C1, T), dim3(64), 0, stream, scores, boxes, anno_boxes, anno_classes,
                      anno_active, confs, is_positive, size_categories, (unsigned long long*)num_annos, B, M, C1, N, T,
                      K, img_h, img_w);

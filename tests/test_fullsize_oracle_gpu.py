@@ -29,12 +29,14 @@ CFG = Config(backbone="resnet50", enc_layers=6, dec_layers=6, num_images=5)
 def reference():
     """Oracle forward + set loss on the host (checker only)."""
     import os
+    prev = torch.get_num_threads()
     torch.set_num_threads(min(os.cpu_count() or 1, 64))
     data = make_batch(1, T_, H_, W_, seed=SEED, max_boxes=40)
     sd = O.make_state_dict(CFG, SEED)
     with torch.no_grad():
         ref = O.core_forward(sd, CFG, data["video"], O.imu_from_data(data), skip_dead=True)
         loss, _, _ = ocrit.total_loss(CFG, ref, data)
+    torch.set_num_threads(prev)                  # later tests' CPU references were recorded with their own thread counts
     targets = ocrit.to_detr_targets(H_, W_, data["active"], data["boxes"], data["classes"])
     idx = ocrit.hungarian_match(CFG, ref["pred_logits"], ref["pred_boxes"], targets)
     return data, ref, float(loss), targets, idx

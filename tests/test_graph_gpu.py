@@ -327,3 +327,35 @@ def test_matcher_failure_inside_a_replay_is_raised_at_the_next_call():
     with pytest.raises(FodError, match="non-finite"):
         fwd(data)
     fwd(data)                                           # the word was cleared: the pass works again
+
+
+def test_od_map_counts_hold_across_graph_replays():
+    """fod_od_map's annotation counts start from zero at every call: replays of a captured call (the captured training
+    step runs it once per step) give the eager counts each time, not counts on top of what the buffer held."""
+    from future_od.native import ops
+    g = torch.Generator().manual_seed(3)
+    B, M, C1, N = 2, 128, 9, 40
+
+    def xyxy(n, size):
+        xy = torch.rand(B, n, 2, generator=g) * size
+        return torch.cat([xy, xy + torch.rand(B, n, 2, generator=g) * 200 + 4], -1).to(DEV)
+
+    scores, boxes, anno = torch.rand(B, M, C1, generator=g).to(DEV), xyxy(M, 800), xyxy(N, 800)
+    cls = torch.randint(0, C1 - 1, (B, N), generator=g).to(DEV)
+    act = (torch.rand(B, N, generator=g) < 0.7).long().to(DEV)
+    args = (scores, boxes, anno, cls, act, (900, 1600))
+    ref = ops.od_map(*args)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        ops.od_map(*args)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = ops.od_map(*args)
+    assert int(ref[3].sum()) > 0
+    for _ in range(4):
+        graph.replay()
+        torch.cuda.synchronize()
+        for a, b in zip(out, ref):
+            assert torch.equal(a, b)

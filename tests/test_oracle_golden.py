@@ -12,7 +12,15 @@ from oracle import od_map as ood
 from oracle import stdetr as O
 from oracle.stdetr import Config
 
-torch.set_num_threads(8)
+
+@pytest.fixture(autouse=True)
+def _eight_threads():
+    """The fixtures were recorded with 8 threads (make_golden.py) and how CPU reductions are grouped follows the thread
+    count: every test here runs with 8, whatever an earlier test of the session set."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(prev)
 
 
 def close(a, b, atol=2e-5, rtol=1e-4):

@@ -1,25 +1,22 @@
 """Drop-in boundary check: every name the reference's run / eval scripts import from the package,
 every function of ours they call and every keyword they pass must resolve against THIS package.
 
-The reference scripts are only PARSED (ast) where they lie under /root/reference -- nothing of them is imported,
-executed or copied; on a box without the reference checkout (the GPU box) the test skips."""
-import ast
+What the scripts use is recorded in tests/golden/reference_surface.json (names, keywords and argument counts, written
+by tests/golden/make_surface.py from the reference checkout; nothing of the scripts is imported, executed or copied)."""
 import dataclasses
-import glob
 import importlib
 import inspect
+import json
 import os
 
 import pytest
 
-REF = "/root/reference"
+SURFACE_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_surface.json")
+with open(SURFACE_FILE) as _f:
+    SURFACE = json.load(_f)
 # the experiment / evaluation scripts (the callers of the surface); runs/_model.py, _helper.py and _loader.py ARE the
 # surface and are replaced by this package's own files of the same names
-SCRIPTS = sorted(p for p in glob.glob(os.path.join(REF, "runs", "*.py")) + glob.glob(os.path.join(REF, "runs", "eval", "*.py"))
-                 if not os.path.basename(p).startswith("_"))
-OURS = ("future_od", "runs", "config")
-
-pytestmark = pytest.mark.skipif(not SCRIPTS, reason="reference checkout not present")
+SCRIPTS = sorted(SURFACE)
 
 
 def _accepts(fn, kw):
@@ -32,58 +29,50 @@ def _accepts(fn, kw):
     return kw in sig.parameters or any(p.kind == p.VAR_KEYWORD for p in sig.parameters.values())
 
 
-@pytest.mark.parametrize("path", SCRIPTS, ids=[os.path.relpath(p, REF) for p in SCRIPTS])
+@pytest.mark.parametrize("path", SCRIPTS)
 def test_reference_script_resolves_against_the_package(path):
-    tree = ast.parse(open(path).read())
+    use = SURFACE[path]
     bound = {}                                      # local name -> object of ours
     checked = 0
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] in OURS:
-            mod = importlib.import_module(node.module)
-            for a in node.names:
-                if not hasattr(mod, a.name):            # a submodule: from future_od.datasets import nu_scenes
-                    try:
-                        importlib.import_module(f"{node.module}.{a.name}")
-                    except ImportError:
-                        pass
-                assert hasattr(mod, a.name), f"{os.path.basename(path)}: {node.module} has no {a.name}"
-                bound[a.asname or a.name] = getattr(mod, a.name)
-                checked += 1
-        elif isinstance(node, ast.Import):
-            for a in node.names:
-                if a.name.split(".")[0] in OURS:
-                    mod = importlib.import_module(a.name)
-                    bound[a.asname or a.name.split(".")[0]] = mod if a.asname else importlib.import_module(a.name.split(".")[0])
-                    checked += 1
-    for node in ast.walk(tree):
-        # attribute of an imported module / class: nu_scenes.CATEGORY_DICT, T.JointResize, transformer.MLP ...
-        if isinstance(node, ast.Attribute) and isinstance(node.value, ast.Name) and node.value.id in bound:
-            obj = bound[node.value.id]
-            if inspect.ismodule(obj) or inspect.isclass(obj):
-                assert hasattr(obj, node.attr), f"{os.path.basename(path)}: {node.value.id}.{node.attr} missing"
-                checked += 1
-        # keywords of calls to imported callables
-        if isinstance(node, ast.Call):
-            fn = None
-            if isinstance(node.func, ast.Name) and node.func.id in bound:
-                fn = bound[node.func.id]
-            elif (isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name)
-                  and node.func.value.id in bound and hasattr(bound[node.func.value.id], node.func.attr)):
-                fn = getattr(bound[node.func.value.id], node.func.attr)
-            if fn is None or not callable(fn):
-                continue
-            for kw in node.keywords:
-                if kw.arg is not None:
-                    assert _accepts(fn, kw.arg), f"{os.path.basename(path)}: {getattr(fn, '__name__', fn)}() takes no '{kw.arg}'"
-                    checked += 1
-            if not dataclasses.is_dataclass(fn) and not inspect.isclass(fn):
+    for imp in use["imports"]:
+        if "from" in imp:
+            mod = importlib.import_module(imp["from"])
+            name = imp["name"]
+            if not hasattr(mod, name):              # a submodule: from future_od.datasets import nu_scenes
                 try:
-                    params = [p for p in inspect.signature(fn).parameters.values()
-                              if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]
-                    varargs = any(p.kind == p.VAR_POSITIONAL for p in inspect.signature(fn).parameters.values())
-                    assert varargs or len(node.args) <= len(params), f"{os.path.basename(path)}: too many positionals for {fn.__name__}"
-                except (TypeError, ValueError):
+                    importlib.import_module(f"{imp['from']}.{name}")
+                except ImportError:
                     pass
+            assert hasattr(mod, name), f"{os.path.basename(path)}: {imp['from']} has no {name}"
+            bound[imp["as"] or name] = getattr(mod, name)
+        else:
+            mod = importlib.import_module(imp["import"])
+            bound[imp["as"] or imp["import"].split(".")[0]] = mod if imp["as"] else importlib.import_module(imp["import"].split(".")[0])
+        checked += 1
+    # attribute of an imported module / class: nu_scenes.CATEGORY_DICT, T.JointResize, transformer.MLP ...
+    for base, attr in use["attributes"]:
+        obj = bound[base]
+        if inspect.ismodule(obj) or inspect.isclass(obj):
+            assert hasattr(obj, attr), f"{os.path.basename(path)}: {base}.{attr} missing"
+            checked += 1
+    # keywords of calls to imported callables
+    for call in use["calls"]:
+        fn = bound[call["func"][0]]
+        if len(call["func"]) == 2:
+            fn = getattr(fn, call["func"][1], None)
+        if fn is None or not callable(fn):
+            continue
+        for kw in call["keywords"]:
+            assert _accepts(fn, kw), f"{os.path.basename(path)}: {getattr(fn, '__name__', fn)}() takes no '{kw}'"
+            checked += 1
+        if not dataclasses.is_dataclass(fn) and not inspect.isclass(fn):
+            try:
+                params = [p for p in inspect.signature(fn).parameters.values()
+                          if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]
+                varargs = any(p.kind == p.VAR_POSITIONAL for p in inspect.signature(fn).parameters.values())
+                assert varargs or call["positional"] <= len(params), f"{os.path.basename(path)}: too many positionals for {fn.__name__}"
+            except (TypeError, ValueError):
+                pass
     assert checked > 0 or os.path.basename(path) == "helpers.py"        # (helpers.py imports nothing of ours)
 
 

@@ -19,7 +19,7 @@ echo "write done"
 cd $R
 python tools/pmc_traffic.py $out/pmc_fetch $out/pmc_write 2 $out/pmc_traffic.json > $out/pmc_traffic.txt
 cp $out/pmc_traffic.json profiles/pmc_traffic.json   # so that the bench line below carries roofline.traffic
-python bench.py > $out/bench_line.json 2> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
 # MFMA-busy per entry point (SQ_VALU_MFMA_BUSY_CYCLES over 1024 SIMDs x kernel cycles)
 cd /tmp
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $out/pmc_mfma -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-roofline --no-extras --no-graph > $out/pmc_mfma.log 2>&1
