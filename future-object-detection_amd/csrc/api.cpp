@@ -32,6 +32,8 @@ extern "C" size_t fod_workspace_bytes(int kind) {
     case FOD_WS_NT_SPLIT_TICKETS: return (size_t)FOD_NT_SPLIT_TICKETS * sizeof(unsigned);
     case FOD_WS_TN_PARTIALS: return FOD_TN_WS_BYTES;
     case FOD_WS_ATTN_SPLIT_PER_TILE: return (size_t)FOD_ATTN_SPLIT_WS_FLOATS_PER_TILE * sizeof(float);
+    case FOD_WS_DET: return FOD_DET_WS_BYTES;
+    case FOD_WS_TN_MULTI_DET: return FOD_TN_MULTI_DET_WS_BYTES;
     default: return 0;
   }
 }

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "det_reduce.h"
 
 namespace {
 
@@ -114,7 +115,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
   }
 }
 
-template <typename T, int D, int LPR>
+// DET (fod_layernorm_bwd_det): dgamma points at the scratch and dbeta is unused -- a workgroup (grouped form: a row)
+// stores its [2][D] partial sums (dgamma terms, then dbeta terms) at dgamma + index * 2 * D; det_reduce_kernel sums them.
+template <typename T, int D, int LPR, bool DET = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ xs,
                                                      const float* __restrict__ mean,
                                                      const float* __restrict__ rstd,
@@ -159,8 +162,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
     ln_store<T, EPL>(dx + row * D + c0, o);
 #pragma unroll
     for (int i = 0; i < EPL; ++i) {
-      atomicAdd(dgamma + goff + i, d[i] * xh[i]);
-      atomicAdd(dbeta + goff + i, d[i]);
+      if (DET) {
+        dgamma[row * (2 * D) + c0 + i] = d[i] * xh[i];
+        dgamma[row * (2 * D) + D + c0 + i] = d[i];
+      } else {
+        atomicAdd(dgamma + goff + i, d[i] * xh[i]);
+        atomicAdd(dbeta + goff + i, d[i]);
+      }
     }
     return;
   }
@@ -208,8 +216,13 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
   }
   __syncthreads();
   for (int c = threadIdx.x; c < D; c += 256) {
-    atomicAdd(dgamma + c, sg[0][c] + sg[1][c] + sg[2][c] + sg[3][c]);
-    atomicAdd(dbeta + c, sb[0][c] + sb[1][c] + sb[2][c] + sb[3][c]);
+    if (DET) {
+      dgamma[(long)blockIdx.x * (2 * D) + c] = sg[0][c] + sg[1][c] + sg[2][c] + sg[3][c];
+      dgamma[(long)blockIdx.x * (2 * D) + D + c] = sb[0][c] + sb[1][c] + sb[2][c] + sb[3][c];
+    } else {
+      atomicAdd(dgamma + c, sg[0][c] + sg[1][c] + sg[2][c] + sg[3][c]);
+      atomicAdd(dbeta + c, sb[0][c] + sb[1][c] + sb[2][c] + sb[3][c]);
+    }
   }
 }
 
@@ -890,6 +903,58 @@ extern "C" int fod_layernorm_bwd(int dtype, const void* dy, const void* xsum, co
 #undef LN_BWD
   FOD_LAUNCH_CHECK();
   return FOD_OK;
+}
+
+// The same launches with the dgamma / dbeta terms stored per workgroup (grouped form: per row) into `ws` and summed in
+// index order by a second launch.
+extern "C" int fod_layernorm_bwd_det(int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,
+                                     const float* gamma, void* dx, float* dgamma, float* dbeta, int rows, int D,
+                                     int group_rows, void* ws, size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE_SCRATCH("layernorm_bwd_det", ws, ws_bytes, FOD_DET_WS_BYTES);
+  FOD_REQUIRE(dy && xsum && mean && rstd && gamma && dx && dgamma && dbeta && rows > 0, "layernorm_bwd_det: bad args");
+  FOD_REQUIRE(group_rows >= 0 && (group_rows == 0 || (rows % group_rows == 0 && rows <= 4096)),
+              "layernorm_bwd_det: %d rows in groups of %d (grouped form: at most 4096 rows)", rows, group_rows);
+  FOD_REQUIRE(D % 64 == 0 && D >= 64 && D <= 512, "layernorm_bwd_det: D=%d must be a multiple of 64, <= 512", D);
+  FOD_REQUIRE(((uintptr_t)dy % 16) == 0 && ((uintptr_t)xsum % 16) == 0 && ((uintptr_t)dx % 16) == 0 &&
+              ((uintptr_t)gamma % 16) == 0, "layernorm_bwd_det: operands must be 16-byte aligned");
+  float* part = reinterpret_cast<float*>(ws);
+  int grid = 0;
+  const bool few = rows < 8192;
+  if (few) {
+    grid = grid_for(rows, 16);
+    if (grid > 512) grid = 512;
+    if (group_rows > 0) grid = (rows + 3) / 4;
+  } else {
+    FOD_REQUIRE(group_rows == 0, "layernorm_bwd_det: the grouped form takes at most 4096 rows");
+  }
+#define LN_BWD_DET(DD)                                                                                        \
+  do {                                                                                                        \
+    constexpr int LPR = (DD % 128 == 0) ? 16 : 8;                                                             \
+    if (few) {                                                                                                \
+      hipLaunchKernelGGL((ln_bwd_kernel<T, DD, 64, true>), dim3(grid), dim3(256), 0, stream, (const T*)dy,    \
+                         (const T*)xsum, mean, rstd, gamma, (T*)dx, part, nullptr, rows, group_rows);         \
+    } else {                                                                                                  \
+      grid = grid_for(rows, 4 * (64 / LPR) * ln_bwd_groups());                                                \
+      if (grid > 512) grid = 512;                                                                             \
+      hipLaunchKernelGGL((ln_bwd_kernel<T, DD, LPR, true>), dim3(grid), dim3(256), 0, stream, (const T*)dy,   \
+                         (const T*)xsum, mean, rstd, gamma, (T*)dx, part, nullptr, rows, 0);                  \
+    }                                                                                                         \
+  } while (0)
+  FOD_DISPATCH_T(dtype, "layernorm_bwd_det", switch (D / 64) {
+    case 1: LN_BWD_DET(64); break; case 2: LN_BWD_DET(128); break; case 3: LN_BWD_DET(192); break;
+    case 4: LN_BWD_DET(256); break; case 5: LN_BWD_DET(320); break; case 6: LN_BWD_DET(384); break;
+    case 7: LN_BWD_DET(448); break; default: LN_BWD_DET(512); break; })
+#undef LN_BWD_DET
+  FOD_LAUNCH_CHECK();
+  // grouped: one partial per row, group g sums its group_rows rows; else one partial per workgroup
+  const int nparts = group_rows > 0 ? group_rows : grid;
+  const int groups = group_rows > 0 ? rows / group_rows : 1;
+  foddet::ReduceParams r{};
+  r.part = part; r.part_stride = 2L * D; r.part_batch = (long)nparts * 2 * D; r.part_total = r.part_batch; r.nparts = nparts;
+  r.out0 = dgamma; r.n0 = D; r.cols0 = D; r.ld0 = D; r.out0_batch = D;
+  r.out1 = dbeta; r.n1 = D; r.out1_batch = D;
+  r.accumulate = 1;
+  return det_reduce_launch(r, groups, stream);
 }
 
 // ---- out_j[g, n] = sum over the rows of group g of G_j[m, n], for several (G_j, out_j) pairs of one shape in ONE launch,

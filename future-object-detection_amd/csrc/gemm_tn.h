@@ -24,6 +24,12 @@ struct TnParams {
   float* ws;                       // gemm_tn_big.hip: per-(split, tile) partial tiles, summed by a second launch; or NULL
   float* ws_caller;                // the caller's workspace (fod_gemm_tn_acc / fod_conv2d_wgrad_acc `ws`), ws_caller_bytes long
   size_t ws_caller_bytes;
+  // Deterministic forms (`_det` entry points) only; zero otherwise.  det = 1: nothing is added with atomics -- a launch
+  // that cannot place its partial results in the caller's workspace fails instead.
+  int det;
+  float* part;                     // gemm_tn.hip: partial s = part + s * part_stride: [N1 * K2] tile sums, then [N1] column sums
+  long part_stride;
+  float* part_cs;                  // gemm_tn_big.hip: partial column sums [nsplit * waves along j][N1]
 };
 
 // gemm_tn_big.hip: the 8-wave LDS-DMA kernel for long bf16 reductions (conv weight gradients, the encoder's Linear

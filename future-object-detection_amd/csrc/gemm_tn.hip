@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "det_reduce.h"
 #include "gemm_tn.h"
 
 namespace {
@@ -62,7 +63,9 @@ FOD_DEVINL void tn_frag(Frag<float>& f, const unsigned char* tile, int ks, int c
 }
 
 // RING = depth of the register staging ring: RING-1 steps of global loads are in flight while one is computed.
-template <typename T, int MODE, int RING>
+// DET (the `_det` entry points): a launch with several M-splits stores each split's tile and column sums into
+// p.part + split * p.part_stride instead of adding them with atomics; det_reduce_kernel sums the splits in index order.
+template <typename T, int MODE, int RING, bool DET = false>
 FOD_DEVINL void gemm_tn_body(const TnParams& p, const int bid_x, const int bid_y, const int bid_z) {
   constexpr int VEC = Elem<T>::VEC;
   constexpr int PITCH = TnCfg<T>::PITCH;
@@ -279,7 +282,11 @@ FOD_DEVINL void gemm_tn_body(const TnParams& p, const int bid_x, const int bid_y
         s[e] = 0.f;
         for (int r = 0; r < RPP; ++r) s[e] += red[(r * CHR + tid) * VEC + e];
       }
-      if (p.nsplit != 1) {
+      if (DET && p.nsplit != 1) {
+        float* mine = p.part + (long)split * p.part_stride + (long)p.N1 * p.K2;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) mine[gi + e] = s[e];
+      } else if (p.nsplit != 1) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) atomicAdd(p.colsum + gi + e, s[e]);
       } else if (p.accumulate) {
@@ -317,7 +324,20 @@ FOD_DEVINL void gemm_tn_body(const TnParams& p, const int bid_x, const int bid_y
     for (int b = 0; b < 2; ++b)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] *= rs[a][r];
-  if (!single) {
+  if (DET && !single) {
+    float* mine = p.part + (long)split * p.part_stride;       // [N1][K2], compact
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int j = j0 + wj * 64 + b * 32 + (lane & 31);
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int i = i0 + wi * 64 + a * 32 + acc_row(r, lane);
+          if (i < p.N1 && j < p.K2) mine[(long)i * p.K2 + j] = acc[a][b][r];
+        }
+    }
+  } else if (!single) {
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
       const int j = j0 + wj * 64 + b * 32 + (lane & 31);
@@ -370,18 +390,27 @@ template <typename T>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
   gemm_tn_body<T, MODE_DENSE, 3>(p, blockIdx.x, blockIdx.y, blockIdx.z);
 }
+template <typename T>
+__global__ __launch_bounds__(256, 2) void gemm_tn_det_kernel(const TnParams p) {
+  gemm_tn_body<T, MODE_DENSE, 3, true>(p, blockIdx.x, blockIdx.y, blockIdx.z);
+}
 
 // MANY long bf16 weight gradients of nn.Linear layers in ONE launch (fod_gemm_tn_multi_long): block b works on block
 // blk_local[b] = (split * ti + tile_i) * tj + tile_j of job blk_job[b] (< 0: nothing).  One encoder layer's weight
 // gradients are 4 .. 32 tiles of 128 x 128 each: launched one by one they leave most of the chip idle however M is
 // split (256 x 256 outputs: 133 TFLOP/s); ~40 of them per step, none on the backward pass's critical path.
-__global__ __launch_bounds__(256, 2) void gemm_tn_multi_long_kernel(const fod_tn_job* __restrict__ jobs,
-                                                                    const int* __restrict__ blk_job,
-                                                                    const int* __restrict__ blk_local) {
+template <bool DET>
+FOD_DEVINL void gemm_tn_multi_long_body(const fod_tn_job* __restrict__ jobs, const int* __restrict__ blk_job,
+                                        const int* __restrict__ blk_local, const long* __restrict__ part_off,
+                                        float* __restrict__ ws) {
   const int jb = blk_job[blockIdx.x];
   if (jb < 0) return;
   const fod_tn_job& j = jobs[jb];
   TnParams p{};
+  if (DET) {
+    p.part = ws + part_off[jb];
+    p.part_stride = (long)j.N1 * j.K2 + (j.colsum ? j.N1 : 0);
+  }
   p.G = j.G; p.X = j.X; p.dW = j.dW;
   p.ldg = j.ldg; p.ldx = j.ldx; p.ldw = j.ldw;
   p.M = j.M; p.N1 = j.N1; p.K2 = j.K2;
@@ -395,14 +424,48 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_multi_long_kernel(const fod_tn
   p.m_per_split = j.m_per_split;
   const int local = blk_local[blockIdx.x];
   const int tile = local % (p.ti * p.tj);
-  gemm_tn_body<__bf16, MODE_DENSE, 3>(p, tile % p.tj, tile / p.tj, local / (p.ti * p.tj));
+  gemm_tn_body<__bf16, MODE_DENSE, 3, DET>(p, tile % p.tj, tile / p.tj, local / (p.ti * p.tj));
+}
+__global__ __launch_bounds__(256, 2) void gemm_tn_multi_long_kernel(const fod_tn_job* __restrict__ jobs,
+                                                                    const int* __restrict__ blk_job,
+                                                                    const int* __restrict__ blk_local) {
+  gemm_tn_multi_long_body<false>(jobs, blk_job, blk_local, nullptr, nullptr);
+}
+// fod_gemm_tn_multi_long_det: job jb's splits store their partial results at ws + part_off[jb] (part_off in floats) ...
+__global__ __launch_bounds__(256, 2) void gemm_tn_multi_long_det_kernel(const fod_tn_job* __restrict__ jobs,
+                                                                        const int* __restrict__ blk_job,
+                                                                        const int* __restrict__ blk_local,
+                                                                        const long* __restrict__ part_off,
+                                                                        float* __restrict__ ws) {
+  gemm_tn_multi_long_body<true>(jobs, blk_job, blk_local, part_off, ws);
+}
+// ... and this launch behind it adds them to dW / colsum in split order: grid (chunks, jobs), one thread per output element
+__global__ __launch_bounds__(256) void gemm_tn_multi_long_reduce_kernel(const fod_tn_job* __restrict__ jobs,
+                                                              const long* __restrict__ part_off,
+                                                              const float* __restrict__ ws) {
+  const fod_tn_job& j = jobs[blockIdx.y];
+  if (j.nsplit == 1) return;                    // one split: the first launch stored (or added to) the outputs itself
+  const long n0 = (long)j.N1 * j.K2;
+  const long n = n0 + (j.colsum ? j.N1 : 0);
+  const float* part = ws + part_off[blockIdx.y];
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
+    float acc = 0.f;
+    for (int s = 0; s < j.nsplit; ++s) acc += part[s * n + e];
+    float* dst = e < n0 ? j.dW + (e / j.K2) * j.ldw + e % j.K2 : j.colsum + (e - n0);
+    *dst += acc;                                // as the atomic form: added to what the output holds
+  }
 }
 template <typename T>
 __global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const TnParams p) {
   gemm_tn_body<T, MODE_CONV, 3>(p, blockIdx.x, blockIdx.y, blockIdx.z);
 }
-
 template <typename T>
+__global__ __launch_bounds__(256, 2) void conv2d_wgrad_det_kernel(const TnParams p) {
+  gemm_tn_body<T, MODE_CONV, 3, true>(p, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// DET (fod_colsum_acc_det): `out` is the scratch [row splits][groups * N]; row split y stores its sums there
+template <typename T, bool DET = false>
 __global__ void colsum_kernel(const T* __restrict__ G, long ldg, int M, int N, int rows_per_block,
                               int group_rows, float* __restrict__ out) {
   // block = 256 threads = 64 columns x 4 row-lanes; grid = (ceil(N/64), row splits, groups)
@@ -418,6 +481,12 @@ __global__ void colsum_kernel(const T* __restrict__ G, long ldg, int M, int N, i
     for (int m = mb + rl; m < me; m += 4) s += to_f32(G[(long)m * ldg + c]);
   red[rl][threadIdx.x & 63] = s;
   __syncthreads();
+  if (DET) {
+    if (rl == 0 && c < N)
+      out[((long)blockIdx.y * gridDim.z + blockIdx.z) * N + c] =
+          red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    return;
+  }
   if (rl == 0 && c < N)
     atomicAdd(out + (long)blockIdx.z * N + c,
               red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
@@ -670,6 +739,13 @@ int launch_tn(int dtype, TnParams& p, hipStream_t stream) {
   static const char* env_rows = getenv("FOD_TN_ROWS");       // experiment knobs (tools/): rows per split, XCD order
   static const char* env_xcd = getenv("FOD_TN_XCD");
   if (env_rows && atoi(env_rows) > 0 && p.M > 512) splits = ceil_div(p.M, atoi(env_rows));
+  // deterministic form: one partial [N1 * K2 (+ N1)] per split in the caller's workspace -- fewer, longer splits where
+  // the planned number would not fit (a single split needs no workspace: plain stores)
+  const long part_floats = (long)p.N1 * p.K2 + (p.colsum ? p.N1 : 0);
+  if (p.det) {
+    const long fit = (long)(p.ws_caller_bytes / sizeof(float)) / part_floats;
+    if (splits > fit) splits = fit < 2 ? 1 : (int)fit;
+  }
   // XCD-grouped order (all tiles of an M-split on one XCD, see the kernel): the splits are dealt to the 8 XCDs,
   // so their count is floored to a multiple of 8; taken when that costs < 10 % of the blocks (measured on the
   // backbone's wgrads: -25 % time on the 4..16-tile 1x1 / 3x3 layers, +10 % where flooring 28 -> 24 splits).
@@ -682,6 +758,31 @@ int launch_tn(int dtype, TnParams& p, hipStream_t stream) {
   p.nsplit = ceil_div(p.M, p.m_per_split);
   p.xcd_order = (want_xcd && p.nsplit >= 8) ? 1 : 0;
   const dim3 grid = p.xcd_order ? dim3(ti * tj * ((p.nsplit + 7) / 8 * 8)) : dim3(tj, ti, p.nsplit);
+  if (p.det) {
+    if (dtype != FOD_BF16 && dtype != FOD_F32) {
+      fod_set_error("gemm_tn: bad dtype %d", dtype);
+      return FOD_ERR_ARG;
+    }
+    FOD_REQUIRE_SCRATCH("gemm_tn (deterministic)", p.ws_caller, p.ws_caller_bytes,
+                        p.nsplit > 1 ? (size_t)p.nsplit * part_floats * sizeof(float) : 0);
+    p.part = p.ws_caller;
+    p.part_stride = part_floats;
+    if (dtype == FOD_BF16) {
+      if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_det_kernel<__bf16>), grid, dim3(256), 0, stream, p);
+      else hipLaunchKernelGGL((conv2d_wgrad_det_kernel<__bf16>), grid, dim3(256), 0, stream, p);
+    } else {
+      if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_det_kernel<float>), grid, dim3(256), 0, stream, p);
+      else hipLaunchKernelGGL((conv2d_wgrad_det_kernel<float>), grid, dim3(256), 0, stream, p);
+    }
+    FOD_LAUNCH_CHECK();
+    if (p.nsplit == 1) return FOD_OK;
+    foddet::ReduceParams r{};
+    r.part = p.part; r.part_stride = part_floats; r.part_total = (long)p.nsplit * part_floats; r.nparts = p.nsplit;
+    r.out0 = p.dW; r.n0 = p.N1 * p.K2; r.cols0 = p.K2; r.ld0 = p.ldw;
+    r.out1 = p.colsum; r.n1 = p.colsum ? p.N1 : 0;
+    r.accumulate = 1;                           // as the atomic form: added to what the outputs hold (zero or a gradient)
+    return det_reduce_launch(r, 1, stream);
+  }
   if (dtype == FOD_BF16) {
     if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_kernel<__bf16>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((conv2d_wgrad_kernel<__bf16>), grid, dim3(256), 0, stream, p);
@@ -746,6 +847,21 @@ extern "C" int fod_gemm_tn_multi_long(const fod_tn_job* jobs, const int* blk_job
   return FOD_OK;
 }
 
+extern "C" int fod_gemm_tn_multi_long_det(const fod_tn_job* jobs, const int* blk_job, const int* blk_local, int nblocks,
+                                          const long* part_off, int njobs, size_t part_floats, void* ws,
+                                          size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE_SCRATCH("gemm_tn_multi_long_det", ws, ws_bytes, part_floats * sizeof(float));
+  FOD_REQUIRE(jobs && blk_job && blk_local && part_off && nblocks > 0 && njobs > 0 && njobs <= 65535,
+              "gemm_tn_multi_long_det: bad args");
+  hipLaunchKernelGGL(gemm_tn_multi_long_det_kernel, dim3(nblocks), dim3(256), 0, stream, jobs, blk_job, blk_local,
+                     part_off, reinterpret_cast<float*>(ws));
+  FOD_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gemm_tn_multi_long_reduce_kernel, dim3(64, njobs), dim3(256), 0, stream, jobs, part_off,
+                     reinterpret_cast<const float*>(ws));
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}
+
 extern "C" int fod_tn_plan_long(int M, int rows_hint, int* m_per_split, int* nsplit) {
   FOD_REQUIRE(M > 0 && m_per_split && nsplit, "tn_plan_long: bad args");
   if (rows_hint < MSTEP) rows_hint = MSTEP;
@@ -756,9 +872,10 @@ extern "C" int fod_tn_plan_long(int M, int rows_hint, int* m_per_split, int* nsp
   return FOD_OK;
 }
 
-extern "C" int fod_gemm_tn_acc(int dtype, const void* G, long ldg, const void* X, long ldx, float* dW,
-                               long ldw, int M, int N1, int K2, const float* row_scale, float* colsum,
-                               int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
+namespace {
+int tn_acc_impl(int det, int dtype, const void* G, long ldg, const void* X, long ldx, float* dW, long ldw, int M, int N1,
+                int K2, const float* row_scale, float* colsum, int accumulate, void* ws, size_t ws_bytes,
+                hipStream_t stream) {
   const int vec = dtype == FOD_BF16 ? 8 : 4;
   FOD_REQUIRE(G && X && dW, "gemm_tn: null operand");
   FOD_REQUIRE(M > 0 && N1 > 0 && K2 > 0, "gemm_tn: empty problem");
@@ -772,6 +889,7 @@ extern "C" int fod_gemm_tn_acc(int dtype, const void* G, long ldg, const void* X
   p.rscale = row_scale;
   p.colsum = colsum;
   p.accumulate = accumulate;
+  p.det = det;
   p.ws_caller = reinterpret_cast<float*>(ws);
   p.ws_caller_bytes = ws ? ws_bytes : 0;
   const long esz = dtype == FOD_BF16 ? 2 : 4;
@@ -786,10 +904,24 @@ extern "C" int fod_gemm_tn_acc(int dtype, const void* G, long ldg, const void* X
   }
   return launch_tn<MODE_DENSE>(dtype, p, stream);
 }
+}  // namespace
 
-extern "C" int fod_conv2d_wgrad_acc(int dtype, const void* dy, const void* x, float* dw,
-                                    const fod_conv_geom* g, const float* row_scale, int accumulate,
-                                    void* ws, size_t ws_bytes, hipStream_t stream) {
+extern "C" int fod_gemm_tn_acc(int dtype, const void* G, long ldg, const void* X, long ldx, float* dW,
+                               long ldw, int M, int N1, int K2, const float* row_scale, float* colsum,
+                               int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return tn_acc_impl(0, dtype, G, ldg, X, ldx, dW, ldw, M, N1, K2, row_scale, colsum, accumulate, ws, ws_bytes, stream);
+}
+
+extern "C" int fod_gemm_tn_acc_det(int dtype, const void* G, long ldg, const void* X, long ldx, float* dW,
+                                   long ldw, int M, int N1, int K2, const float* row_scale, float* colsum,
+                                   int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE_SCRATCH("gemm_tn_acc_det", ws, ws_bytes, FOD_TN_WS_BYTES);
+  return tn_acc_impl(1, dtype, G, ldg, X, ldx, dW, ldw, M, N1, K2, row_scale, colsum, accumulate, ws, ws_bytes, stream);
+}
+
+namespace {
+int conv_wgrad_impl(int det, int dtype, const void* dy, const void* x, float* dw, const fod_conv_geom* g,
+                    const float* row_scale, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
   const int vec = dtype == FOD_BF16 ? 8 : 4;
   FOD_REQUIRE(dy && x && dw && g, "conv_wgrad: null operand");
   FOD_REQUIRE(g->Cin % vec == 0 && g->Cout % vec == 0, "conv_wgrad: channels %d/%d must be multiples of %d",
@@ -810,6 +942,7 @@ extern "C" int fod_conv2d_wgrad_acc(int dtype, const void* dy, const void* x, fl
   p.Hd = g->Ho; p.Wd = g->Wo;
   p.kh = g->kh; p.kw = g->kw; p.stride = g->stride; p.pad = g->pad;
   p.accumulate = accumulate;
+  p.det = det;
   p.ws_caller = reinterpret_cast<float*>(ws);
   p.ws_caller_bytes = ws ? ws_bytes : 0;
   const long esz = dtype == FOD_BF16 ? 2 : 4;
@@ -819,9 +952,24 @@ extern "C" int fod_conv2d_wgrad_acc(int dtype, const void* dy, const void* x, fl
   p.x_bytes = (unsigned)xb;
   return launch_tn<MODE_CONV>(dtype, p, stream);
 }
+}  // namespace
 
-extern "C" int fod_colsum_acc(int dtype, const void* G, long ldg, int M, int N, int group_rows, float* out,
-                              hipStream_t stream) {
+extern "C" int fod_conv2d_wgrad_acc(int dtype, const void* dy, const void* x, float* dw,
+                                    const fod_conv_geom* g, const float* row_scale, int accumulate,
+                                    void* ws, size_t ws_bytes, hipStream_t stream) {
+  return conv_wgrad_impl(0, dtype, dy, x, dw, g, row_scale, accumulate, ws, ws_bytes, stream);
+}
+
+extern "C" int fod_conv2d_wgrad_acc_det(int dtype, const void* dy, const void* x, float* dw,
+                                        const fod_conv_geom* g, const float* row_scale, int accumulate,
+                                        void* ws, size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE_SCRATCH("conv2d_wgrad_acc_det", ws, ws_bytes, FOD_TN_WS_BYTES);
+  return conv_wgrad_impl(1, dtype, dy, x, dw, g, row_scale, accumulate, ws, ws_bytes, stream);
+}
+
+namespace {
+int colsum_impl(int det, int dtype, const void* G, long ldg, int M, int N, int group_rows, float* out, void* ws,
+                size_t ws_bytes, hipStream_t stream) {
   FOD_REQUIRE(G && out && M > 0 && N > 0, "colsum: bad args");
   if (group_rows <= 0) group_rows = M;
   const int groups = ceil_div(M, group_rows);
@@ -832,6 +980,27 @@ extern "C" int fod_colsum_acc(int dtype, const void* G, long ldg, int M, int N, 
   if (splits < 1) splits = 1;
   const int rpb = (group_rows + splits - 1) / splits;
   const dim3 grid(ceil_div(N, 64), ceil_div(group_rows, rpb), groups);
+  if (det) {
+    if (dtype != FOD_BF16 && dtype != FOD_F32) {
+      fod_set_error("colsum: bad dtype %d", dtype);
+      return FOD_ERR_ARG;
+    }
+    const long per = (long)groups * N;
+    FOD_REQUIRE_SCRATCH("colsum_acc_det", ws, ws_bytes, (size_t)grid.y * per * sizeof(float));
+    float* part = reinterpret_cast<float*>(ws);
+    if (dtype == FOD_BF16)
+      hipLaunchKernelGGL((colsum_kernel<__bf16, true>), grid, dim3(256), 0, stream, (const __bf16*)G, ldg, M, N, rpb,
+                         group_rows, part);
+    else
+      hipLaunchKernelGGL((colsum_kernel<float, true>), grid, dim3(256), 0, stream, (const float*)G, ldg, M, N, rpb,
+                         group_rows, part);
+    FOD_LAUNCH_CHECK();
+    foddet::ReduceParams r{};
+    r.part = part; r.part_stride = per; r.part_total = (long)grid.y * per; r.nparts = (int)grid.y;
+    r.out0 = out; r.n0 = (int)per; r.cols0 = (int)per; r.ld0 = per;
+    r.accumulate = 1;
+    return det_reduce_launch(r, 1, stream);
+  }
   if (dtype == FOD_BF16)
     hipLaunchKernelGGL((colsum_kernel<__bf16>), grid, dim3(256), 0, stream, (const __bf16*)G, ldg, M, N, rpb,
                        group_rows, out);
@@ -844,4 +1013,16 @@ extern "C" int fod_colsum_acc(int dtype, const void* G, long ldg, int M, int N, 
   }
   FOD_LAUNCH_CHECK();
   return FOD_OK;
+}
+}  // namespace
+
+extern "C" int fod_colsum_acc(int dtype, const void* G, long ldg, int M, int N, int group_rows, float* out,
+                              hipStream_t stream) {
+  return colsum_impl(0, dtype, G, ldg, M, N, group_rows, out, nullptr, 0, stream);
+}
+
+extern "C" int fod_colsum_acc_det(int dtype, const void* G, long ldg, int M, int N, int group_rows, float* out, void* ws,
+                                  size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE_SCRATCH("colsum_acc_det", ws, ws_bytes, FOD_DET_WS_BYTES);
+  return colsum_impl(1, dtype, G, ldg, M, N, group_rows, out, ws, ws_bytes, stream);
 }

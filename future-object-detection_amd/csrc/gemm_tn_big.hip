@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "det_reduce.h"
 #include "gemm_tn.h"
 #include "lds_dma.h"
 
@@ -52,7 +53,10 @@ FOD_DEVINL Frag<__bf16> tr_frag(const unsigned char* tile, int a0, int ks) {
   return f;
 }
 
-template <int MODE, int BI, int BJ>
+// DET (deterministic dense launches with a fused bias gradient): every wave's share of the column sums goes to
+// p.part_cs by plain stores instead of atomics.  Convolutions have no fused column sums: their deterministic form is
+// this kernel as it is, with the partial tiles in the workspace.
+template <int MODE, int BI, int BJ, bool DET = false>
 __global__ __launch_bounds__(512) void tn_big_kernel(const TnParams p) {
   static_assert((BI + BJ == 384 && (BI == 128 || BI == 256)) || (BI == 256 && BJ == 256),
                 "tile shapes: 128 x 256, 256 x 128 or 256 x 256");
@@ -324,7 +328,11 @@ __global__ __launch_bounds__(512) void tn_big_kernel(const TnParams p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int i = i0 + wi * 64 + a * 32 + acc_row(r, lane);
-        if (i < p.N1) atomicAdd(p.colsum + i, cs[a][r]);
+        if (DET) {      // this wave's share of the split's column sums by a plain store, summed by det_reduce_kernel
+          if (i < p.N1) p.part_cs[(long)(split * WJ + wj) * p.N1 + i] = cs[a][r];
+        } else {
+          if (i < p.N1) atomicAdd(p.colsum + i, cs[a][r]);
+        }
       }
   }
   if (p.ws) {
@@ -414,14 +422,44 @@ int launch_shape(const TnParams& p, hipStream_t stream) {
   const char* env_ws = getenv("FOD_TN_WS");                      // "0": f32 atomics straight into dW (experiments)
   const size_t need = (size_t)ntile * p.nsplit * BI * BJ * sizeof(float);
   const bool aligned = ((uintptr_t)p.dW % 16) == 0 && p.ldw % 4 == 0;
-  if (p.nsplit > 1 && p.ws_caller && need <= p.ws_caller_bytes && aligned && ((uintptr_t)p.ws_caller % 16) == 0 &&
-      !(env_ws && env_ws[0] == '0'))
+  if (p.det) {
+    // deterministic form: the partial tiles of a split launch and every wave's share of the bias gradient (the WJ waves
+    // along j of a block add to the same column sums, also in a launch with one split) go to the workspace or the call
+    // fails; a single split's tile has one contributor per element and is added as before
+    constexpr int WJ = 512 / BI;
+    const size_t need_tiles = p.nsplit > 1 ? need : 0;
+    const size_t need_cs = p.colsum ? (size_t)p.nsplit * WJ * p.N1 * sizeof(float) : 0;
+    FOD_REQUIRE_SCRATCH("gemm_tn_big (deterministic)", p.ws_caller, p.ws_caller_bytes, need_tiles + need_cs);
+    FOD_REQUIRE(p.nsplit == 1 || aligned, "gemm_tn_big (deterministic): dW must be 16-byte aligned with ldw %% 4 == 0");
+    if (p.nsplit > 1) q.ws = p.ws_caller;
+    if (p.colsum) q.part_cs = p.ws_caller + need_tiles / sizeof(float);
+  } else if (p.nsplit > 1 && p.ws_caller && need <= p.ws_caller_bytes && aligned && ((uintptr_t)p.ws_caller % 16) == 0 &&
+             !(env_ws && env_ws[0] == '0')) {
     q.ws = p.ws_caller;
-  hipLaunchKernelGGL((tn_big_kernel<MODE, BI, BJ>), grid, dim3(512), lds, stream, q);
+  }
+  if constexpr (MODE == MODE_DENSE) {
+    if (q.part_cs) {
+      static LdsLimitOnce lds_once_det;
+      if (int rc = fod_lds_limit_once(lds_once_det, reinterpret_cast<const void*>(&tn_big_kernel<MODE, BI, BJ, true>), lds, "gemm_tn_big")) return rc;
+      hipLaunchKernelGGL((tn_big_kernel<MODE, BI, BJ, true>), grid, dim3(512), lds, stream, q);
+    } else {
+      hipLaunchKernelGGL((tn_big_kernel<MODE, BI, BJ>), grid, dim3(512), lds, stream, q);
+    }
+  } else {
+    hipLaunchKernelGGL((tn_big_kernel<MODE, BI, BJ>), grid, dim3(512), lds, stream, q);
+  }
   FOD_LAUNCH_CHECK();
   if (q.ws) {
     hipLaunchKernelGGL((tn_reduce_kernel<BI, BJ>), dim3(p.N1 * ceil_div(p.K2 / 4, 64)), dim3(256), 0, stream, q);
     FOD_LAUNCH_CHECK();
+  }
+  if (q.part_cs) {
+    constexpr int WJ = 512 / BI;
+    foddet::ReduceParams r{};
+    r.part = q.part_cs; r.part_stride = p.N1; r.part_total = (long)p.nsplit * WJ * p.N1; r.nparts = p.nsplit * WJ;
+    r.out0 = p.colsum; r.n0 = p.N1; r.cols0 = p.N1; r.ld0 = p.N1;
+    r.accumulate = 1;
+    return det_reduce_launch(r, 1, stream);
   }
   return FOD_OK;
 }

@@ -12,6 +12,7 @@
 // gemm_nt_small_kernel); the row sums meet through LDS (16 rows x 4 waves) twice (mean, then centred squares: the same
 // two-pass formula as ln_fwd_kernel, on the same bf16-rounded sum that is stored for the backward pass).
 #include "common.h"
+#include "det_reduce.h"
 
 namespace {
 
@@ -195,7 +196,8 @@ struct LanBwdParams {
 // PRE: the forward launch also computed q = y W2^T + b2 (THEN form), so the gradient of y is dy + dq . W2: that product runs
 // here first (W2^T rows as the A operand, dq rows as the B operand), its result goes through LDS once to reach the operand
 // layout the layer-norm gradient reads (every wave needs whole rows), and the launch that would have formed it is gone.
-template <bool PRE>
+// DET (fod_linear_add_norm_bwd_det): p.dgamma is the scratch, workgroup b stores its column sums at [b][2][256] there.
+template <bool PRE, bool DET = false>
 __global__ __launch_bounds__(256) void linear_add_norm_bwd_kernel(const LanBwdParams p) {
   constexpr int D = 256, KS = D / 32;
   __shared__ __attribute__((aligned(16))) __bf16 dybuf[PRE ? 16 : 1][D + 8];
@@ -331,8 +333,13 @@ __global__ __launch_bounds__(256) void linear_add_norm_bwd_kernel(const LanBwdPa
     }
     __syncthreads();                                       // ... and read, before the next tile overwrites them
   }
-  atomicAdd(p.dgamma + tid, ag);
-  atomicAdd(p.dbeta + tid, ab);
+  if (DET) {
+    p.dgamma[(long)blockIdx.x * (2 * D) + tid] = ag;
+    p.dgamma[(long)blockIdx.x * (2 * D) + D + tid] = ab;
+  } else {
+    atomicAdd(p.dgamma + tid, ag);
+    atomicAdd(p.dbeta + tid, ab);
+  }
 }
 
 // ---- out = ((relu(x W1^T + b1)) W2^T + b2) * table[m % mod]: a two-layer 256 -> 256 -> 256 MLP and the periodic multiply that
@@ -462,6 +469,9 @@ struct Mlp2BwdParams {
   int M, mod;
 };
 
+// DET (fod_mlp2_mul_bwd_det): p.dtable is the scratch [M][256]; every row's dout * q goes there by plain stores and
+// det_reduce_kernel adds the rows that share a table row in row order.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void mlp2_mul_bwd_kernel(const Mlp2BwdParams p) {
   constexpr int D = 256, KS = D / 32;
   __shared__ __attribute__((aligned(16))) __bf16 gbuf[16][D + 8];
@@ -526,7 +536,11 @@ __global__ __launch_bounds__(256) void mlp2_mul_bwd_kernel(const Mlp2BwdParams p
 #pragma unroll 4
       for (int r = 0; r < 16; ++r) {
         const int mr = m0 + r;
-        if (mr < p.M) atomicAdd(p.dtable + (long)(p.mod > 0 ? mr % p.mod : mr) * D + 64 * wave + lane, pbuf[r][64 * wave + lane]);
+        if (DET) {
+          if (mr < p.M) p.dtable[(long)mr * D + 64 * wave + lane] = pbuf[r][64 * wave + lane];
+        } else {
+          if (mr < p.M) atomicAdd(p.dtable + (long)(p.mod > 0 ? mr % p.mod : mr) * D + 64 * wave + lane, pbuf[r][64 * wave + lane]);
+        }
       }
     }
     // ---- dh^T[k, m] = sum_n W2^T[k, n] ds[m, n], gated
@@ -604,10 +618,10 @@ extern "C" int fod_linear_add_norm_fwd(int dtype, const void* a, long lda, const
   return FOD_OK;
 }
 
-extern "C" int fod_linear_add_norm_bwd(int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,
-                                       const float* gamma, const void* w_t, void* dsum, void* da, float* dgamma,
-                                       float* dbeta, int M, int N, int K, const void* pre_g, const void* pre_w_t,
-                                       hipStream_t stream) {
+namespace {
+int lan_bwd_impl(int det, int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,
+                 const float* gamma, const void* w_t, void* dsum, void* da, float* dgamma, float* dbeta, int M, int N,
+                 int K, const void* pre_g, const void* pre_w_t, void* ws, size_t ws_bytes, hipStream_t stream) {
   FOD_REQUIRE(dtype == FOD_BF16, "linear_add_norm_bwd: bf16 only (dtype %d)", dtype);
   FOD_REQUIRE((dy || pre_g) && xsum && mean && rstd && gamma && dsum && dgamma && dbeta && M > 0, "linear_add_norm_bwd: bad args");
   FOD_REQUIRE((pre_g == nullptr) == (pre_w_t == nullptr), "linear_add_norm_bwd: pre_g and pre_w_t come together");
@@ -622,10 +636,43 @@ extern "C" int fod_linear_add_norm_bwd(int dtype, const void* dy, const void* xs
   p.wt = (const __bf16*)(w_t ? w_t : xsum); p.dsum = (__bf16*)dsum; p.da = (__bf16*)da; p.dgamma = dgamma; p.dbeta = dbeta;
   p.M = M;
   p.pre_g = (const __bf16*)pre_g; p.pre_wt = (const __bf16*)pre_w_t;
+  if (det) {
+    const int grid = lan_grid(M);
+    FOD_REQUIRE_SCRATCH("linear_add_norm_bwd_det", ws, ws_bytes, (size_t)grid * 512 * sizeof(float));
+    p.dgamma = reinterpret_cast<float*>(ws);
+    p.dbeta = nullptr;
+    if (pre_g) hipLaunchKernelGGL((linear_add_norm_bwd_kernel<true, true>), dim3(grid), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((linear_add_norm_bwd_kernel<false, true>), dim3(grid), dim3(256), 0, stream, p);
+    FOD_LAUNCH_CHECK();
+    foddet::ReduceParams r{};
+    r.part = p.dgamma; r.part_stride = 512; r.part_total = (long)grid * 512; r.nparts = grid;
+    r.out0 = dgamma; r.n0 = 256; r.cols0 = 256; r.ld0 = 256;
+    r.out1 = dbeta; r.n1 = 256;
+    r.accumulate = 1;
+    return det_reduce_launch(r, 1, stream);
+  }
   if (pre_g) hipLaunchKernelGGL(linear_add_norm_bwd_kernel<true>, dim3(lan_grid(M)), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(linear_add_norm_bwd_kernel<false>, dim3(lan_grid(M)), dim3(256), 0, stream, p);
   FOD_LAUNCH_CHECK();
   return FOD_OK;
+}
+}  // namespace
+
+extern "C" int fod_linear_add_norm_bwd(int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,
+                                       const float* gamma, const void* w_t, void* dsum, void* da, float* dgamma,
+                                       float* dbeta, int M, int N, int K, const void* pre_g, const void* pre_w_t,
+                                       hipStream_t stream) {
+  return lan_bwd_impl(0, dtype, dy, xsum, mean, rstd, gamma, w_t, dsum, da, dgamma, dbeta, M, N, K, pre_g, pre_w_t, nullptr,
+                      0, stream);
+}
+
+extern "C" int fod_linear_add_norm_bwd_det(int dtype, const void* dy, const void* xsum, const float* mean,
+                                           const float* rstd, const float* gamma, const void* w_t, void* dsum, void* da,
+                                           float* dgamma, float* dbeta, int M, int N, int K, const void* pre_g,
+                                           const void* pre_w_t, void* ws, size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE_SCRATCH("linear_add_norm_bwd_det", ws, ws_bytes, FOD_DET_WS_BYTES);
+  return lan_bwd_impl(1, dtype, dy, xsum, mean, rstd, gamma, w_t, dsum, da, dgamma, dbeta, M, N, K, pre_g, pre_w_t, ws,
+                      ws_bytes, stream);
 }
 
 extern "C" int fod_mlp2_mul_fwd(int dtype, const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
@@ -647,9 +694,10 @@ extern "C" int fod_mlp2_mul_fwd(int dtype, const void* x, const void* w1, const 
   return FOD_OK;
 }
 
-extern "C" int fod_mlp2_mul_bwd(int dtype, const void* dout, const void* table, int table_rows, const void* q, const void* h,
-                                const void* w2_t, const void* w1_t, void* ds, void* dh, void* dx, float* dtable, int M,
-                                int D, hipStream_t stream) {
+namespace {
+int mlp2_bwd_impl(int det, int dtype, const void* dout, const void* table, int table_rows, const void* q, const void* h,
+                  const void* w2_t, const void* w1_t, void* ds, void* dh, void* dx, float* dtable, int M, int D, void* ws,
+                  size_t ws_bytes, hipStream_t stream) {
   FOD_REQUIRE(dtype == FOD_BF16, "mlp2_mul_bwd: bf16 only (dtype %d)", dtype);
   FOD_REQUIRE(dout && h && w2_t && w1_t && dh && dx && M > 0, "mlp2_mul_bwd: bad args");
   FOD_REQUIRE(D == 256, "mlp2_mul_bwd: built for 256 -> 256 -> 256 (D %d)", D);
@@ -661,7 +709,33 @@ extern "C" int fod_mlp2_mul_bwd(int dtype, const void* dout, const void* table, 
   p.dout = (const __bf16*)dout; p.table = (const __bf16*)table; p.q = (const __bf16*)q; p.h = (const __bf16*)h;
   p.w2t = (const __bf16*)w2_t; p.w1t = (const __bf16*)w1_t; p.ds = (__bf16*)ds; p.dh = (__bf16*)dh; p.dx = (__bf16*)dx;
   p.dtable = dtable; p.M = M; p.mod = table ? table_rows : 0;
-  hipLaunchKernelGGL(mlp2_mul_bwd_kernel, dim3(lan_grid(M)), dim3(256), 0, stream, p);
+  if (det && table) {
+    FOD_REQUIRE_SCRATCH("mlp2_mul_bwd_det", ws, ws_bytes, (size_t)M * 256 * sizeof(float));
+    p.dtable = reinterpret_cast<float*>(ws);
+    hipLaunchKernelGGL(mlp2_mul_bwd_kernel<true>, dim3(lan_grid(M)), dim3(256), 0, stream, p);
+    FOD_LAUNCH_CHECK();
+    const int trows = table_rows < M ? table_rows : M;
+    foddet::ReduceParams r{};
+    r.part = p.dtable; r.part_stride = (long)trows * 256; r.part_total = (long)M * 256; r.nparts = ceil_div(M, trows);
+    r.out0 = dtable; r.n0 = trows * 256; r.cols0 = 256; r.ld0 = 256;
+    r.accumulate = 1;
+    return det_reduce_launch(r, 1, stream);
+  }
+  hipLaunchKernelGGL(mlp2_mul_bwd_kernel<false>, dim3(lan_grid(M)), dim3(256), 0, stream, p);
   FOD_LAUNCH_CHECK();
   return FOD_OK;
+}
+}  // namespace
+
+extern "C" int fod_mlp2_mul_bwd(int dtype, const void* dout, const void* table, int table_rows, const void* q, const void* h,
+                                const void* w2_t, const void* w1_t, void* ds, void* dh, void* dx, float* dtable, int M,
+                                int D, hipStream_t stream) {
+  return mlp2_bwd_impl(0, dtype, dout, table, table_rows, q, h, w2_t, w1_t, ds, dh, dx, dtable, M, D, nullptr, 0, stream);
+}
+
+extern "C" int fod_mlp2_mul_bwd_det(int dtype, const void* dout, const void* table, int table_rows, const void* q,
+                                    const void* h, const void* w2_t, const void* w1_t, void* ds, void* dh, void* dx,
+                                    float* dtable, int M, int D, void* ws, size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE_SCRATCH("mlp2_mul_bwd_det", ws, ws_bytes, FOD_DET_WS_BYTES);
+  return mlp2_bwd_impl(1, dtype, dout, table, table_rows, q, h, w2_t, w1_t, ds, dh, dx, dtable, M, D, ws, ws_bytes, stream);
 }

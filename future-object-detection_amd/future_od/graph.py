@@ -129,7 +129,10 @@ class GraphedStep:
     # ------------------------------------------------------------------------------------------
     @staticmethod
     def _signature(data):
-        return tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in data.items() if isinstance(v, torch.Tensor)))
+        sig = tuple(sorted((k, tuple(v.shape), str(v.dtype)) for k, v in data.items() if isinstance(v, torch.Tensor)))
+        # deterministic mode (Fn.set_deterministic) selects other entry points: a graph serves the mode it was captured
+        # in, a flipped switch leads to a capture of its own
+        return sig + (("deterministic",),) if ops.is_deterministic() else sig
 
     def _check(self, data):
         if (isinstance(self.core, torch.nn.parallel.DistributedDataParallel)

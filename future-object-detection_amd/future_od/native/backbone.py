@@ -3,7 +3,7 @@
 Forward: f32 NCHW frames -> NHWC compute dtype -> implicit-GEMM convs with the frozen-BN scale
 folded into the prepared weights and shift/ReLU/residual fused in the epilogue -> [F, h, w, hidden].
 Backward: a hand-written reverse sweep (dgrad with the ReLU mask and the residual-branch gradient
-fused in its epilogue, wgrad into fp32 with atomics), stopping at the first trainable block
+fused in its epilogue, wgrad into fp32 -- with atomics on the default path, in fixed order in deterministic mode), stopping at the first trainable block
 because stem and layer1 are frozen (reference future_od/models/paper.py:102-109).
 
 Module/parameter names follow torchvision's ResNet so checkpoints load unchanged

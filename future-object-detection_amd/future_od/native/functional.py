@@ -192,6 +192,12 @@ ARENA = _ZeroArena()
 GRAD_SYNC = None
 
 
+# Deterministic mode (one switch for the whole kernel layer; see native/ops.py): Fn.set_deterministic(True), or
+# FOD_DETERMINISTIC=1 in the environment, or build_model(args) with args.deterministic.  Default: off.
+set_deterministic = ops.set_deterministic
+is_deterministic = ops.is_deterministic
+
+
 def set_grad_sync(reducer):
     global GRAD_SYNC
     GRAD_SYNC = reducer
@@ -434,13 +440,48 @@ class _WgradQueue:
         head = self._job_array(table)
         return np.concatenate([head, maps]), head.size, nblocks
 
-    def _pack_long(self, jobs):
+    def _long_plan(self, M, det):
+        """(rows per M-split, M-splits) of a long job.  Deterministic mode keeps one partial result per split in scratch
+        of bounded size (include/fod.h: FOD_TN_MULTI_DET_WS_BYTES): at most L.TN_DET_MAX_SPLITS longer splits."""
+        import ctypes as C
+        key = ("det", M) if det else M
+        plan = self._plans.get(key)
+        if plan is None:
+            rows = max(self.long_rows, -(-M // L.TN_DET_MAX_SPLITS)) if det else self.long_rows
+            mps, ns = C.c_int(), C.c_int()
+            L.call("fod_tn_plan_long", M, rows, C.addressof(mps), C.addressof(ns))
+            plan = self._plans[key] = (mps.value, ns.value)
+        return plan
+
+    def _det_floats(self, job):
+        """Scratch floats of a long job in a deterministic launch: one [N1 x K2 (+ N1)] partial per M-split."""
+        ns = self._long_plan(job[7], True)[1]
+        return ns * (job[8] * job[9] + (job[8] if job[3] else 0)) if ns > 1 else 0
+
+    def det_groups(self, jobs):
+        """The long jobs of a flush cut into launches whose partial results fit the deterministic scratch (launches of
+        one stream are ordered: they share it)."""
+        cap = L.LIB.fod_workspace_bytes(L.WS_TN_MULTI_DET) // 4
+        groups, floats = [[]], 0
+        for j in jobs:
+            need = self._det_floats(j)
+            if need > cap:
+                raise L.FodError(f"deterministic mode: a {j[8]} x {j[9]} weight gradient needs {4 * need} bytes of scratch, "
+                                 f"more than fod_workspace_bytes(WS_TN_MULTI_DET) = {4 * cap}")
+            if groups[-1] and floats + need > cap:
+                groups.append([])
+                floats = 0
+            groups[-1].append(j)
+            floats += need
+        return groups
+
+    def _pack_long(self, jobs, det=False):
         """Table + block maps of a fod_gemm_tn_multi_long launch.  The blocks of one M-split of a job re-read the same
         rows of G and X: they go to ONE XCD (block ids congruent mod 8 share an L2), splits dealt round-robin; idle
-        blocks (job -1) pad the shorter XCD queues."""
-        import ctypes as C
+        blocks (job -1) pad the shorter XCD queues.  det: the plan of deterministic mode, and behind the maps one i64
+        per job (table order): where in the scratch its partial results start (floats)."""
         import numpy as np
-        key = ("long",) + tuple((j[7], j[8], j[9]) for j in jobs)
+        key = ("long-det" if det else "long",) + tuple((j[7], j[8], j[9]) + ((j[3] != 0,) if det else ()) for j in jobs)
         cached = self._maps.get(key)
         if cached is None:
             order = sorted(range(len(jobs)), key=lambda i: -jobs[i][7] * jobs[i][8] * jobs[i][9])
@@ -449,11 +490,7 @@ class _WgradQueue:
             turn = 0
             for slot, i in enumerate(order):
                 j = jobs[i]
-                plan = self._plans.get(j[7])
-                if plan is None:
-                    mps, ns = C.c_int(), C.c_int()
-                    L.call("fod_tn_plan_long", j[7], self.long_rows, C.addressof(mps), C.addressof(ns))
-                    plan = self._plans[j[7]] = (mps.value, ns.value)
+                plan = self._long_plan(j[7], det)
                 plans.append(plan)
                 ntile = ((j[8] + 127) // 128) * ((j[9] + 127) // 128)
                 for sp in range(plan[1]):
@@ -469,12 +506,20 @@ class _WgradQueue:
                     bl[at:at + ntile, xcd] = np.arange(first, first + ntile, dtype=np.int32)
                     at += ntile
             maps = np.concatenate([bj.reshape(-1), bl.reshape(-1)]).view(np.uint8)
+            part_floats = 0
+            if det:
+                offs = []
+                for i in order:
+                    offs.append(part_floats)
+                    part_floats += self._det_floats(jobs[i])
+                maps = np.concatenate([maps, np.asarray(offs, dtype=np.int64).view(np.uint8)])
             if len(self._maps) > 64:
                 self._maps.clear()
-            cached = self._maps[key] = (order, plans, maps, depth * 8)
-        order, plans, maps, nblocks = cached
+            cached = self._maps[key] = (order, plans, maps, depth * 8, part_floats)
+        order, plans, maps, nblocks, part_floats = cached
         head = self._job_array([jobs[i][:12] + (0, jobs[i][12]) + plans[k] for k, i in enumerate(order)])
-        return np.concatenate([head, maps]), head.size, nblocks
+        raw = np.concatenate([head, maps])
+        return (raw, head.size, nblocks, part_floats) if det else (raw, head.size, nblocks)
 
     def _top_up(self, device):
         while len(self._spares) < 8:
@@ -496,15 +541,23 @@ class _WgradQueue:
         dev = keep[0][0].device
         if jobs:
             self._launch("fod_gemm_tn_multi", jobs, members, dev, keep)
-        if long_jobs:
+        if long_jobs and ops.is_deterministic():
+            for group in self.det_groups(long_jobs):
+                self._launch("fod_gemm_tn_multi_long_det", group, {}, dev, keep)
+        elif long_jobs:
             self._launch("fod_gemm_tn_multi_long", long_jobs, {}, dev, keep)
 
     def _launch(self, entry, jobs, members, dev, keep):
-        long = entry == "fod_gemm_tn_multi_long"
+        det = entry == "fod_gemm_tn_multi_long_det"
+        long = det or entry == "fod_gemm_tn_multi_long"
         sig = (entry, tuple(jobs), tuple((i, tuple(m)) for i, m in sorted(members.items())))
         tab = self._tables.get(sig)
         if tab is None:
-            raw, off, nblocks = self._pack_long(jobs) if long else self._pack(jobs, members)
+            part_floats = 0
+            if det:
+                raw, off, nblocks, part_floats = self._pack_long(jobs, det=True)
+            else:
+                raw, off, nblocks = self._pack_long(jobs) if long else self._pack(jobs, members)
             if torch.cuda.is_current_stream_capturing():
                 if not self._spares or raw.size > self.SPARE_BYTES or self._spares[-1][1].device != dev:
                     return self._one_by_one(jobs, members, long)
@@ -512,17 +565,19 @@ class _WgradQueue:
                 self._baked.append((pin, table))         # the graph reads both at every replay: never reused
                 pin[:raw.size].copy_(torch.from_numpy(raw))
                 table[:raw.size].copy_(pin[:raw.size], non_blocking=True)
-                tab = (table, off, nblocks)
+                tab = (table, off, nblocks, part_floats)
             else:
                 table = torch.from_numpy(raw).pin_memory().to(dev, non_blocking=True)
-                tab = (table, off, nblocks)
+                tab = (table, off, nblocks, part_floats)
                 if len(self._tables) >= 32:
                     self._tables.clear()
                 self._tables[sig] = tab
                 self._top_up(dev)
-        table, off, nblocks = tab
+        table, off, nblocks, part_floats = tab
         base = table.data_ptr()
-        L.call(entry, base, base + off, base + off + 4 * nblocks, nblocks, ops.stream(),
+        # deterministic: the per-job scratch offsets follow the two block maps; the scratch is the current stream's
+        extra = ((base + off + 8 * nblocks, len(jobs), part_floats) + ops.det_workspace(dev, L.WS_TN_MULTI_DET)) if det else ()
+        L.call(entry, base, base + off, base + off + 4 * nblocks, nblocks, *extra, ops.stream(),
                work=sum(2.0 * j[7] * j[8] * j[9] for j in jobs)
                + sum(2.0 * m[7] * m[8] * m[9] for ms in members.values() for m in ms), tag="fod_gemm_tn_acc")
         self.launches += 1
@@ -531,9 +586,10 @@ class _WgradQueue:
     def _one_by_one(self, jobs, members, long=False):
         if long:
             for G, X, dW, cs, ldg, ldx, ldw, M, N1, K2, acc, _sc, _ss in jobs:
-                ws, ws_bytes = ops.tn_workspace(torch.device("cuda", torch.cuda.current_device())) if M >= 8192 else (None, 0)
-                L.call("fod_gemm_tn_acc", L.BF16, G, ldg, X, ldx, dW, ldw, M, N1, K2, 0, cs, 1, ws, ws_bytes, ops.stream(),
-                       work=2.0 * M * N1 * K2)
+                det = ops.is_deterministic()
+                ws, ws_bytes = ops.tn_workspace(torch.device("cuda", torch.cuda.current_device())) if M >= 8192 or det else (None, 0)
+                L.call("fod_gemm_tn_acc_det" if det else "fod_gemm_tn_acc", L.BF16, G, ldg, X, ldx, dW, ldw, M, N1, K2, 0, cs, 1, ws, ws_bytes, ops.stream(),
+                       work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
             return
         for i, (G, X, dW, cs, ldg, ldx, ldw, M, N1, K2, acc, seg_cols, seg_stride) in enumerate(jobs):
             L.call("fod_gemm_tn_grouped", L.BF16, G, ldg, seg_cols, seg_stride, X, ldx, dW, ldw, M, N1, K2, cs,
@@ -823,7 +879,7 @@ def _queued_linear_wgrad(weight, bias, g, x, need_w, need_b):
 
 class TableGradAcc:
     """One f32 accumulation buffer for the gradient of a table that several Mlp2MulFn nodes multiply by (the decoder
-    layers' query_scale(x) * sine embedding): every node's backward launch adds into it with atomics; the node that runs
+    layers' query_scale(x) * sine embedding): every node's backward launch adds into it (atomics on the default path, row-ordered sums in deterministic mode); the node that runs
     LAST in the backward pass (the first in the forward pass: later layers depend on its output) hands the total on --
     one gradient instead of one per layer that autograd would sum with kernels of its own."""
 
@@ -1138,7 +1194,7 @@ def linear_add_norm_then(a, x, weight, bias, gamma, beta, then_weight, then_bias
 class ConvFn(Function):
     """y = act(conv2d(x, W) + b) on NHWC activations: a stand-alone trainable convolution (the backbone has its own
     whole-network node, native/backbone.py).  W is an OIHW parameter (any strides with a dense tap plane), stride 1,
-    padding k // 2.  Backward: ReLU mask, input gradient, weight gradient (f32 atomics into a [Cout][kh][kw][Cin]
+    padding k // 2.  Backward: ReLU mask, input gradient, weight gradient (f32 atomics on the default path, fixed-order partial sums in deterministic mode, into a [Cout][kh][kw][Cin]
     buffer returned as an OIHW view), bias gradient."""
 
     @staticmethod
@@ -1243,6 +1299,16 @@ def mix64(x):
 
 
 DROP_SEEDS = _DropSeeds()
+
+
+def manual_seed(seed):
+    """torch.manual_seed(seed) AND a restart of the dropout call counter (and of the device-side base captured steps
+    advance): two trainings in ONE process draw the same masks only if both start here -- torch.manual_seed alone
+    leaves the counter where the first training stopped.  A fresh process starts at zero by itself."""
+    torch.manual_seed(seed)
+    DROP_SEEDS.count = 0
+    if ops.DROP_BASE is not None:
+        ops.DROP_BASE.zero_()          # in place: captured graphs hold its address
 
 
 class DropoutFn(Function):

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libfod_hip.so"))
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 F32, BF16 = 0, 1
 EW_ADD, EW_MUL, EW_RELU_MASK, EW_SCALE, EW_ADD3, EW_RELU, EW_COPY_B = range(7)
@@ -134,9 +134,18 @@ SIGNATURES = {
     "fod_multi_sqnorm_acc": [_p, _p, _p, _p, _i, _p, _p],
     "fod_multi_sqnorm_det": [_p, _p, _p, _p, _i, _p, _p, _p],
     "fod_multi_adamw": [_p, _p, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _f, _p],
+    # deterministic twins: the same arguments plus (ws, ws_bytes) in front of the stream
+    "fod_gemm_tn_acc_det": [_i, _p, _l, _p, _l, _p, _l, _i, _i, _i, _p, _p, _i, _p, C.c_size_t, _p],
+    "fod_gemm_tn_multi_long_det": [_p, _p, _p, _i, _p, _i, C.c_size_t, _p, C.c_size_t, _p],
+    "fod_colsum_acc_det": [_i, _p, _l, _i, _i, _i, _p, _p, C.c_size_t, _p],
+    "fod_conv2d_wgrad_acc_det": [_i, _p, _p, _p, _CG, _p, _i, _p, C.c_size_t, _p],
+    "fod_linear_add_norm_bwd_det": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, C.c_size_t, _p],
+    "fod_mlp2_mul_bwd_det": [_i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p],
+    "fod_layernorm_bwd_det": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
 }
 EXPORTS = sorted(list(SIGNATURES) + ["fod_last_error", "fod_abi_version", "fod_multi_chunk", "fod_workspace_bytes"])
-WS_NT_SPLIT, WS_NT_SPLIT_TICKETS, WS_TN_PARTIALS, WS_ATTN_SPLIT_PER_TILE = range(4)      # fod_workspace_bytes(kind)
+WS_NT_SPLIT, WS_NT_SPLIT_TICKETS, WS_TN_PARTIALS, WS_ATTN_SPLIT_PER_TILE, WS_DET, WS_TN_MULTI_DET = range(6)   # fod_workspace_bytes(kind)
+TN_DET_MAX_SPLITS = 4      # FOD_TN_DET_MAX_SPLITS: M-splits per job of a deterministic fod_gemm_tn_multi_long_det plan
 
 
 def _load():

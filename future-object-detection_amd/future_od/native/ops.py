@@ -3,6 +3,7 @@ an out-of-bounds access on the GPU), output allocation through torch (which owns
 memory), launch on torch's current HIP stream.  No arithmetic happens in this file."""
 import ctypes as C
 import math
+import os
 
 import torch
 
@@ -85,8 +86,36 @@ def preallocate_graph_workspaces(device):
     """Called by future_od/graph.py BEFORE a capture: the scratch buffers captured launches use exist already, so their
     allocation and zero-fill do not become nodes of the graph (a 64 MiB memset per replay otherwise)."""
     device = torch.device(device)
-    for kind in (L.WS_NT_SPLIT, L.WS_NT_SPLIT_TICKETS, L.WS_TN_PARTIALS):
+    kinds = (L.WS_NT_SPLIT, L.WS_NT_SPLIT_TICKETS, L.WS_TN_PARTIALS)
+    if _DETERMINISTIC:
+        kinds += (L.WS_DET, L.WS_TN_MULTI_DET)
+    for kind in kinds:
         _workspace(kind, device, captured=True)
+
+
+# ---- deterministic mode ---------------------------------------------------------------------------------------------
+# Off (the default): the weight / bias / norm-parameter gradients that several workgroups contribute to are added with
+# f32 atomics, so their last bits depend on which workgroup finishes first.  On: every wrapper below that reaches such a
+# kernel calls its `_det` twin (include/fod.h) and hands it scratch from _workspace(): partial results by plain stores,
+# summed in index order -- gradients, and with them parameters and Adam moments, are bit-identical from run to run
+# on one GPU (more than one rank: the all-reduce's summation order is RCCL's and not covered).  The library keeps no
+# state: the mode is this module's, and an argument (the entry point called) for the library.
+_DETERMINISTIC = os.environ.get("FOD_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(flag):
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(flag)
+
+
+def is_deterministic():
+    return _DETERMINISTIC
+
+
+def det_workspace(device, kind=L.WS_DET):
+    """(address, bytes) of the scratch a deterministic entry point is handed, for the current stream."""
+    ws = _workspace(kind, device)
+    return ws.data_ptr(), ws.numel() * 4
 
 
 def _epi(scale=None, shift=None, residual=None, ld_residual=0, residual_row_mod=0, relu_mask=None,
@@ -184,10 +213,10 @@ def gemm_tn_acc(g, x, dw, row_scale=None, colsum=None, zeroed=False):
         _chk(row_scale, "row_scale", torch.float32); assert row_scale.numel() == N1
     if colsum is not None:
         _chk(colsum, "colsum", torch.float32); assert colsum.numel() == N1
-    ws, ws_bytes = tn_workspace(g.device) if M >= 8192 else (None, 0)      # only long reductions take partial tiles
-    call("fod_gemm_tn_acc", dt(g), ptr(g), N1, ptr(x), K2, ptr(dw), K2, M, N1, K2, ptr(row_scale), ptr(colsum),
+    ws, ws_bytes = tn_workspace(g.device) if M >= 8192 or _DETERMINISTIC else (None, 0)   # only long reductions take partial tiles
+    call("fod_gemm_tn_acc_det" if _DETERMINISTIC else "fod_gemm_tn_acc", dt(g), ptr(g), N1, ptr(x), K2, ptr(dw), K2, M, N1, K2, ptr(row_scale), ptr(colsum),
          0 if zeroed else 1, ws, ws_bytes, stream(),
-         work=2.0 * M * N1 * K2)
+         work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
     return dw
 
 
@@ -248,7 +277,10 @@ def colsum_acc(g, out, group_rows=0):
     M = g.numel() // N
     groups = 1 if group_rows <= 0 else (M + group_rows - 1) // group_rows
     assert out.numel() == groups * N, (g.shape, out.shape, group_rows)
-    call("fod_colsum_acc", dt(g), ptr(g), N, M, N, group_rows, ptr(out), stream())
+    if _DETERMINISTIC:
+        call("fod_colsum_acc_det", dt(g), ptr(g), N, M, N, group_rows, ptr(out), *det_workspace(g.device), stream())
+    else:
+        call("fod_colsum_acc", dt(g), ptr(g), N, M, N, group_rows, ptr(out), stream())
     return out
 
 
@@ -370,10 +402,10 @@ def conv2d_wgrad_acc(dy, x, dw, geom, row_scale=None, zeroed=False):
     assert dw.numel() == geom.Cout * geom.kh * geom.kw * geom.Cin
     if row_scale is not None:
         _chk(row_scale, "row_scale", torch.float32); assert row_scale.numel() == geom.Cout
-    ws, ws_bytes = tn_workspace(dy.device) if dy.numel() // geom.Cout >= 8192 else (None, 0)
-    call("fod_conv2d_wgrad_acc", dt(dy), ptr(dy), ptr(x), ptr(dw), _Addr(geom), ptr(row_scale),
+    ws, ws_bytes = tn_workspace(dy.device) if dy.numel() // geom.Cout >= 8192 or _DETERMINISTIC else (None, 0)
+    call("fod_conv2d_wgrad_acc_det" if _DETERMINISTIC else "fod_conv2d_wgrad_acc", dt(dy), ptr(dy), ptr(x), ptr(dw), _Addr(geom), ptr(row_scale),
          0 if zeroed else 1, ws, ws_bytes, stream(),
-         work=_conv_flops(geom))
+         work=_conv_flops(geom), tag="fod_conv2d_wgrad_acc")
     return dw
 
 
@@ -715,8 +747,10 @@ def linear_add_norm_bwd(dy, xsum, mean, rstd, gamma, w_t, dgamma, dbeta, want_da
     _chk(dgamma, "dgamma", torch.float32); _chk(dbeta, "dbeta", torch.float32)
     dsum = torch.empty_like(xsum)
     da = torch.empty((M, K), dtype=xsum.dtype, device=xsum.device) if want_da else None
-    call("fod_linear_add_norm_bwd", dt(xsum), ptr(dy), ptr(xsum), ptr(mean), ptr(rstd), ptr(gamma), ptr(w_t), ptr(dsum),
-         ptr(da), ptr(dgamma), ptr(dbeta), M, N, K, ptr(pre_g), ptr(pre_w_t), stream(),
+    det = det_workspace(xsum.device) if _DETERMINISTIC else ()
+    call("fod_linear_add_norm_bwd_det" if det else "fod_linear_add_norm_bwd", dt(xsum), ptr(dy), ptr(xsum), ptr(mean),
+         ptr(rstd), ptr(gamma), ptr(w_t), ptr(dsum),
+         ptr(da), ptr(dgamma), ptr(dbeta), M, N, K, ptr(pre_g), ptr(pre_w_t), *det, stream(),
          work=2.0 * M * N * K * ((1 if want_da else 0) + (1 if pre_g is not None else 0)), tag="fod_gemm_nt")
     return dsum, da
 
@@ -757,7 +791,8 @@ def mlp2_mul_fwd(x, w1, b1, w2, b2, table=None):
 
 
 def mlp2_mul_bwd(dout, table, q, h, w2_t, w1_t, dtable):
-    """Backward of mlp2_mul_fwd in one launch: (ds, dh, dx); dtable f32 [table_rows, D] += dout * q (atomics)."""
+    """Backward of mlp2_mul_fwd in one launch: (ds, dh, dx); dtable f32 [table_rows, D] += dout * q (atomics on the
+    default path; in deterministic mode per-row products in scratch, summed in row order by a second launch)."""
     _chk(dout, "dout", torch.bfloat16); _chk(h, "h", torch.bfloat16)
     _chk(w2_t, "w2_t", torch.bfloat16); _chk(w1_t, "w1_t", torch.bfloat16)
     D = dout.shape[-1]
@@ -772,8 +807,10 @@ def mlp2_mul_bwd(dout, table, q, h, w2_t, w1_t, dtable):
         ds = torch.empty((M, D), dtype=dout.dtype, device=dout.device)
     dh = torch.empty((M, D), dtype=dout.dtype, device=dout.device)
     dx = torch.empty((M, D), dtype=dout.dtype, device=dout.device)
-    call("fod_mlp2_mul_bwd", dt(dout), ptr(dout), ptr(table), rows_t, ptr(q), ptr(h), ptr(w2_t), ptr(w1_t), ptr(ds), ptr(dh),
-         ptr(dx), ptr(dtable), M, D, stream(), work=4.0 * M * D * D, tag="fod_gemm_nt")
+    det = det_workspace(dout.device) if _DETERMINISTIC else ()
+    call("fod_mlp2_mul_bwd_det" if det else "fod_mlp2_mul_bwd", dt(dout), ptr(dout), ptr(table), rows_t, ptr(q), ptr(h),
+         ptr(w2_t), ptr(w1_t), ptr(ds), ptr(dh),
+         ptr(dx), ptr(dtable), M, D, *det, stream(), work=4.0 * M * D * D, tag="fod_gemm_nt")
     return (ds if table is not None else dout), dh, dx
 
 
@@ -787,8 +824,9 @@ def layernorm_bwd(dy, xsum, mean, rstd, gamma, dgamma, dbeta, group_rows=0):
     for t in (gamma, dgamma, dbeta):
         _chk(t, "gamma/dgamma/dbeta", torch.float32); assert t.numel() == groups * D
     dx = torch.empty_like(dy)
-    call("fod_layernorm_bwd", dt(dy), ptr(dy), ptr(xsum), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
-         ptr(dgamma), ptr(dbeta), rows, D, group_rows, stream())
+    det = det_workspace(dy.device) if _DETERMINISTIC else ()
+    call("fod_layernorm_bwd_det" if det else "fod_layernorm_bwd", dt(dy), ptr(dy), ptr(xsum), ptr(mean), ptr(rstd),
+         ptr(gamma), ptr(dx), ptr(dgamma), ptr(dbeta), rows, D, group_rows, *det, stream())
     return dx
 
 

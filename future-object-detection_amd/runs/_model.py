@@ -5,6 +5,8 @@ reference's literals, so the reference's run scripts work unchanged:
 
     args.compute_dtype : "bf16" (default) | "fp32"      -- arithmetic mode of the kernels
     args.attn_dtype    : "bf16" | "fp8" | "fp8-all"    -- MX-fp8 attention cores (eval-mode math; csrc/attention_fp8.hip)
+    args.deterministic : True | False                  -- bit-reproducible gradients / training steps on one GPU
+                                                          (Fn.set_deterministic; default: FOD_DETERMINISTIC, off)
     args.num_images    : decoder cross-attention blocks (reference literal: 2)
     args.backbone      : "resnet50" (reference literal) | "resnet18" | "resnet34"
     args.skip_dead_frames : True (default) -- do not compute frames that cannot reach the output
@@ -83,6 +85,11 @@ def build_model(args, detr_args: SpatioTemporalDETRArgs):
         # BASELINE.json configs[4]: "fp8" = MX-fp8 QK^T / PV in the long-sequence attention launches (the encoder's
         # self-attention), "fp8-all" = in every attention launch; a process-wide switch of the kernel layer
         Fn.ATTN_FP8["mode"] = {"bf16": "off", "fp8": "long", "fp8-all": "all"}[attn_dtype]
+    deterministic = getattr(args, "deterministic", None)
+    if deterministic is not None:
+        # fixed-order sums instead of f32 atomics in the backward pass; like attn_dtype a process-wide switch of the
+        # kernel layer (one GPU: the all-reduce of a data-parallel run keeps RCCL's summation order)
+        Fn.set_deterministic(bool(deterministic))
     core.skip_dead_frames = bool(getattr(args, "skip_dead_frames", True))
     model = SpatioTemporalDETR(args=detr_args, model=core)
     model.to(args.device)

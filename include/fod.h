@@ -17,6 +17,14 @@
  *   - return 0 on success; on failure a code below, text via fod_last_error().
  *   - `_acc` entry points ADD into their f32 output (global atomics): zero it first or pass a
  *     gradient buffer to accumulate into.
+ *   - `_det` entry points are the DETERMINISTIC twins of the entry points that add with f32 atomics (whose sums depend on
+ *     which workgroup finishes first): same arguments plus `void* ws, size_t ws_bytes` in front of the stream.  Every
+ *     contributing workgroup stores its partial result into `ws` with plain stores and a short second launch on the
+ *     same stream adds the partials in index order -- for fixed arguments, one GPU and one build the outputs are
+ *     bit-identical from call to call.  The result may differ in the last bits from the atomic twin's and depends on
+ *     the launch geometry, never on timing.  `ws` is never optional: a NULL, misaligned (16 bytes) or too small scratch
+ *     returns FOD_ERR_ARG, there is no fallback to atomics.  Sizes: see "Scratch of the deterministic forms" below.
+ *     Nothing is kept in `ws` between calls and it need not be zeroed; launches of ONE stream may share it.
  */
 #ifndef FOD_H_
 #define FOD_H_
@@ -37,7 +45,7 @@ enum { FOD_OK = 0, FOD_ERR_ARG = 1, FOD_ERR_LAUNCH = 2, FOD_ERR_RUNTIME = 3 };
 size_t fod_last_error(char* buf, size_t cap);
 /* ABI version of this header; the loader refuses a library that disagrees. */
 int fod_abi_version(void);
-#define FOD_ABI_VERSION 4
+#define FOD_ABI_VERSION 5
 
 /* Fused epilogue of the NT contraction family.  In order:
  *   v = acc * scale[n] + shift[n];  v += residual[row(m), n];  v = relu ? max(v,0) : v;
@@ -67,8 +75,24 @@ typedef struct fod_epilogue {
 #define FOD_TN_WS_BYTES ((size_t)64 << 20)
 /* The library allocates NO device memory and keeps no device state: every scratch is the caller's (the attention key
  * split: fod_attn_shape.split_ws; the two above).  Sizes, for bindings that cannot read macros: */
-enum { FOD_WS_NT_SPLIT = 0, FOD_WS_NT_SPLIT_TICKETS = 1, FOD_WS_TN_PARTIALS = 2, FOD_WS_ATTN_SPLIT_PER_TILE = 3 };
+enum { FOD_WS_NT_SPLIT = 0, FOD_WS_NT_SPLIT_TICKETS = 1, FOD_WS_TN_PARTIALS = 2, FOD_WS_ATTN_SPLIT_PER_TILE = 3,
+       FOD_WS_DET = 4, FOD_WS_TN_MULTI_DET = 5 };
 size_t fod_workspace_bytes(int kind);
+/* Scratch of the deterministic forms (the least a `_det` entry point accepts, whatever the shape; a shape that would need
+ * more is split less finely, or -- where it cannot be -- refused):
+ *   fod_gemm_tn_acc_det, fod_conv2d_wgrad_acc_det                     FOD_TN_WS_BYTES  (FOD_WS_TN_PARTIALS)
+ *       one [N1 x K2 (+ N1)] f32 partial per M-split; the split count is lowered until they fit
+ *   fod_colsum_acc_det, fod_layernorm_bwd_det, fod_linear_add_norm_bwd_det, fod_mlp2_mul_bwd_det
+ *                                                                     FOD_DET_WS_BYTES (FOD_WS_DET)
+ *       [workgroups][2][D] column sums (grouped layer norm: [rows <= 4096][2][D <= 512] = this bound);
+ *       fod_mlp2_mul_bwd_det: [M][256], i.e. M <= 16384 rows
+ *   fod_gemm_tn_multi_long_det                                        FOD_TN_MULTI_DET_WS_BYTES (FOD_WS_TN_MULTI_DET)
+ *       sum over the launch's jobs of nsplit * (N1 * K2 (+ N1)) floats.  The bound holds for a caller that plans at
+ *       most FOD_TN_DET_MAX_SPLITS M-splits per job (fod_tn_plan_long with rows_hint >= M / FOD_TN_DET_MAX_SPLITS) and
+ *       starts a new launch when the next job would not fit: 8 M output elements per launch at 4 splits. */
+#define FOD_DET_WS_BYTES ((size_t)16 << 20)
+#define FOD_TN_MULTI_DET_WS_BYTES ((size_t)128 << 20)
+#define FOD_TN_DET_MAX_SPLITS 4
 
 /* C[m,n] = epi( sum_k A[(m % a_row_mod) , k] * B[n, k] )      A:[*,K] lda, B:[N,K] ldb, C:[M,N] ldc
  * Replaces nn.Linear forward (B = weight) and input-gradient (B = weight^T) on the path:
@@ -150,9 +174,22 @@ int fod_gemm_tn_multi(const fod_tn_job* jobs, const int* blk_job, const int* blk
 int fod_gemm_tn_multi_long(const fod_tn_job* jobs, const int* blk_job, const int* blk_local, int nblocks,
                            fod_stream_t stream);
 int fod_tn_plan_long(int M, int rows_hint, int* m_per_split, int* nsplit);
+/* Deterministic twins (see the conventions at the top).  fod_gemm_tn_multi_long_det: job j's M-splits store their
+ * partial tiles and column sums at ws + part_off[j] FLOATS (part_off: device array of njobs offsets, job j owning
+ * jobs[j].nsplit * (N1 * K2 + (colsum ? N1 : 0)) floats from there; jobs with one split own none); part_floats = the
+ * total the table needs, checked against ws_bytes.  A second launch adds each job's splits to dW / colsum in split
+ * order. */
+int fod_gemm_tn_acc_det(int dtype, const void* G, long ldg, const void* X, long ldx, float* dW, long ldw,
+                        int M, int N1, int K2, const float* row_scale, float* colsum, int accumulate,
+                        void* ws, size_t ws_bytes, fod_stream_t stream);
+int fod_gemm_tn_multi_long_det(const fod_tn_job* jobs, const int* blk_job, const int* blk_local, int nblocks,
+                               const long* part_off, int njobs, size_t part_floats, void* ws, size_t ws_bytes,
+                               fod_stream_t stream);
 
 int fod_colsum_acc(int dtype, const void* G, long ldg, int M, int N, int group_rows, float* out,
                    fod_stream_t stream);
+int fod_colsum_acc_det(int dtype, const void* G, long ldg, int M, int N, int group_rows, float* out, void* ws,
+                       size_t ws_bytes, fod_stream_t stream);
 
 /* Many fod_permute3_cast jobs in one launch: dst[i0*t0 + i1*t1 + i2] = src[i0*s0 + i1*s1 + i2*s2] * scale[...]
  * for i1 < valid1 and i2 < valid2, else 0.  `jobs` is a DEVICE array; block b handles chunk blk_chunk[b]
@@ -205,6 +242,8 @@ int fod_conv2d_dgrad(int dtype, const void* dy, const void* w_t, void* dx, const
 int fod_conv2d_wgrad_acc(int dtype, const void* dy, const void* x, float* dw, const fod_conv_geom* g,
                          const float* row_scale, int accumulate, void* ws /* optional, as fod_gemm_tn_acc */,
                          size_t ws_bytes, fod_stream_t stream);
+int fod_conv2d_wgrad_acc_det(int dtype, const void* dy, const void* x, float* dw, const fod_conv_geom* g,
+                             const float* row_scale, int accumulate, void* ws, size_t ws_bytes, fod_stream_t stream);
 
 /* One FROZEN 64-channel bottleneck block in one launch (csrc/bottleneck_fused.hip; torchvision Bottleneck with
  * FrozenBatchNorm2d, reference paper.py:94-98, for the blocks that keep nothing for backward, paper.py:102-109):
@@ -340,6 +379,10 @@ int fod_linear_add_norm_bwd(int dtype, const void* dy, const void* xsum, const f
                             /* optional (the forward call had then_*): the gradient of y is dy + pre_g . then_w, with
                              * pre_g [M, 256] the gradient of then_out and pre_w_t = then_w^T as [256][256]; dy may be NULL */
                             const void* pre_g, const void* pre_w_t, fod_stream_t stream);
+int fod_linear_add_norm_bwd_det(int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,
+                                const float* gamma, const void* w_t, void* dsum, void* da, float* dgamma, float* dbeta,
+                                int M, int N, int K, const void* pre_g, const void* pre_w_t, void* ws, size_t ws_bytes,
+                                fod_stream_t stream);
 /* out [M, 256] = ((relu(x W1^T + b1)) W2^T + b2) * table[m % table_rows] in ONE launch (bf16, 256 -> 256 -> 256): the
  * decoder's query_scale MLP and its product with the reference points' sine embedding, once per decoder layer (reference
  * transformer.py:384-386).  h [M, 256] (hidden activations) and q [M, 256] (the MLP's output before the product) are
@@ -352,6 +395,9 @@ int fod_mlp2_mul_fwd(int dtype, const void* x, const void* w1, const float* b1, 
 int fod_mlp2_mul_bwd(int dtype, const void* dout, const void* table, int table_rows, const void* q, const void* h,
                      const void* w2_t, const void* w1_t, void* ds, void* dh, void* dx, float* dtable, int M, int D,
                      fod_stream_t stream);
+int fod_mlp2_mul_bwd_det(int dtype, const void* dout, const void* table, int table_rows, const void* q, const void* h,
+                         const void* w2_t, const void* w1_t, void* ds, void* dh, void* dx, float* dtable, int M, int D,
+                         void* ws, size_t ws_bytes, fod_stream_t stream);
 /* group_rows > 0 (rows % group_rows == 0): gamma / beta (and dgamma / dbeta) are [rows / group_rows, D] tables and rows
  * [g * group_rows, (g + 1) * group_rows) use entry g -- the same norm of several layers in one launch; 0: one [D] pair. */
 int fod_layernorm_fwd(int dtype, const void* x, const void* residual, int res_row_div, int res_row_mod,
@@ -361,6 +407,9 @@ int fod_layernorm_fwd(int dtype, const void* x, const void* residual, int res_ro
 int fod_layernorm_bwd(int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,
                       const float* gamma, void* dx, float* dgamma, float* dbeta, int rows, int D,
                       int group_rows, fod_stream_t stream);
+int fod_layernorm_bwd_det(int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,
+                          const float* gamma, void* dx, float* dgamma, float* dbeta, int rows, int D,
+                          int group_rows, void* ws, size_t ws_bytes, fod_stream_t stream);
 
 /* out_j[g, n] = sum over rows m of group g (group_rows consecutive rows) of G_j[m, n] for njobs <= 16 (G_j, out_j) pairs of
  * ONE shape in one launch; bf16 in and out, f32 accumulation in a fixed order.  ptrs: host array of njobs x 2 addresses
