@@ -32,6 +32,7 @@ Restrictions (checked): one device per process, static shapes -- a batch with ot
 import torch
 import torch.distributed as dist
 
+from future_od.native import capture
 from future_od.native import functional as Fn
 from future_od.native import ops
 
@@ -171,6 +172,7 @@ class GraphedStep:
             # train mode: the dropout kernels mix this device scalar into the seeds baked into the graph, so every
             # replay draws new masks (forward and backward of one step read the same value)
             ops.DROP_BASE.add_(1)
+            capture.hold("dropout base", ops.DROP_BASE)       # replaced when a step is captured on another device
         self.opt.zero_grad()
         Fn.set_grad_sync(None)          # an eager pass through a FodDataParallel wrapper may have left its reducer installed
         post, _state, loss, stats, od = self.core(data=data, distributed=False)
@@ -289,8 +291,8 @@ class GraphedStep:
         finally:
             if snap is not None:
                 self._restore(snap)
-        # the optimizer tables this graph's AdamW node reads: learning-rate changes go into THAT plan (__call__), and
-        # the record keeps it alive for as long as the graph lives
+        # the optimizer tables this graph's AdamW node reads: learning-rate changes go into THAT plan (__call__); like
+        # everything else the capture baked in it is kept alive by out["record"] (native/capture.py)
         out["plan"] = getattr(self.opt, "_launched_plan", None)
         return out
 
@@ -335,47 +337,48 @@ class GraphedStep:
         ops.preallocate_graph_workspaces(dev)     # scratch of the captured launches: allocated and zeroed out here
         if not self.ddp:
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with capture.Record() as record, torch.cuda.graph(graph):
                 outs = self._forward_backward(static)
                 self.opt.step()
             torch.cuda.synchronize(dev)
             # the capture itself executed nothing: parameters, moments and the device step count are those after the
             # warm-up steps; python's step counter ran one ahead during capture
             self.opt._step_no -= 1
-            return {"graph": graph, "static": static, "outs": outs}
+            return {"graph": graph, "static": static, "outs": outs, "record": record}
         # data parallel: the collectives stay outside the two graphs
         self._global_num_boxes(static, static["_num_boxes"])
         torch.cuda.synchronize(dev)
         # The backward pass in two pieces (native/functional.py: BackboneCut): A1 = forward + everything down to the
         # backbone's output (all transformer gradients), A2 = the backbone's backward.  The transformer gradients are
         # all-reduced while A2 runs -- the overlap the eager reducer has (parallel.py), without a collective in a graph.
-        graph_a = torch.cuda.CUDAGraph()
-        cut = Fn.BackboneCut() if self.overlap else None
-        Fn.BACKBONE_CUT = cut
-        try:
-            # thread-local capture mode: the process group's watchdog thread polls its events while this thread captures
-            with torch.cuda.graph(graph_a, capture_error_mode="thread_local"):
-                outs = self._forward_backward(static)
-        finally:
-            Fn.BACKBONE_CUT = None
-        first = self._reduce_targets()
-        graph_a2, second = None, []
-        if cut is not None and cut.pairs:
-            off1 = Fn.ARENA.off if Fn.ARENA.active else 0
-            graph_a2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph_a2, pool=graph_a.pool(), capture_error_mode="thread_local"):
-                cut.finish()
-            second = self._reduce_targets(arena_from=off1, skip={t.data_ptr() for t in first})
-        graph_b = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph_b, pool=graph_a.pool(), capture_error_mode="thread_local"):
-            self.opt.step()
+        with capture.Record() as record:          # one record for the two or three graphs: they are dropped together
+            graph_a = torch.cuda.CUDAGraph()
+            cut = Fn.BackboneCut() if self.overlap else None
+            Fn.BACKBONE_CUT = cut
+            try:
+                # thread-local capture mode: the process group's watchdog thread polls its events while this thread captures
+                with torch.cuda.graph(graph_a, capture_error_mode="thread_local"):
+                    outs = self._forward_backward(static)
+            finally:
+                Fn.BACKBONE_CUT = None
+            first = self._reduce_targets()
+            graph_a2, second = None, []
+            if cut is not None and cut.pairs:
+                off1 = Fn.ARENA.off if Fn.ARENA.active else 0
+                graph_a2 = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph_a2, pool=graph_a.pool(), capture_error_mode="thread_local"):
+                    cut.finish()
+                second = self._reduce_targets(arena_from=off1, skip={t.data_ptr() for t in first})
+            graph_b = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph_b, pool=graph_a.pool(), capture_error_mode="thread_local"):
+                self.opt.step()
         torch.cuda.synchronize(dev)
         self.opt._step_no -= 1
         both = first + second
         self.comm_stats = {"tensors": len(both), "bytes": sum(t.numel() * t.element_size() for t in both),
                            "overlapped_bytes": sum(t.numel() * t.element_size() for t in first) if graph_a2 else 0}
         return {"graph": graph_a, "graph_bb": graph_a2, "graph_opt": graph_b, "targets": first, "targets_bb": second,
-                "static": static, "outs": outs}
+                "static": static, "outs": outs, "record": record}
 
     # ------------------------------------------------------------------------------------------
     def __call__(self, data, sync=True):
@@ -383,8 +386,10 @@ class GraphedStep:
         parameters then DIVERGE; it exists to time the step without communication."""
         token = getattr(self.opt, "_state_token", 0)
         if token != getattr(self, "_opt_token", token):
-            self._retired_graphs = getattr(self, "_retired_graphs", []) + [self._graphs]
-            self._graphs = {}                      # optimizer.load_state_dict() replaced the moment tensors: capture anew
+            # optimizer.load_state_dict() replaced the moment tensors: capture anew.  Once per checkpoint load: no replay
+            # may be in flight when the old graphs, and with them what their records hold, are dropped
+            torch.cuda.synchronize()
+            self._graphs = {}
         self._opt_token = token
         sig = self._signature(data)
         g = self._graphs.get(sig)
@@ -493,10 +498,10 @@ class GraphedForward:
         graph = torch.cuda.CUDAGraph()
         ops.preallocate_graph_workspaces(dev)
         Fn.PREP.refresh()                         # the graph reads the prepared weight copies; they are refreshed
-        with torch.cuda.graph(graph):             # eagerly before a replay, and only when a parameter has changed
-            outs = self._run(static)
+        with capture.Record() as record, torch.cuda.graph(graph):      # eagerly before a replay, and only when a
+            outs = self._run(static)                                    # parameter has changed
         torch.cuda.synchronize(dev)
-        return {"graph": graph, "static": static, "outs": outs}
+        return {"graph": graph, "static": static, "outs": outs, "record": record}
 
     def __call__(self, data):
         if self.model.training:

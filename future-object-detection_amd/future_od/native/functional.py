@@ -11,6 +11,7 @@ import os
 import torch
 from torch.autograd import Function
 
+from . import capture
 from . import lib as L
 from . import ops
 
@@ -81,9 +82,9 @@ class _Prepared:
         if tab is None:
             tab = self._build_tables([j for e in stale for j in e.jobs])
             if len(self._tables) > 16:
-                self._retired = getattr(self, "_retired", []) + [({}, dict(self._tables))]   # a graph may have baked one in
                 self._tables.clear()
             self._tables[key] = tab
+        capture.hold_or_ask("refresh table", tab)      # raw pointers: a capture that records this launch keeps it
         jobs_dev, blk_job, blk_chunk, nblocks, _keep = tab
         L.call("fod_multi_permute3", ops.ptr(jobs_dev), ops.ptr(blk_job), ops.ptr(blk_chunk), nblocks, ops.stream())
         for e in stale:
@@ -118,10 +119,9 @@ class _Prepared:
         self.epoch += 1
 
     def clear(self):
-        # the old buffers and job tables are retired, not freed: a captured graph of an earlier model replays kernels
-        # that read them -- the refresh launch's job table holds raw POINTERS, and a recycled table is a wild access
-        # (observed: a GPU memory fault when a graph of model 1 was replayed after model 2 had been built)
-        self._retired = getattr(self, "_retired", []) + [(self._store, dict(self._tables))]
+        # buffers and job tables that a captured graph replays are held by that graph's record (native/capture.py: the
+        # store generation through the provider below, a table where its launch is recorded); the rest is freed here
+        capture.hold_or_ask("prepared operands", self._store)      # (cleared inside a capture that has read them)
         self._store = {}                 # a NEW dict: per-parameter memos (prep_linear) compare its identity
         self._tables.clear()
 
@@ -143,14 +143,13 @@ class _ZeroArena:
         self.active = False
         self.extra = []
         self.cap = 0
-        self.retired = []
 
     def recycle(self, device):
         device = torch.device(device)
         need = max(self.high, 1 << 20)
         if self.buf is None or self.buf.device != device or self.buf.numel() < need:
             if self.buf is not None:
-                self.retired.append(self.buf)      # a captured step may have baked slices of it in: never freed
+                capture.hold_or_ask("gradient arena", self.buf)     # (outgrown inside a capture that wrote slices of it)
             self.buf = torch.zeros(int(need * 1.25), dtype=torch.float32, device=device)
         elif self.off:
             self.buf[:self.off].zero_()
@@ -186,6 +185,10 @@ class _ZeroArena:
 
 
 ARENA = _ZeroArena()
+
+# what every capture reads, held once per capture: the store generation (each entry's buffers and job operands) and
+# the buffer whose slices a captured backward writes
+capture.provide(lambda: (("prepared operands", PREP._store), ("gradient arena", ARENA.buf)))
 
 # Data-parallel runs: the object that averages finished arena regions across ranks (parallel.GradientReducer),
 # installed by FodDataParallel.forward for the coming backward pass; None otherwise.
@@ -251,8 +254,8 @@ class _WgradQueue:
     parallel.FodDataParallel switches the queue off for it).
 
     Inside a stream capture the job table is written into a pinned host buffer set aside BEFORE the capture (allocating
-    pinned memory inside one hangs) and copied by a captured memcpy node; host and device side of such a table are
-    never reused.  Without a spare the jobs are launched one by one."""
+    pinned memory inside one hangs) and copied by a captured memcpy node; host and device side of such a table belong to
+    the capture (native/capture.py).  Without a spare the jobs are launched one by one."""
 
     SPARE_BYTES = 1 << 18
 
@@ -281,7 +284,6 @@ class _WgradQueue:
         self.epoch = 1
         self._tables = {}
         self._spares = []
-        self._baked = []
         self.hold = False            # tests: collect jobs outside a backward pass until flush() is called
         self.launches = 0            # multi launches / jobs they carried (tests, bench diagnostics)
         self.carried = 0
@@ -562,7 +564,7 @@ class _WgradQueue:
                 if not self._spares or raw.size > self.SPARE_BYTES or self._spares[-1][1].device != dev:
                     return self._one_by_one(jobs, members, long)
                 pin, table = self._spares.pop()
-                self._baked.append((pin, table))         # the graph reads both at every replay: never reused
+                capture.hold_or_ask("weight-gradient table", (pin, table))     # the graph reads both at every replay
                 pin[:raw.size].copy_(torch.from_numpy(raw))
                 table[:raw.size].copy_(pin[:raw.size], non_blocking=True)
                 tab = (table, off, nblocks, part_floats)

@@ -7,6 +7,7 @@ import os
 
 import torch
 
+from . import capture
 from . import lib as L
 from .lib import F32, BF16, AttnShape, ConvGeom, Epilogue
 
@@ -64,9 +65,8 @@ def _chk(t, name, dtype=None):
 # ---- caller-owned scratch of the library (include/fod.h: it allocates no device memory and keeps no device state) ------
 # One buffer per (kind, device, stream) for eagerly launched work and one per (kind, device) for everything captured
 # into graphs (replays of this process's graphs are launched from one thread onto one stream at a time): launches of one
-# stream are ordered, a replay running next to an eager step or two eager streams must not share partial tiles.  A
-# buffer is never freed -- a captured graph holds its address (the retire-don't-free rule of the attention split
-# workspace below).
+# stream are ordered, a replay running next to an eager step or two eager streams must not share partial tiles.  This is
+# a cache: an entry is never replaced, so there is nothing for a graph's record to hold.
 _WS = {}
 
 
@@ -79,6 +79,8 @@ def _workspace(kind, device, captured=None):
         nbytes = L.LIB.fod_workspace_bytes(kind)
         hit = torch.zeros(nbytes // 4, dtype=torch.int32, device=device)     # the ticket words must start at zero
         _WS[key] = hit
+    if captured:
+        capture.hold_or_ask("scratch", hit)      # never replaced; but this is where a capture without a record is noticed
     return hit
 
 
@@ -91,6 +93,10 @@ def preallocate_graph_workspaces(device):
         kinds += (L.WS_DET, L.WS_TN_MULTI_DET)
     for kind in kinds:
         _workspace(kind, device, captured=True)
+    # the attention split scratch is sized by its users: as large as the largest the (warm-up) streams needed
+    tiles = max((hit[2] for key, hit in _ATTN_SPLIT.items() if key[0] == device.index), default=0)
+    if tiles:
+        _attn_split_workspace(device, tiles, captured=True)
 
 
 # ---- deterministic mode ---------------------------------------------------------------------------------------------
@@ -532,22 +538,23 @@ _ATTN_SPLIT = {}
 _ATTN_SPLIT_FLOATS_PER_TILE = 8 * 2176          # FOD_ATTN_SPLIT_WS_FLOATS_PER_TILE (include/fod.h)
 
 
-def _attn_split_workspace(device, tiles):
-    """Scratch of the launches whose keys are split across blocks (fod_attn_shape.split_ws / split_tickets): one per
-    device, reused by every call (the launches of one stream are ordered; the kernels leave the tickets zero)."""
-    key = (device.type, device.index)
+def _attn_split_workspace(device, tiles, captured=None):
+    """Scratch of the launches whose keys are split across blocks (fod_attn_shape.split_ws / split_tickets): keyed like
+    _WS (the launches of one stream are ordered; the kernels leave the tickets zero).  It grows by replacement: a
+    stream's outgrown buffer goes back to torch's allocator, which orders its reuse behind that stream's launches; the
+    one captured launches read is held by each capture that reads it."""
+    if captured is None:
+        captured = torch.cuda.is_current_stream_capturing()
+    key = (device.index, "graph" if captured else stream())
     hit = _ATTN_SPLIT.get(key)
     if hit is None or hit[2] < tiles:
         cap = max(tiles, 256)
-        if hit is not None:
-            _ATTN_SPLIT_RETIRED.append(hit)      # a captured graph may still hold its addresses: never freed
         hit = (torch.empty(cap * _ATTN_SPLIT_FLOATS_PER_TILE, dtype=torch.float32, device=device),
                torch.zeros(cap, dtype=torch.int32, device=device), cap)
         _ATTN_SPLIT[key] = hit
+    if captured:
+        capture.hold_or_ask("attention split scratch", hit)      # (no-op while preallocating: nothing is capturing)
     return hit[0], hit[1]
-
-
-_ATTN_SPLIT_RETIRED = []
 
 
 def _same_bt(a, b, name):

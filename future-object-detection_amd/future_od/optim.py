@@ -9,6 +9,7 @@ import math
 
 import torch
 
+from future_od.native import capture
 from future_od.native import lib as L
 from future_od.native.ops import ptr, stream
 
@@ -134,18 +135,17 @@ class FusedAdamW(torch.optim.Optimizer):
             host[:, 1] = torch.tensor(gptrs, dtype=torch.int64)
             plan["tab"][0].copy_(host, non_blocking=True)
             if capturing:
-                # the copy becomes a graph node that re-reads this slot at every replay: the slot is retired from the
-                # ring's rotation for good (a captured step never comes back here; a later capture builds a new plan)
-                # (its replacement was pinned when the plan was built: no host allocation may happen inside a capture)
+                # the copy becomes a graph node that re-reads this slot at every replay: the slot leaves the ring's
+                # rotation and belongs to the capture (a captured step never comes back here; a later capture builds a
+                # new plan).  Its replacement was pinned when the plan was built: no host allocation inside a capture
                 done[turn] = None
+                capture.hold_or_ask("optimizer ring slot", host)
                 spares = plan.setdefault("spares", [])
                 if spares:
                     plan["ring"][turn] = spares.pop()
-                    plan.setdefault("captured_slots", []).append(host)
                 else:
                     # out of spare slots: the next eager step rebuilds the plan (and its ring); this one's tables are
-                    # baked into the capture in progress and stay alive
-                    self._retired_plans = getattr(self, "_retired_plans", []) + [plan]
+                    # baked into the capture in progress, which holds the plan (_launch)
                     self._plan = None
             else:
                 ev = torch.cuda.Event()
@@ -194,13 +194,15 @@ class FusedAdamW(torch.optim.Optimizer):
         if self._sq is None or self._sq.device != dev:
             self._sq = torch.zeros(1, dtype=torch.float32, device=dev)
         nblocks = bt.numel()
-        sq = None
+        sq = scr = None
         if self.max_norm > 0:
             # fixed summation order: data-parallel replicas with equal gradients get bit-equal clip factors
             scr = getattr(self, "_sq_scratch", None)
             if scr is None or scr.device != dev or scr.numel() < nblocks + 1:
-                if scr is not None:
-                    self._retired = getattr(self, "_retired", []) + [scr]     # a captured step may still hold its address
+                if scr is not None and not capture.hold_or_ask("optimizer state", scr):
+                    # rare (the plan grew).  The old scratch goes back to torch's allocator, which orders reuse behind
+                    # the stream that allocated it only: no launch of another stream may still be reading it
+                    torch.cuda.synchronize(scr.device)
                 scr = self._sq_scratch = torch.zeros(nblocks + 1, dtype=torch.float32, device=dev)
             L.call("fod_multi_sqnorm_det", ptr(ptrs), ptr(numel), ptr(bt), ptr(bc), nblocks, ptr(self._sq), ptr(scr), stream())
             sq = self._sq
@@ -209,6 +211,10 @@ class FusedAdamW(torch.optim.Optimizer):
         bc2 = 1.0 - betas[1] ** self._step_no
         L.call("fod_multi_adamw", ptr(ptrs), ptr(numel), ptr(lr_wd), ptr(bt), ptr(bc), nblocks, betas[0], betas[1],
                eps, bc1, bc2, ptr(self._bias_dev), ptr(sq), self.max_norm, stream())
+        # once per step: a capture that recorded the two launches keeps what they read (moments and parameters are
+        # the optimizer's and the model's own; load_state_dict, which replaces the moments, invalidates the graphs)
+        capture.hold_or_ask("optimizer state", (getattr(self, "_launched_plan", None), tab, self._sq, scr, self._bias_dev,
+                                                self._dev_step, self._dev_betas))
         # the kernel wrote the parameters through raw pointers (their `_version` did not move): every prepared
         # operand derived from a parameter (compute-dtype / transposed / BN-folded copies) is now out of date
         from future_od.native import functional as Fn
@@ -232,11 +238,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._launched_plan = plan
                 self._launch(plan["tab"], plan["dev"], betas, eps)
                 return None
-        old_plan = getattr(self, "_plan", None)
-        if old_plan is not None:
-            # its device tables may be baked into a captured step (future_od/graph.py): kept alive, never freed
-            self._retired_plans = getattr(self, "_retired_plans", []) + [old_plan]
-        plan = self._build_plan()
+        plan = self._build_plan()                # (the one it replaces lives on in the graphs captured with it)
         self._plan = plan
         self._launched_plan = plan               # None: the general path below (its tables are not reusable)
         if plan is not None:
@@ -280,6 +282,4 @@ class FusedAdamW(torch.optim.Optimizer):
         self._state_token = getattr(self, "_state_token", 0) + 1      # the moment tensors are new objects: captured steps
         if getattr(self, "_dev_step", None) is not None:              # that baked the old ones in must be re-captured
             self._dev_step.fill_(float(self._step_no))
-        if getattr(self, "_plan", None) is not None:
-            self._retired_plans = getattr(self, "_retired_plans", []) + [self._plan]
         self._plan = None

@@ -86,7 +86,6 @@ def test_capture_without_spare_job_tables_launches_the_queued_gradients_one_by_o
     assert q.enabled
     monkeypatch.setattr(q, "_spares", [])
     monkeypatch.setattr(q, "_top_up", lambda dev: None)
-    baked = len(q._baked)
     data = make_batch(2, 3, 96, 128, seed=11, max_boxes=9, device=DEV)
     data2 = make_batch(2, 3, 96, 128, seed=12, max_boxes=20, device=DEV)
     m_e, o_e = _build("bf16")
@@ -95,9 +94,83 @@ def test_capture_without_spare_job_tables_launches_the_queued_gradients_one_by_o
     seq = [data, data, data, data, data2, data]
     le = [float(_eager_step(m_e, o_e, d)) for d in seq]
     lg = [None, None, None] + [float(step(d)[1].detach()) for d in seq[3:]]
-    assert step.replays == 3 and len(q._baked) == baked          # no table was baked into the graph
+    (g,) = step._graphs.values()
+    assert step.replays == 3 and g["record"].of("weight-gradient table") == []     # no table was baked into the graph
     for i in range(3, len(seq)):
         assert abs(lg[i] - le[i]) <= 2e-3 * max(abs(le[i]), 1.0), (i, lg[i], le[i])
+
+
+def test_graphs_of_earlier_models_replay_after_later_models_were_built(monkeypatch):
+    """A captured graph reads prepared weight copies, job tables (raw pointers), arena slices and optimizer tables by
+    address; building a model drops the prepared-operand store of the one before (runs/_model.py: PREP.clear()), and the
+    refresh tables are dropped after 16 stale sets.  What a live graph reads must survive both, held by the graph's
+    record (native/capture.py): a training-step graph of model A and an evaluation graph of model F are replayed after
+    three further models were built and stepped.  Freed blocks are handed out again, not unmapped, so a lifetime
+    mistake shows as wrong numbers.  Tolerances: those of test_graphed_steps_track_eager_steps (bf16, at most 7 steps)."""
+    from future_od.datasets.synthetic import make_batch
+    from future_od.graph import GraphedForward, GraphedStep
+    from future_od.native import functional as Fn
+    data = make_batch(2, 3, 96, 128, seed=11, max_boxes=9, device=DEV)
+    data2 = make_batch(2, 3, 96, 128, seed=12, max_boxes=20, device=DEV)
+    m_e, o_e = _build("bf16")
+    m_a, o_a = _build("bf16")
+    step = GraphedStep(m_a, o_a, warmup=2)
+    le = [float(_eager_step(m_e, o_e, data)) for _ in range(4)]
+    la = [float(step(data)[1].detach())]                      # 3 eager warm-up steps + 1 replay
+    m_f, _ = _build("bf16")
+    fwd = GraphedForward(m_f)
+    post, loss, _, od = fwd(data)
+    first = [loss.clone(), post["class_scores"].clone(), post["boxes"].clone()] + [t.clone() for t in od]
+    (g,) = step._graphs.values()
+    for kind in ("prepared operands", "refresh table", "gradient arena", "weight-gradient table", "optimizer state"):
+        assert g["record"].of(kind), kind
+    tables, build_tables = [], Fn.PREP._build_tables
+    monkeypatch.setattr(Fn.PREP, "_build_tables", lambda jobs: tables.append(len(jobs)) or build_tables(jobs))
+    for seed in (5, 6, 7):                                    # three further models, two eager steps each
+        m_x, o_x = _build("bf16", seed=seed)
+        for d in (data, data2):
+            _eager_step(m_x, o_x, d)
+        del m_x, o_x                                          # (each _build dropped the store of the model before)
+    assert len(tables) > 16, len(tables)                      # the table cap was passed
+    for d in (data2, data, data2):
+        le.append(float(_eager_step(m_e, o_e, d)))
+        la.append(float(step(d)[1].detach()))
+    post, loss, _, od = fwd(data)
+    for a, b in zip(first, [loss, post["class_scores"], post["boxes"]] + list(od)):
+        assert torch.equal(a, b)
+    assert step.replays == 4 and fwd.replays == 2 and o_a._step_no == o_e._step_no == 7
+    for got, want in zip(la, le[3:]):
+        assert abs(got - want) <= 2e-3 * max(abs(want), 1.0), (la, le[3:])
+    worst, total, count = 0.0, 0.0, 0
+    for pe, pa in zip(m_e.parameters(), m_a.parameters()):
+        d = (pe.detach() - pa.detach()).abs()
+        worst, total, count = max(worst, float(d.max())), total + float(d.sum()), count + d.numel()
+    assert total / count < 2e-5 and worst < 1.5e-3, (total / count, worst)
+
+
+def test_dropped_models_and_their_graphs_give_their_device_memory_back():
+    """Three rounds of build, capture, two replays, drop: device memory in use after round 3 exceeds that after round
+    2 by less than one bf16 copy of the weights: what a graph baked in is freed with the graph, and a model's prepared
+    weight copies with the next build_model (a leak of either is that copy of every weight, plus the transposed copy of
+    every trainable one, per round)."""
+    import gc
+    from future_od.datasets.synthetic import make_batch
+    from future_od.graph import GraphedStep
+    data = make_batch(2, 3, 96, 128, seed=11, max_boxes=9, device=DEV)
+    in_use = []
+    for _ in range(3):
+        model, opt = _build("bf16")
+        one_copy = 2 * sum(p.numel() for p in model.parameters())
+        step = GraphedStep(model, opt, warmup=2)
+        step(data)
+        step(data)
+        assert step.replays == 2
+        torch.cuda.synchronize()
+        del step, model, opt
+        gc.collect()
+        in_use.append(torch.cuda.memory_allocated())
+    print(f"device memory in use after each round: {in_use}, one bf16 copy of the weights: {one_copy}")
+    assert in_use[2] - in_use[1] < one_copy, (in_use, one_copy)
 
 
 def test_graph_outputs_are_the_eager_outputs_at_equal_parameters():
