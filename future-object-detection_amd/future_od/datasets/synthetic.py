@@ -22,10 +22,15 @@ def _quat_mul(a, b):
 
 
 def make_batch(B, L, H, W, seed=1234, device="cpu", num_classes=8, max_boxes=40, min_boxes=1,
-               video_dtype=torch.float32):
-    """One batch of B clips of L frames.  Generated on CPU (seeded), then moved to `device`."""
+               video_dtype=torch.float32, raw_frames=False):
+    """One batch of B clips of L frames.  Generated on CPU (seeded), then moved to `device`.
+    `raw_frames`: the clip is uint8 noise over the whole 0..255 range, as a camera frame reader hands frames over
+    (the input of future_od/utils/augment.py), instead of normalised values."""
     g = torch.Generator().manual_seed(seed)
-    video = torch.randn(B, L, 3, H, W, generator=g, dtype=torch.float32).to(video_dtype)
+    if raw_frames:
+        video = torch.randint(0, 256, (B, L, 3, H, W), generator=g, dtype=torch.uint8)
+    else:
+        video = torch.randn(B, L, 3, H, W, generator=g, dtype=torch.float32).to(video_dtype)
     translation = (0.5 * torch.randn(B, L, 3, generator=g)).cumsum(1)
     translation = translation - translation[:, :1]
     q = torch.randn(B, L, 4, generator=g)

@@ -1,0 +1,278 @@
+"""Joint transforms of a clip and its boxes, with the class names and constructor arguments of the reference
+(reference future_od/datasets/transforms.py; composed by its loaders, runs/_loader.py:30-35,45,74-79,89).
+
+Every transform has two faces:
+
+* `t(images, boxes, classes) -> (images, boxes, classes)`: the per-sample CPU form.  `images` is a float clip
+  [L, 3, h, w], `boxes` [n, 4] are xyxy pixels, `classes` [n].  This is what a CPU dataset calls and what the device
+  path is tested against.  Cropping is slicing, resizing is `F.interpolate(mode="bilinear", align_corners=False)`
+  without antialiasing (what the reference's pinned torchvision does to tensors).
+* `t.plan(h, w, rng) -> Plan`: draws the transform's random numbers and returns the GEOMETRY for a frame of that size
+  -- one source rectangle, the output size, a flip flag -- plus the annotation steps.  The image half of a plan is one
+  bilinear pass, which is what `fod_clip_crop_resize` executes on the device from the raw uint8 frames
+  (future_od/utils/augment.py); the annotation half runs on the host (`Plan.annotate`).
+
+Plannable is: crops (a rectangle inside a rectangle composes exactly), then at most one `JointResize`, then at most one
+`JointHorizontalFlip`, with `SizeFilter` / no-ops anywhere; `RandomSelect` plans the branch it draws.  Anything else
+would need a second resampling: `plan` raises ValueError naming the step, it never approximates.
+
+Random numbers come from a `random.Random`-like `rng`; `rng=None` (and `__call__`) means Python's global `random`
+module, so `random.seed(s); t(...)` and `t.plan(h, w, random.Random(s))` draw the same numbers.
+
+Annotation rules (the reference's, quirks included): a crop subtracts (left, top, left, top), keeps a box iff
+x0 <= width and y0 <= height and x1 >= 0 and y1 >= 0 (inclusive: a box that only touches the crop survives as a
+degenerate one), then clamps to [0, width] x [0, height]; a resize multiplies by (new_w / old_w, new_h / old_h, ...);
+a flip maps (x0, x1) -> (w - x1, w - x0); `SizeFilter` keeps area / (h * w) > min_size.  The sized crops use ONE scale
+for both sides: int(h * scale), int(w * scale)."""
+import random as _random
+from abc import ABC, abstractmethod
+from typing import List, Tuple
+
+import torch
+import torch.nn.functional as F
+
+
+class ImageRemap:
+    """uint8 0..255 -> float 0..1."""
+
+    def __call__(self, tensor):
+        return tensor.float() / 255
+
+
+# ---- annotation steps: plain tuples, applied by ONE function for both faces -------------------------------------------
+# ("crop", left, top, width, height) | ("resize", old_w, old_h, new_w, new_h) | ("flip", width)
+# | ("size_filter", width, height, min_size)
+
+def annotate(step, boxes, classes):
+    """One annotation step on boxes [n, 4] (xyxy pixels, float) and classes [n]; returns new tensors."""
+    kind = step[0]
+    if kind == "crop":
+        _, left, top, width, height = step
+        boxes = boxes - torch.tensor([left, top, left, top], dtype=boxes.dtype)
+        keep = (boxes[:, 0] <= width) & (boxes[:, 1] <= height) & (boxes[:, 2] >= 0) & (boxes[:, 3] >= 0)
+        boxes, classes = boxes[keep], classes[keep]
+        hi = torch.tensor([width, height, width, height], dtype=boxes.dtype)
+        return torch.minimum(boxes.clamp(min=0), hi), classes
+    if kind == "resize":
+        _, old_w, old_h, new_w, new_h = step
+        w_scale, h_scale = new_w / old_w, new_h / old_h
+        return boxes * torch.tensor([w_scale, h_scale, w_scale, h_scale], dtype=boxes.dtype), classes
+    if kind == "flip":
+        width = step[1]
+        return torch.stack([width - boxes[:, 2], boxes[:, 1], width - boxes[:, 0], boxes[:, 3]], dim=1), classes
+    if kind == "size_filter":
+        _, width, height, min_size = step
+        area = (boxes[:, 2] - boxes[:, 0]) * (boxes[:, 3] - boxes[:, 1])
+        keep = (area / (height * width)) > min_size
+        return boxes[keep], classes[keep]
+    raise ValueError(f"unknown annotation step {step!r}")
+
+
+class Plan:
+    """Composed geometry of a joint transform for one frame size: `rect` = (top, left, height, width) in the source
+    frame, `size` = (H, W) of the output, `flip`, and the annotation `steps` in the order they were composed."""
+
+    def __init__(self, h, w):
+        self.source = (int(h), int(w))
+        self.rect = (0, 0, int(h), int(w))
+        self.size = (int(h), int(w))
+        self.flip = False
+        self.steps = []
+        self._resized = self._flip_seen = False
+
+    def row(self):
+        """(top, left, height, width, flip): a row of the `plans` operand of ops.clip_crop_resize."""
+        return (*self.rect, int(self.flip))
+
+    def annotate(self, boxes, classes):
+        for step in self.steps:
+            boxes, classes = annotate(step, boxes, classes)
+        return boxes, classes
+
+    def __repr__(self):
+        return f"Plan(rect={self.rect}, size={self.size}, flip={self.flip}, steps={self.steps})"
+
+
+class JointTransform(ABC):
+    @abstractmethod
+    def __call__(self, images, boxes, classes) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Perform a joint transform."""
+
+    @abstractmethod
+    def _extend(self, plan: Plan, rng) -> None:
+        """Draw this transform's random numbers from `rng` and compose it onto `plan`."""
+
+    def plan(self, h, w, rng=None) -> Plan:
+        plan = Plan(h, w)
+        self._extend(plan, _random if rng is None else rng)
+        return plan
+
+
+class JointNoOpTransform(JointTransform):
+    def __call__(self, images, boxes, classes):
+        return images, boxes, classes
+
+    def _extend(self, plan, rng):
+        pass
+
+
+class JointCompose(JointTransform):
+    def __init__(self, transforms: List[JointTransform]):
+        self.transforms = transforms
+
+    def __call__(self, images, boxes, classes):
+        for transform in self.transforms:
+            images, boxes, classes = transform(images, boxes, classes)
+        return images, boxes, classes
+
+    def _extend(self, plan, rng):
+        for transform in self.transforms:
+            if not hasattr(transform, "_extend"):
+                raise ValueError(f"{type(transform).__name__} cannot be planned: it does not describe its geometry")
+            transform._extend(plan, rng)
+
+
+class JointResize(JointTransform):
+    def __init__(self, size: Tuple[int, int], interpolation: str = "bilinear"):
+        self._size = [int(v) for v in size]
+        self._interpolation = getattr(interpolation, "value", interpolation)
+
+    def __call__(self, images, boxes, classes):
+        old_h, old_w = images.shape[-2:]
+        new_h, new_w = self._size
+        kw = {"align_corners": False} if self._interpolation in ("bilinear", "bicubic") else {}
+        images = F.interpolate(images, size=(new_h, new_w), mode=self._interpolation, **kw)
+        boxes, classes = annotate(("resize", old_w, old_h, new_w, new_h), boxes, classes)
+        return images, boxes, classes
+
+    def _extend(self, plan, rng):
+        if self._interpolation != "bilinear":
+            raise ValueError(f"JointResize(interpolation={self._interpolation!r}) cannot be planned: the device pass is bilinear")
+        if plan._resized:
+            raise ValueError("JointResize after a JointResize cannot be planned: two resamplings are not one bilinear pass")
+        if plan._flip_seen:
+            raise ValueError("JointResize after a JointHorizontalFlip cannot be planned: the flip comes last")
+        old_h, old_w = plan.size
+        plan.size = (self._size[0], self._size[1])
+        plan._resized = True
+        plan.steps.append(("resize", old_w, old_h, self._size[1], self._size[0]))
+
+
+class BaseCrop(JointTransform, ABC):
+    @abstractmethod
+    def _get_crop_param(self, image_h: int, image_w: int, rng) -> Tuple[int, int, int, int]:
+        """(top, left, height, width) of the crop of an image_h x image_w frame."""
+
+    def _checked(self, image_h, image_w, rng):
+        top, left, crop_h, crop_w = self._get_crop_param(image_h, image_w, rng)
+        if not (0 < crop_h <= image_h and 0 < crop_w <= image_w and 0 <= top <= image_h - crop_h
+                and 0 <= left <= image_w - crop_w):
+            raise ValueError(f"{type(self).__name__}: crop {crop_h}x{crop_w} at ({top}, {left}) leaves the "
+                             f"{image_h}x{image_w} frame (padding crops are not supported)")
+        return top, left, crop_h, crop_w
+
+    def __call__(self, images, boxes, classes):
+        image_h, image_w = images.shape[-2:]
+        top, left, crop_h, crop_w = self._checked(image_h, image_w, _random)
+        images = images[..., top:top + crop_h, left:left + crop_w]
+        boxes, classes = annotate(("crop", left, top, crop_w, crop_h), boxes, classes)
+        return images, boxes, classes
+
+    def _extend(self, plan, rng):
+        if plan._resized or plan._flip_seen:
+            raise ValueError(f"{type(self).__name__} after a {'JointResize' if plan._resized else 'JointHorizontalFlip'} "
+                             "cannot be planned: crops come first (a crop of resampled pixels is a second resampling)")
+        image_h, image_w = plan.size
+        top, left, crop_h, crop_w = self._checked(image_h, image_w, rng)
+        plan.rect = (plan.rect[0] + top, plan.rect[1] + left, crop_h, crop_w)
+        plan.size = (crop_h, crop_w)
+        plan.steps.append(("crop", left, top, crop_w, crop_h))
+
+
+class JointCenterCrop(BaseCrop):
+    def __init__(self, size):
+        self.th, self.tw = int(size[0]), int(size[1])
+
+    def _get_crop_param(self, image_h, image_w, rng):
+        return (image_h - self.th) // 2, (image_w - self.tw) // 2, self.th, self.tw
+
+
+class JointRandomCrop(JointCenterCrop):
+    def _get_crop_param(self, image_h, image_w, rng):
+        if self.th > image_h or self.tw > image_w:
+            return 0, 0, self.th, self.tw                      # refused by _checked
+        return rng.randint(0, image_h - self.th), rng.randint(0, image_w - self.tw), self.th, self.tw
+
+
+class RandomSizedCrop(BaseCrop):
+    def __init__(self, min_scale, max_scale):
+        assert max_scale <= 1.0, "Cannot crop more than the whole image!"
+        self._min_scale, self._max_scale = min_scale, max_scale
+
+    def _crop_size(self, image_h, image_w, rng):
+        scale = rng.uniform(self._min_scale, self._max_scale)
+        return int(image_h * scale), int(image_w * scale)
+
+    def _get_crop_param(self, image_h, image_w, rng):
+        crop_h, crop_w = self._crop_size(image_h, image_w, rng)
+        return rng.randint(0, image_h - crop_h), rng.randint(0, image_w - crop_w), crop_h, crop_w
+
+
+class CenterBiasedRandomSizedCrop(RandomSizedCrop):
+    """The crop's origin follows a triangular distribution that peaks where the crop is centred."""
+
+    def _get_crop_param(self, image_h, image_w, rng):
+        crop_h, crop_w = self._crop_size(image_h, image_w, rng)
+        max_i, max_j = image_h - crop_h + 1, image_w - crop_w + 1
+        top = min(int(rng.triangular(0, max_i, max_i / 2)), max_i - 1)       # the closed upper end would leave the frame
+        left = min(int(rng.triangular(0, max_j, max_j / 2)), max_j - 1)
+        return top, left, crop_h, crop_w
+
+
+class JointHorizontalFlip(JointTransform):
+    def __init__(self, p: float = 0.5):
+        self._p = p
+
+    def __call__(self, images, boxes, classes):
+        if _random.random() < self._p:
+            images = images.flip(-1)
+            boxes, classes = annotate(("flip", images.shape[-1]), boxes, classes)
+        return images, boxes, classes
+
+    def _extend(self, plan, rng):
+        if plan._flip_seen:
+            raise ValueError("JointHorizontalFlip after a JointHorizontalFlip cannot be planned: at most one flip")
+        plan._flip_seen = True
+        if rng.random() < self._p:
+            plan.flip = True
+            plan.steps.append(("flip", plan.size[1]))
+
+
+class RandomSelect(JointTransform):
+    """`transforms1` with probability p, else `transforms2`."""
+
+    def __init__(self, transforms1, transforms2, p=0.5):
+        self.transforms1, self.transforms2, self.p = transforms1, transforms2, p
+
+    def __call__(self, *args, **kwargs):
+        if _random.random() < self.p:
+            return self.transforms1(*args, **kwargs)
+        return self.transforms2(*args, **kwargs)
+
+    def _extend(self, plan, rng):
+        JointCompose([self.transforms1 if rng.random() < self.p else self.transforms2])._extend(plan, rng)
+
+
+class SizeFilter(JointTransform):
+    """Filter objects based on size (relative to image size)."""
+
+    def __init__(self, min_size):
+        self.min_size = min_size
+
+    def __call__(self, images, boxes, classes):
+        image_h, image_w = images.shape[-2:]
+        boxes, classes = annotate(("size_filter", image_w, image_h, self.min_size), boxes, classes)
+        return images, boxes, classes
+
+    def _extend(self, plan, rng):
+        plan.steps.append(("size_filter", plan.size[1], plan.size[0], self.min_size))

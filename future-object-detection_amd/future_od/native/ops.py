@@ -349,6 +349,31 @@ def clip_to_stem_layout(video, dtype, mean=None, std=None):
     return out
 
 
+def clip_crop_resize(video_u8, plans, size, mean, std):
+    """Raw uint8 frames [B,L,C<=3,H0,W0] + device plans int32 [B,5] = (top, left, height, width, flip) -> the normalised
+    f32 clip [B,L,C,*size]: crop, bilinear resize (align_corners=False), flip and pixel pipeline in one pass; see
+    fod_clip_crop_resize.  The kernel reads the plans from device memory and clamps a rectangle that leaves the frame."""
+    if not isinstance(video_u8, torch.Tensor) or not video_u8.is_cuda or video_u8.dtype != torch.uint8 \
+            or video_u8.dim() != 5:
+        raise L.FodError("clip_crop_resize: video must be a uint8 device tensor [B, L, C, H0, W0] "
+                         "(the HIP path has no CPU fallback)")
+    b, l, c, h0, w0 = video_u8.shape
+    sb, sl, sc, sh, sw = video_u8.stride()
+    if c > 3 or (sc, sh, sw) != (h0 * w0, w0, 1):
+        raise L.FodError(f"clip_crop_resize: frame planes must be contiguous, got strides {video_u8.stride()}")
+    _chk(plans, "plans", torch.int32); _chk(mean, "mean", torch.float32); _chk(std, "std", torch.float32)
+    if tuple(plans.shape) != (b, 5) or mean.numel() != c or std.numel() != c:
+        raise L.FodError(f"clip_crop_resize: plans {tuple(plans.shape)} / mean {mean.numel()} / std {std.numel()} do not "
+                         f"fit a clip of {b} x {c} planes")
+    if not (plans.device == mean.device == std.device == video_u8.device):
+        raise L.FodError("clip_crop_resize: operands live on different devices")
+    h, w = (int(v) for v in size)
+    out = torch.empty((b, l, c, h, w), dtype=torch.float32, device=video_u8.device)
+    call("fod_clip_crop_resize", ptr(video_u8), ptr(out), b, l, c, h0, w0, h, w, sb, sl, ptr(plans), ptr(mean), ptr(std),
+         stream())
+    return out
+
+
 def conv_stem_fwd(xp, w, h, wd, *, shift=None, relu=True):
     """xp: haloed layout of an [*, 3, h, wd] clip; w [Cout, 7, 8, 4] -> y NHWC [F, Ho, Wo, Cout]."""
     _chk(xp, "xp"); _chk(w, "w", xp.dtype)

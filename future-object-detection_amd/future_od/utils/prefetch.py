@@ -10,6 +10,10 @@ batch is copied from pinned host memory on a side stream while the current step 
 
 The batch dict keeps `_host_annotations` (see `recursive_to`), which the model uses to build the targets without
 reading anything back from the device.
+
+A loader that carries a `device_transform` (future_od/utils/augment.py: DeviceJointTransform) yields RAW uint8 clips:
+its `host` half runs before the pinned copy (plans drawn, annotations transformed), its `device` half inside the
+side-stream block right after the copy, so the crop / resize kernel runs under the previous step like the copy does.
 """
 import torch
 
@@ -20,6 +24,10 @@ class DevicePrefetcher:
     def __init__(self, loader, device):
         self.loader = loader
         self.device = torch.device(device)
+        self.transform = getattr(loader, "device_transform", None)
+        if self.transform is not None and self.device.type != "cuda":
+            raise RuntimeError(f"the loader's device transform needs a GPU, not {self.device}: the crop / resize of raw "
+                               "frames is a HIP kernel without a CPU fallback, and skipping it would train on other data")
         self.stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
 
     def __len__(self):
@@ -33,12 +41,17 @@ class DevicePrefetcher:
         if self.stream is None:
             return recursive_to(batch, self.device), None
         host = {}
+        if self.transform is not None:
+            batch = self.transform.host(batch)
+            batch.pop(HOST_ANNOTATIONS)          # the transformed host tensors; kept below, not uploaded twice
         if isinstance(batch, dict) and all(k in batch for k in _ANNOTATION_KEYS):
             host = {k: batch[k] for k in _ANNOTATION_KEYS
                     if isinstance(batch[k], torch.Tensor) and batch[k].device.type == "cpu"}
         with torch.cuda.stream(self.stream):
             moved = _walk(batch, lambda t: (t if t.is_pinned() else t.pin_memory()).to(self.device, non_blocking=True)
                           if t.device.type == "cpu" else t)
+            if self.transform is not None:
+                moved = self.transform.device(moved)
             ready = self.stream.record_event()
         if len(host) == len(_ANNOTATION_KEYS) and HOST_ANNOTATIONS not in moved:
             moved[HOST_ANNOTATIONS] = host

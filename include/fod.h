@@ -45,7 +45,7 @@ enum { FOD_OK = 0, FOD_ERR_ARG = 1, FOD_ERR_LAUNCH = 2, FOD_ERR_RUNTIME = 3 };
 size_t fod_last_error(char* buf, size_t cap);
 /* ABI version of this header; the loader refuses a library that disagrees. */
 int fod_abi_version(void);
-#define FOD_ABI_VERSION 5
+#define FOD_ABI_VERSION 6
 
 /* Fused epilogue of the NT contraction family.  In order:
  *   v = acc * scale[n] + shift[n];  v += residual[row(m), n];  v = relu ? max(v,0) : v;
@@ -279,6 +279,20 @@ int fod_u8_nchw_to_nhwc(int dtype, const unsigned char* src, void* dst, int F, i
 int fod_clip_to_stem_layout(int dtype, int src_u8, const void* src, void* dst, int F, int C, int H, int W, int Hp,
                             int Wp, int inner, long stride_outer, long stride_inner, const float* mean,
                             const float* std, fod_stream_t stream);
+
+/* Image half of the reference's joint augmentation (future_od/datasets/transforms.py:41-61 JointResize, 64-101 the
+ * crops, 152-163 JointHorizontalFlip; composed by the loaders, runs/_loader.py:30-35,74-79) applied to RAW uint8 frames
+ * on the device: dst[b][l][c][y][x] (f32, contiguous [B][L][C][H][W], 16-byte aligned) is the bilinear sample
+ * (align_corners = False, no antialiasing: torch.nn.functional.interpolate's arithmetic, in f32 on the 0..255 values) of
+ * the crop rectangle of frame (b, l), then ((v / 255) - mean[c]) / std[c] as fod_clip_to_stem_layout normalises.
+ * src: uint8 planes [C <= 3][H0][W0] per frame, frame (b, l) at src + b*src_stride_b + l*src_stride_l (bytes).
+ * plans: DEVICE int32 [B][5] = (top, left, height, width, flip), one row per clip, shared by its L frames and read by
+ * the kernel; a rectangle that leaves the frame is clamped into it (extent first, then origin), never read outside.
+ * The four neighbours of a sample are clamped to the crop rectangle (crop-then-resize never sees pixels outside the
+ * crop); flip != 0 mirrors the output columns.  height == H and width == W copies the rectangle exactly. */
+int fod_clip_crop_resize(const unsigned char* src, float* dst, int B, int L, int C, int H0, int W0, int H, int W,
+                         long src_stride_b, long src_stride_l, const int* plans, const float* mean, const float* std,
+                         fod_stream_t stream);
 
 /* dst[i0][i1][i2] = src[i0*s0 + i1*s1 + i2*s2] * scale[index on scale_axis]   (i2 >= valid2 -> 0)
  * src_dtype/dst_dtype independent.  Weight preparation (cast, transpose, BN-scale fold, channel pad)
