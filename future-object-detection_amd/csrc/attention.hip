@@ -18,6 +18,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 // 2^x as ONE v_exp_f32: exp2f() lowers to six instructions (range test, two selects, add, exp, ldexp) to keep
@@ -1493,10 +1494,10 @@ int launch_all(int which, const AttnParams& p, hipStream_t stream) {
   const dim3 block(256);
   // few queries: spend the block's four waves on the key dimension instead (see attn_fwd_kernel)
   const bool split = p.Tq <= 512 && p.S >= 128;
+  const Knobs kn = fod_knobs();
   if (which == 0) {
-    static const char* env_lds = getenv("FOD_ATTN_LDS");
-    if (sizeof(T) == 2 && !DROP && !split && !(env_lds && env_lds[0] == '0')) {
-      if (env_lds && env_lds[0] == '4')
+    if (sizeof(T) == 2 && !DROP && !split && kn.attn_lds != 0) {
+      if (kn.attn_lds == 4)
         hipLaunchKernelGGL((attn_fwd_lds_kernel<PARTS, 4>), dim3(ceil_div(p.Tq, 128), p.H, p.B), dim3(256), 0, stream, p);
       else
         hipLaunchKernelGGL((attn_fwd_lds_kernel<PARTS, 8>), dim3(ceil_div(p.Tq, 256), p.H, p.B), dim3(512), 0, stream, p);
@@ -1505,8 +1506,7 @@ int launch_all(int which, const AttnParams& p, hipStream_t stream) {
     else
       hipLaunchKernelGGL((attn_fwd_kernel<T, PARTS, false, DROP>), dim3(ceil_div(p.Tq, 128), p.H, p.B), block, 0, stream, p);
   } else if (which == 1) {
-    static const char* env_lds = getenv("FOD_ATTN_LDS");
-    if (sizeof(T) == 2 && !DROP && !split && !(env_lds && env_lds[0] == '0'))
+    if (sizeof(T) == 2 && !DROP && !split && kn.attn_lds != 0)
       hipLaunchKernelGGL((attn_bwd_dq_lds_kernel<PARTS, 4>), dim3(ceil_div(p.Tq, 128), p.H, p.B), dim3(256), 0, stream, p);
     else if (split)
       hipLaunchKernelGGL((attn_bwd_dq_kernel<T, PARTS, true, DROP>), dim3(ceil_div(p.Tq, 32) * p.ksplit, p.H, p.B), block, 0, stream, p);
@@ -1514,12 +1514,10 @@ int launch_all(int which, const AttnParams& p, hipStream_t stream) {
       hipLaunchKernelGGL((attn_bwd_dq_kernel<T, PARTS, false, DROP>), dim3(ceil_div(p.Tq, 128), p.H, p.B), block, 0, stream, p);
   } else {
     const dim3 grid(ceil_div(p.S, 128), p.H, p.B);
-    static const char* env_pf = getenv("FOD_ATTN_PF");
-    static const char* env_lds = getenv("FOD_ATTN_LDS");
     // the three LDS kernels go together (same predicate as the forward and dq passes): they share the score arithmetic
-    if (sizeof(T) == 2 && !DROP && !split && !(env_lds && env_lds[0] == '0'))
+    if (sizeof(T) == 2 && !DROP && !split && kn.attn_lds != 0)
       hipLaunchKernelGGL((attn_bwd_dkv_lds_kernel<PARTS, 4>), grid, block, 0, stream, p);
-    else if (sizeof(T) == 2 && !(env_pf && env_pf[0] == '0'))
+    else if (sizeof(T) == 2 && kn.attn_pf != 0)
       hipLaunchKernelGGL((attn_bwd_dkv_pf_kernel<PARTS, DROP>), grid, block, 0, stream, p);
     else
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, PARTS, DROP>), grid, block, 0, stream, p);

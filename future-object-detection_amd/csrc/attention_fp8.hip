@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "knobs.h"
 
 namespace {
 typedef __attribute__((ext_vector_type(8))) int i32x8;
@@ -440,8 +441,7 @@ extern "C" int fod_attn_fwd_fp8(const void* q_pack, const void* kv_pack, int par
   const dim3 grid(ceil_div(p.Tq, 256), p.H, p.B);
   // one 64-key tile per barrier by default: measured 42.1 us against 43.6 us with two (encoder shape, 10 frames; bf16
   // kernel 45.5-46.2 us; profiles/r03e_fp8_attention_microbench.txt).  FOD_FP8_STAGE=2: two tiles per barrier
-  static const char* env_st = getenv("FOD_FP8_STAGE");
-  const bool one = !(env_st && env_st[0] == '2');
+  const bool one = fod_knobs().fp8_stage != 2;
   if (parts == 2 && one) hipLaunchKernelGGL((attn_fwd_fp8_kernel<2, 1>), grid, dim3(512), 0, stream, p);
   else if (parts == 2) hipLaunchKernelGGL((attn_fwd_fp8_kernel<2, 2>), grid, dim3(512), 0, stream, p);
   else if (one) hipLaunchKernelGGL((attn_fwd_fp8_kernel<1, 1>), grid, dim3(512), 0, stream, p);

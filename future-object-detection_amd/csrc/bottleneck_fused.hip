@@ -31,6 +31,7 @@
 // asked L2 for one step earlier); v4 removes the weight traffic and the LDS slab round trip and is within 1.3-1.6 x of what
 // its bytes cost at 5 TB/s.
 #include "common.h"
+#include "knobs.h"
 #include "lds_dma.h"
 
 namespace {
@@ -655,8 +656,7 @@ extern "C" int fod_bottleneck_fused_fwd(int dtype, const void* x, const void* w1
   p.w1 = (const __bf16*)w1; p.w2 = (const __bf16*)w2; p.w3 = (const __bf16*)w3; p.wd = (const __bf16*)wd;
   p.b1 = b1; p.b2 = b2; p.b3 = b3; p.bd = bd;
   p.N = Nimg; p.H = H; p.W = W; p.Cin = Cin;
-  const char* ver = getenv("FOD_BNK_VERSION");
-  if (!(ver && ver[0] == '2') && (long)Nimg * H * W * Cin * 2 < 0xFFFFFFF0L) {
+  if (fod_knobs().bnk_version != 2 && (long)Nimg * H * W * Cin * 2 < 0xFFFFFFF0L) {
     // v4: one persistent workgroup per CU
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;

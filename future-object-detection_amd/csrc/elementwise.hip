@@ -5,6 +5,7 @@
 
 #include "common.h"
 #include "det_reduce.h"
+#include "knobs.h"
 
 namespace {
 
@@ -864,12 +865,8 @@ extern "C" int fod_layernorm_fwd(int dtype, const void* x, const void* residual,
 
 // row groups a wave of the many-row layer-norm backward walks (FOD_LN_BWD_GROUPS; measured at the encoder's 14 500 rows)
 static int ln_bwd_groups() {
-  static const int v = [] {
-    const char* e = getenv("FOD_LN_BWD_GROUPS");
-    const int n = e ? atoi(e) : 4;
-    return n >= 1 && n <= 16 ? n : 4;
-  }();
-  return v;
+  const int n = fod_knobs().ln_bwd_groups;
+  return n >= 1 && n <= 16 ? n : 4;
 }
 
 extern "C" int fod_layernorm_bwd(int dtype, const void* dy, const void* xsum, const float* mean, const float* rstd,

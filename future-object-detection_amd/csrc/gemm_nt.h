@@ -1,6 +1,7 @@
 // Shared between gemm_nt.hip (128-row tiles, register-staged ring) and gemm_nt_big.hip (256-row tiles, LDS-DMA ring).
 #pragma once
 #include "common.h"
+#include "knobs.h"
 
 namespace fodnt {
 
@@ -58,9 +59,13 @@ constexpr int ROW_BYTES = 128;   // bytes of k per tile row
 
 FOD_DEVINL int lds_off(int row, int chunk) { return row * ROW_BYTES + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
-// gemm_nt_big.hip: the 256 x 128 LDS-DMA kernel for large bf16 problems
-bool big_applies(int mode, const NtParams& p);
-int launch_big_mode(int mode, const NtParams& p, hipStream_t stream);
+constexpr int BMB = 256, BKB_EL = 64;   // gemm_nt_big.hip: rows and k elements of its tiles
 
+// Which kernel takes a problem and how: decided by route() (gemm_nt.hip) from the checked parameters and a snapshot of
+// the knobs, and by nothing else -- the launchers below only launch what it says.
+typedef fod_nt_route NtRoute;
+NtRoute route(int mode, int dtype, const NtParams& p, const Knobs& kn);
+// gemm_nt_big.hip: r.kernel == FOD_ROUTE_NT_BIG
+int launch_big(int mode, const NtParams& p, const NtRoute& r, hipStream_t stream);
 
 }  // namespace fodnt

@@ -29,6 +29,7 @@
 
 #include "common.h"
 #include "gemm_nt.h"
+#include "gemm_tn.h"
 
 namespace {
 
@@ -732,44 +733,17 @@ __global__ __launch_bounds__(256) void gemm_nt_small_kernel(const NtParams p) {
   FOD_STAMP(4);
 }
 
-// The short-launch kernel is used when its 64 x 64 tiles fit the chip in one wave of blocks.
-bool use_small_nt(int dtype, const NtParams& p) {
-  const char* env = getenv("FOD_NT_SMALL");
-  if (env && env[0] == '0') return false;
-  if (dtype != FOD_BF16 || !p.vec_epi) return false;
-  const long blocks = (long)ceil_div(p.M, 64) * ceil_div(p.N, 64);
-  if (blocks > 256) return false;
-  // residual / mask are addressed with 31-bit byte offsets
-  if (p.res && ((long)(p.res_row_mod > 0 ? p.res_row_mod : p.M) * p.ldr + p.N) * 2 >= 0x7FFFFFF0L) return false;
-  if (p.mask && ((long)p.M * p.ldmask + p.N) * 2 >= 0x7FFFFFF0L) return false;
-  return true;
-}
-
 template <typename T, int MODE>
-int launch_nt(const NtParams& p, hipStream_t stream) {
-  if constexpr (std::is_same<T, __bf16>::value) {
-    if (big_applies(MODE, p)) return launch_big_mode(MODE, p, stream);
-  }
+int launch_128(const NtParams& p, const NtRoute& r, hipStream_t stream) {
   NtParams q = p;
   q.gy = ceil_div(p.M, BM);
-  // 64-wide tiles also when 128-wide ones would leave CUs with a single block (or none): a block's prologue and
-  // epilogue (~4.5 us) then overlap nothing; two narrower blocks per CU overlap each other
-  static const char* env_narrow = getenv("FOD_NT_NARROW");
-  const int narrow_below = env_narrow ? atoi(env_narrow) : 320;
-  // ... and when the last round of 128-wide blocks would leave most of the chip idle: fill = tiles / (rounds x
-  // resident blocks), 2 wide or 3 narrow blocks per CU (registers / LDS); a narrow tile is ~10 % less efficient per
-  // FLOP, hence the margin.  layer4's 3x3 convolutions (544 wide tiles: 53 % -> 71 %): forward 0.149 -> 0.130 ms,
-  // input gradient 0.203 -> 0.174 ms; the layer1/2 shapes (tens of thousands of tiles) stay wide.
-  const long t_wide = (long)q.gy * ceil_div(p.N, 128), t_narrow = (long)q.gy * ceil_div(p.N, 64);
-  const double fill_wide = (double)t_wide / (double)(ceil_div(t_wide, 512L) * 512L);
-  const double fill_narrow = (double)t_narrow / (double)(ceil_div(t_narrow, 768L) * 768L);
-  const bool narrow = p.N <= 64 || t_wide < narrow_below || (!env_narrow && fill_narrow > 1.15 * fill_wide);
+  const bool narrow = r.tile_n == 64;
   const dim3 block(256);
   constexpr int BK = ROW_BYTES / (int)sizeof(T);
   const bool utap = MODE != MODE_DENSE && MODE != MODE_STEM && p.Cs % BK == 0;     // a k-tile never straddles two taps
-  q.gx = ceil_div(p.N, narrow ? 64 : 128);
+  q.gx = ceil_div(p.N, r.tile_n);
   const dim3 grid(q.gx * ((q.gy + 7) / 8 * 8));
-  const size_t lds = 2 * (BM + (narrow ? 64 : 128)) * ROW_BYTES;
+  const size_t lds = 2 * (BM + r.tile_n) * ROW_BYTES;
 #define FOD_NT_LAUNCH(KERNEL_NT1, KERNEL_NT2)                                        \
   do {                                                                               \
     if (narrow) hipLaunchKernelGGL((KERNEL_NT1), grid, block, lds, stream, q);       \
@@ -794,16 +768,21 @@ int launch_nt(const NtParams& p, hipStream_t stream) {
   return FOD_OK;
 }
 
+// Launches what route() decided for the checked parameters `p`.
 template <int MODE>
-int dispatch_nt(int dtype, const NtParams& p, hipStream_t stream) {
-  if (dtype == FOD_BF16) return launch_nt<__bf16, MODE>(p, stream);
-  if (dtype == FOD_F32) return launch_nt<float, MODE>(p, stream);
-  fod_set_error("gemm_nt: bad dtype %d", dtype);
-  return FOD_ERR_ARG;
-}
-
-int check_epilogue(const fod_epilogue* e) {
-  (void)e;
+int launch(int dtype, const NtParams& p, hipStream_t stream) {
+  if (dtype != FOD_BF16 && dtype != FOD_F32) {
+    fod_set_error("gemm_nt: bad dtype %d", dtype);
+    return FOD_ERR_ARG;
+  }
+  const NtRoute r = route(MODE, dtype, p, fod_knobs());
+  if (r.kernel == FOD_ROUTE_NT_BIG) return launch_big(MODE, p, r, stream);
+  if (r.kernel == FOD_ROUTE_NT_128)
+    return dtype == FOD_BF16 ? launch_128<__bf16, MODE>(p, r, stream) : launch_128<float, MODE>(p, r, stream);
+  NtParams q = p;
+  q.ksplit = r.ksplit > 1 ? r.ksplit : 0;   // 64 tiles x 8 splits x 64 x 64 f32 = FOD_NT_SPLIT_WS_FLOATS
+  hipLaunchKernelGGL(gemm_nt_small_kernel, dim3(ceil_div(p.N, 64), ceil_div(p.M, 64), r.ksplit), dim3(256), 0, stream, q);
+  FOD_LAUNCH_CHECK();
   return FOD_OK;
 }
 
@@ -830,16 +809,110 @@ void decide_vec_epilogue(NtParams& p) {
 
 }  // namespace
 
-extern "C" int fod_gemm_nt(int dtype, const void* A, long lda, int a_row_mod, const void* B, long ldb,
-                           void* C, long ldc, int M, int N, int K, const fod_epilogue* epi,
-                           hipStream_t stream) {
+namespace fodnt {
+namespace {
+// The short-launch kernel is used when its 64 x 64 tiles fit the chip in one wave of blocks.
+bool small_applies(int dtype, const NtParams& p, const Knobs& kn) {
+  if (!kn.nt_small) return false;
+  if (dtype != FOD_BF16 || !p.vec_epi) return false;
+  const long blocks = (long)ceil_div(p.M, 64) * ceil_div(p.N, 64);
+  if (blocks > 256) return false;
+  // residual / mask are addressed with 31-bit byte offsets
+  if (p.res && ((long)(p.res_row_mod > 0 ? p.res_row_mod : p.M) * p.ldr + p.N) * 2 >= 0x7FFFFFF0L) return false;
+  if (p.mask && ((long)p.M * p.ldmask + p.N) * 2 >= 0x7FFFFFF0L) return false;
+  return true;
+}
+
+// The 256 x 256 tile where it fills the chip (N a multiple of 256, >= 200 square tiles): layer3's 3x3 convolutions at the
+// headline extent, 863 -> 1027 TFLOP/s forward, 831 -> 977 input gradient (profiles/r03q_square_tile.txt).  layer4 (14 500
+// rows: 114 square tiles for 256 CUs) stays on 256 x 128.  FOD_NT_BIG256: "0" = never, "2" = whenever N >= 256 (tests).
+bool big256_applies(const NtParams& p, const Knobs& kn) {
+  if (kn.nt_big256 == 0) return false;
+  if (p.N < 256) return false;
+  if (kn.nt_big256 == 2) return true;
+  const long tiles = (long)ceil_div(p.M, BMB) * ceil_div(p.N, 256);
+  return p.N % 256 == 0 && tiles >= 200;
+}
+
+// Whether a bf16 problem (operands 16-byte aligned) should take the 256-row LDS-DMA kernel: the vector epilogue applies,
+// conv modes have a block-uniform tap walk, the contraction is deep and there are
+// enough tiles for the chip.  Measured per ResNet-50 layer at 10 x 900 x 1600 (profiles/r02f_conv_layers_big_vs_128.txt):
+// +10..15 % where K >= 2048 (3x3 convolutions of layer3 / layer4, layer4's 1x1 reductions: 750 -> 850, 790 -> 900
+// TFLOP/s; 4096^3: 767 -> 952), break-even around K = 1024, and a LOSS on shallow or narrow problems (K <= 576 or
+// N = 64: the pipeline never fills / half the 128-wide tile is padding), which therefore stay on the 128-row kernel.
+bool big_applies(int mode, const NtParams& p, const Knobs& kn) {
+  if (kn.nt_big == 0) return false;
+  if (!p.vec_epi || p.a_seg_len || p.c_seg_cols) return false;
+  if (mode == MODE_STEM) return false;
+  if (mode != MODE_DENSE && (p.Cs % BKB_EL != 0 || p.K < BKB_EL)) return false;
+  if (mode == MODE_DENSE && p.K % 8 != 0) return false;
+  if (p.N % 4 != 0) return false;
+  const long tiles = (long)ceil_div(p.M, BMB) * ceil_div(p.N, 128);
+  if (kn.nt_big == 2) return true;                      // always (tests)
+  // (convolution modes only: the encoder's 14 500 x 2048 x 256 GEMMs took 37.6 us on the square tile against 30.3 on the
+  // 128-row kernel -- four k-tiles per block do not pay for the two-pass epilogue)
+  if (mode != MODE_DENSE && p.K >= kn.nt_big256_mink && p.K < 1536 && big256_applies(p, kn)) return true;
+  return p.K >= kn.nt_big_mink && p.N >= kn.nt_big_minn && tiles >= 200;
+}
+}  // namespace
+
+NtRoute route(int mode, int dtype, const NtParams& p, const Knobs& kn) {
+  NtRoute r{};
+  r.ksplit = 1;
+  if (mode == MODE_DENSE && small_applies(dtype, p, kn)) {
+    r.kernel = FOD_ROUTE_NT_SMALL;
+    r.tile_n = 64;
+    // deep K on few tiles (the decoder's feed-forward: 256 x 256 x 2048 = 16 blocks walking 64 units each, 18-24 us):
+    // split K across blocks so the launch covers more of the chip
+    const long tiles = (long)ceil_div(p.N, 64) * ceil_div(p.M, 64);
+    if (p.K >= 1024 && tiles <= 64 && kn.nt_splitk != 0) {
+      // at most 4 splits (FOD_NT_SPLITK=n: n): the merge reads every partial tile with scalar sc1 loads, ~1.2 us each;
+      // measured whole step 21.95 / 22.09 ms at 4, 22.09 / 22.18 at 8, 22.12 / 22.02 at 2 (same box, alternating)
+      const int cap = kn.nt_splitk > 1 ? (kn.nt_splitk < 8 ? kn.nt_splitk : 8) : 4;   // scratch holds 8
+      int ks = (int)(256 / tiles);
+      if (ks > cap) ks = cap;
+      if (ks > p.K / 256) ks = p.K / 256;
+      r.wants_split_ws = ks > 1;
+      if (ks > 1 && p.split_ws && p.split_tickets) r.ksplit = ks;
+    }
+    return r;
+  }
+  if (dtype == FOD_BF16 && big_applies(mode, p, kn)) {
+    r.kernel = FOD_ROUTE_NT_BIG;
+    const bool square = big256_applies(p, kn);
+    r.tile_n = square ? 256 : 128;
+    r.stages = square ? 2 : 3;
+    r.interleave = kn.nt_big_ilv == Knobs::AUTO ? r.stages == 3 : kn.nt_big_ilv != 0;
+    return r;
+  }
+  r.kernel = FOD_ROUTE_NT_128;
+  r.stages = 2;
+  // 64-wide tiles also when 128-wide ones would leave CUs with a single block (or none): a block's prologue and
+  // epilogue (~4.5 us) then overlap nothing; two narrower blocks per CU overlap each other
+  const int narrow_below = kn.nt_narrow == Knobs::AUTO ? 320 : kn.nt_narrow;
+  // ... and when the last round of 128-wide blocks would leave most of the chip idle: fill = tiles / (rounds x
+  // resident blocks), 2 wide or 3 narrow blocks per CU (registers / LDS); a narrow tile is ~10 % less efficient per
+  // FLOP, hence the margin.  layer4's 3x3 convolutions (544 wide tiles: 53 % -> 71 %): forward 0.149 -> 0.130 ms,
+  // input gradient 0.203 -> 0.174 ms; the layer1/2 shapes (tens of thousands of tiles) stay wide.
+  const long gy = ceil_div(p.M, BM);
+  const long t_wide = gy * ceil_div(p.N, 128), t_narrow = gy * ceil_div(p.N, 64);
+  const double fill_wide = (double)t_wide / (double)(ceil_div(t_wide, 512L) * 512L);
+  const double fill_narrow = (double)t_narrow / (double)(ceil_div(t_narrow, 768L) * 768L);
+  const bool narrow = p.N <= 64 || t_wide < narrow_below || (kn.nt_narrow == Knobs::AUTO && fill_narrow > 1.15 * fill_wide);
+  r.tile_n = narrow ? 64 : 128;
+  return r;
+}
+}  // namespace fodnt
+
+namespace {
+// Checks the arguments of fod_gemm_nt and fills the launch parameters.  The operands may be NULL (a route query).
+int dense_params(NtParams& p, int dtype, const void* A, long lda, int a_row_mod, const void* B, long ldb, void* C,
+                 long ldc, int M, int N, int K, const fod_epilogue* epi) {
   const int vec = dtype == FOD_BF16 ? 8 : 4;
-  FOD_REQUIRE(A && B && C, "gemm_nt: null operand");
   FOD_REQUIRE(M > 0 && N > 0 && K > 0, "gemm_nt: empty problem %d %d %d", M, N, K);
   FOD_REQUIRE(K % vec == 0 && lda % vec == 0 && ldb % vec == 0,
               "gemm_nt: K=%d lda=%ld ldb=%ld must be multiples of %d", K, lda, ldb, vec);
   FOD_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "gemm_nt: operands must be 16-byte aligned");
-  NtParams p{};
   p.A = A; p.B = B; p.C = C;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.M = M; p.N = N; p.K = K;
@@ -852,27 +925,26 @@ extern "C" int fod_gemm_nt(int dtype, const void* A, long lda, int a_row_mod, co
   FOD_REQUIRE(ab < 0xFFFFFFF0L - 16 && bb < 0xFFFFFFF0L - 16, "gemm_nt: operand larger than 4 GiB");
   p.a_bytes = (unsigned)ab;
   p.b_bytes = (unsigned)bb;
-  if (use_small_nt(dtype, p)) {
-    // deep K on few tiles (the decoder's feed-forward: 256 x 256 x 2048 = 16 blocks walking 64 units each, 18-24 us):
-    // split K across blocks so the launch covers more of the chip
-    const long tiles = (long)ceil_div(N, 64) * ceil_div(M, 64);
-    int ks = 1;
-    static const char* env_ks = getenv("FOD_NT_SPLITK");             // "0": never (experiments)
-    if (K >= 1024 && tiles <= 64 && !(env_ks && env_ks[0] == '0')) {
-      // at most 4 splits (FOD_NT_SPLITK=n: n): the merge reads every partial tile with scalar sc1 loads, ~1.2 us each;
-      // measured whole step 21.95 / 22.09 ms at 4, 22.09 / 22.18 at 8, 22.12 / 22.02 at 2 (same box, alternating)
-      const int cap = (env_ks && atoi(env_ks) > 1) ? (atoi(env_ks) < 8 ? atoi(env_ks) : 8) : 4;   // scratch holds 8
-      ks = (int)(256 / tiles);
-      if (ks > cap) ks = cap;
-      if (ks > K / 256) ks = K / 256;
-      if (ks > 1 && p.split_ws && p.split_tickets) p.ksplit = ks;   // 64 tiles x 8 splits x 64 x 64 f32 = FOD_NT_SPLIT_WS_FLOATS
-      else ks = 1;
-    }
-    hipLaunchKernelGGL(gemm_nt_small_kernel, dim3(ceil_div(N, 64), ceil_div(M, 64), ks), dim3(256), 0, stream, p);
-    FOD_LAUNCH_CHECK();
-    return FOD_OK;
-  }
-  return dispatch_nt<MODE_DENSE>(dtype, p, stream);
+  return FOD_OK;
+}
+}  // namespace
+
+extern "C" int fod_gemm_nt(int dtype, const void* A, long lda, int a_row_mod, const void* B, long ldb,
+                           void* C, long ldc, int M, int N, int K, const fod_epilogue* epi,
+                           hipStream_t stream) {
+  FOD_REQUIRE(A && B && C, "gemm_nt: null operand");
+  NtParams p{};
+  if (int rc = dense_params(p, dtype, A, lda, a_row_mod, B, ldb, C, ldc, M, N, K, epi)) return rc;
+  return launch<MODE_DENSE>(dtype, p, stream);
+}
+
+extern "C" int fod_gemm_nt_route(int dtype, long lda, int a_row_mod, long ldb, long ldc, int M, int N, int K,
+                                 const fod_epilogue* epi, fod_nt_route* out) {
+  FOD_REQUIRE(out && (dtype == FOD_BF16 || dtype == FOD_F32), "gemm_nt_route: bad args");
+  NtParams p{};
+  if (int rc = dense_params(p, dtype, nullptr, lda, a_row_mod, nullptr, ldb, nullptr, ldc, M, N, K, epi)) return rc;
+  *out = route(MODE_DENSE, dtype, p, fod_knobs());
+  return FOD_OK;
 }
 
 extern "C" int fod_gemm_nt_grouped(int dtype, const void* A, long lda, int a_seg_len, long a_seg_stride,
@@ -959,10 +1031,12 @@ extern "C" int fod_gemm_nt_batched(int dtype, int batches, const void* A, long l
   return FOD_OK;
 }
 
-static int conv_common(int dtype, bool dgrad, const void* src, const void* w, void* dst,
-                       const fod_conv_geom* g, const fod_epilogue* epi, hipStream_t stream) {
+namespace {
+// Checks the arguments of a convolution forward / input-gradient call and fills the launch parameters.  The operands may be
+// NULL (a route query).
+int conv_params(NtParams& p, int dtype, bool dgrad, const void* src, const void* w, void* dst, const fod_conv_geom* g,
+                const fod_epilogue* epi) {
   const int vec = dtype == FOD_BF16 ? 8 : 4;
-  FOD_REQUIRE(src && w && dst && g, "conv: null operand");
   FOD_REQUIRE(g->stride == 1 || g->stride == 2, "conv: stride %d unsupported", g->stride);
   const int Ho = (g->H + 2 * g->pad - g->kh) / g->stride + 1;
   const int Wo = (g->W + 2 * g->pad - g->kw) / g->stride + 1;
@@ -970,7 +1044,6 @@ static int conv_common(int dtype, bool dgrad, const void* src, const void* w, vo
   FOD_REQUIRE(g->Cin % vec == 0 && g->Cout % vec == 0, "conv: channels %d/%d must be multiples of %d",
               g->Cin, g->Cout, vec);
   FOD_REQUIRE(((uintptr_t)src % 16) == 0 && ((uintptr_t)w % 16) == 0, "conv: operands must be 16-byte aligned");
-  NtParams p{};
   p.A = src; p.B = w; p.C = dst;
   p.kh = g->kh; p.kw = g->kw; p.stride = g->stride; p.pad = g->pad;
   if (!dgrad) {
@@ -997,35 +1070,71 @@ static int conv_common(int dtype, bool dgrad, const void* src, const void* w, vo
   FOD_REQUIRE(ab < 0xFFFFFFF0L - 16 && bb < 0xFFFFFFF0L - 16, "conv: operand larger than 4 GiB");
   p.a_bytes = (unsigned)ab;
   p.b_bytes = (unsigned)bb;
-  if (!dgrad) return dispatch_nt<MODE_CONV>(dtype, p, stream);
-  if (g->stride == 1) return dispatch_nt<MODE_DGRAD>(dtype, p, stream);
-  // stride 2: one launch per input-pixel parity class
-  p.out_H = g->H;
-  p.out_W = g->W;
+  return FOD_OK;
+}
+
+// Stride-2 input gradient: one launch per input-pixel parity class.  Fills q for class `cls` of p; false = the class has
+// no launch.
+bool dgrad_s2_class(NtParams& q, const NtParams& p, const fod_conv_geom* g, int cls) {
+  q = p;
+  q.out_H = g->H;
+  q.out_W = g->W;
+  q.par_h = cls >> 1;
+  q.par_w = cls & 1;
+  q.Hd = (g->H - q.par_h + 1) / 2;
+  q.Wd = (g->W - q.par_w + 1) / 2;
+  if (q.Hd <= 0 || q.Wd <= 0) return false;
+  q.r_first = (q.par_h + g->pad) & 1;
+  q.s_first = (q.par_w + g->pad) & 1;
+  const int n_r = q.r_first < g->kh ? (g->kh - q.r_first + 1) / 2 : 0;
+  q.n_s = q.s_first < g->kw ? (g->kw - q.s_first + 1) / 2 : 0;
+  q.off_h = (q.par_h + g->pad - q.r_first) / 2;
+  q.off_w = (q.par_w + g->pad - q.s_first) / 2;
+  q.M = g->Nimg * q.Hd * q.Wd;
+  q.K = n_r * q.n_s * g->Cout;          // may be 0 (1x1 stride 2, odd classes): the epilogue still runs ...
+  // ... unless the call accumulates in place (residual == dx, "dx += dgrad(dy)", no affine part): a class without
+  // taps then leaves its pixels as they are -- three of the four launches of a 1x1 stride-2 convolution
+  if (q.K == 0 && p.res == p.C && p.res != nullptr && !p.scale && !p.shift && !p.relu && p.ldr == p.ldc) return false;
+  if (q.n_s == 0) q.n_s = 1;
+  return true;
+}
+
+int conv_common(int dtype, bool dgrad, const void* src, const void* w, void* dst, const fod_conv_geom* g,
+                const fod_epilogue* epi, hipStream_t stream) {
+  FOD_REQUIRE(src && w && dst && g, "conv: null operand");
+  NtParams p{};
+  if (int rc = conv_params(p, dtype, dgrad, src, w, dst, g, epi)) return rc;
+  if (!dgrad) return launch<MODE_CONV>(dtype, p, stream);
+  if (g->stride == 1) return launch<MODE_DGRAD>(dtype, p, stream);
   for (int cls = 0; cls < 4; ++cls) {
-    NtParams q = p;
-    q.par_h = cls >> 1;
-    q.par_w = cls & 1;
-    q.Hd = (g->H - q.par_h + 1) / 2;
-    q.Wd = (g->W - q.par_w + 1) / 2;
-    if (q.Hd <= 0 || q.Wd <= 0) continue;
-    q.r_first = (q.par_h + g->pad) & 1;
-    q.s_first = (q.par_w + g->pad) & 1;
-    const int n_r = q.r_first < g->kh ? (g->kh - q.r_first + 1) / 2 : 0;
-    q.n_s = q.s_first < g->kw ? (g->kw - q.s_first + 1) / 2 : 0;
-    q.off_h = (q.par_h + g->pad - q.r_first) / 2;
-    q.off_w = (q.par_w + g->pad - q.s_first) / 2;
-    q.M = g->Nimg * q.Hd * q.Wd;
-    q.K = n_r * q.n_s * g->Cout;          // may be 0 (1x1 stride 2, odd classes): the epilogue still runs ...
-    // ... unless the call accumulates in place (residual == dx, "dx += dgrad(dy)", no affine part): a class without
-    // taps then leaves its pixels as they are -- three of the four launches of a 1x1 stride-2 convolution
-    if (q.K == 0 && p.res == p.C && p.res != nullptr && !p.scale && !p.shift && !p.relu && p.ldr == p.ldc)
-      continue;
-    if (q.n_s == 0) q.n_s = 1;
-    const int rc = dispatch_nt<MODE_DGRAD_S2>(dtype, q, stream);
-    if (rc) return rc;
+    NtParams q;
+    if (!dgrad_s2_class(q, p, g, cls)) continue;
+    if (int rc = launch<MODE_DGRAD_S2>(dtype, q, stream)) return rc;
   }
   return FOD_OK;
+}
+
+int conv_route(int dtype, bool dgrad, const fod_conv_geom* g, const fod_epilogue* epi, fod_nt_route* out) {
+  FOD_REQUIRE(out && g && (dtype == FOD_BF16 || dtype == FOD_F32), "conv2d_route: bad args");
+  NtParams p{};
+  if (int rc = conv_params(p, dtype, dgrad, nullptr, nullptr, nullptr, g, epi)) return rc;
+  int mode = dgrad ? MODE_DGRAD : MODE_CONV;
+  if (dgrad && g->stride == 2) {
+    NtParams q;
+    FOD_REQUIRE(dgrad_s2_class(q, p, g, 0), "conv2d_route: parity class (0, 0) has no launch");
+    p = q;
+    mode = MODE_DGRAD_S2;
+  }
+  *out = route(mode, dtype, p, fod_knobs());
+  return FOD_OK;
+}
+}  // namespace
+
+extern "C" int fod_conv2d_route(int which, int dtype, const fod_conv_geom* g, const fod_epilogue* epi, int det,
+                                size_t ws_bytes, void* out) {
+  if (which == FOD_CONV_WGRAD) return fodtn::conv_wgrad_route(dtype, g, det, ws_bytes, reinterpret_cast<fod_tn_route*>(out));
+  FOD_REQUIRE(which == FOD_CONV_FWD || which == FOD_CONV_DGRAD, "conv2d_route: which = %d", which);
+  return conv_route(dtype, which == FOD_CONV_DGRAD, g, epi, reinterpret_cast<fod_nt_route*>(out));
 }
 
 extern "C" int fod_conv2d_fwd(int dtype, const void* x, const void* w, void* y, const fod_conv_geom* g,
@@ -1069,5 +1178,5 @@ extern "C" int fod_conv_stem_fwd(int dtype, const void* xp, const void* w, void*
   FOD_REQUIRE(ab < 0xFFFFFFF0L - 16 && bb < 0xFFFFFFF0L - 16, "conv_stem: operand larger than 4 GiB");
   p.a_bytes = (unsigned)ab;
   p.b_bytes = (unsigned)bb;
-  return dispatch_nt<MODE_STEM>(dtype, p, stream);
+  return launch<MODE_STEM>(dtype, p, stream);
 }

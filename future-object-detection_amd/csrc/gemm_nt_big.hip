@@ -17,8 +17,6 @@
 // Replaces, on the reference path, the torch conv2d / linear forward and input-gradient of the large layers:
 // torchvision ResNet convs via reference future_od/models/paper.py:114-116, the encoder's nn.Linear layers
 // future_od/models/transformer.py:407-411.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -29,7 +27,6 @@ namespace {
 
 using namespace fodnt;
 
-constexpr int BMB = 256, BKB_EL = 64;
 constexpr int A_DMA = BMB / 64;                            // DMA instructions per wave and tile (8 waves x 8 rows each)
 // Two tile shapes: 256 x 128 with a three-stage ring (48 KiB per stage), and -- FOD_NT_BIG256 -- 256 x 256 with a two-stage
 // ring (64 KiB per stage: three would not fit the 160 KiB of LDS).  The stage loop of the 256 x 128 tile runs at the
@@ -403,74 +400,29 @@ int launch_big_ilv(const NtParams& q, hipStream_t stream) {
   return FOD_OK;
 }
 
-template <int MODE, int BNB, int NSTAGE>
-int launch_big(const NtParams& p, hipStream_t stream) {
+template <int MODE>
+int launch_big_mode(const NtParams& p, const NtRoute& r, hipStream_t stream) {
   NtParams q = p;
   q.gy = ceil_div(p.M, BMB);
-  q.gx = ceil_div(p.N, BNB);
+  q.gx = ceil_div(p.N, r.tile_n);
   // Interleaved requests pay with the three-stage ring (256 x 128: layer4's 3x3 convolutions 871 -> 910 TFLOP/s) and COST
   // with the two-stage one (256 x 256: 967 -> 881 -- the tile requested during this one's MFMAs must have landed by their
   // end, so it is requested as early as possible).  FOD_NT_BIG_ILV=0/1 forces either (profiles/r03r_nt_interleave.txt)
-  const char* env = getenv("FOD_NT_BIG_ILV");
-  const bool ilv = env ? env[0] != '0' : NSTAGE == 3;
-  if (!ilv) return launch_big_ilv<MODE, BNB, NSTAGE, false>(q, stream);
-  return launch_big_ilv<MODE, BNB, NSTAGE, true>(q, stream);
-}
-
-// The 256 x 256 tile where it fills the chip (N a multiple of 256, >= 200 square tiles): layer3's 3x3 convolutions at the
-// headline extent, 863 -> 1027 TFLOP/s forward, 831 -> 977 input gradient (profiles/r03q_square_tile.txt).  layer4 (14 500
-// rows: 114 square tiles for 256 CUs) stays on 256 x 128.  FOD_NT_BIG256: "0" = never, "2" = whenever N >= 256 (tests).
-bool big256_applies(const NtParams& p) {
-  const char* env = getenv("FOD_NT_BIG256");
-  if (env && env[0] == '0') return false;
-  if (p.N < 256) return false;
-  if (env && env[0] == '2') return true;
-  const long tiles = (long)ceil_div(p.M, BMB) * ceil_div(p.N, 256);
-  return p.N % 256 == 0 && tiles >= 200;
-}
-
-template <int MODE>
-int launch_big_pick(const NtParams& p, hipStream_t stream) {
-  if (big256_applies(p)) return launch_big<MODE, 256, 2>(p, stream);
-  return launch_big<MODE, 128, 3>(p, stream);
+  if (r.tile_n == 256)
+    return r.interleave ? launch_big_ilv<MODE, 256, 2, true>(q, stream) : launch_big_ilv<MODE, 256, 2, false>(q, stream);
+  return r.interleave ? launch_big_ilv<MODE, 128, 3, true>(q, stream) : launch_big_ilv<MODE, 128, 3, false>(q, stream);
 }
 
 }  // namespace
 
 namespace fodnt {
 
-// Whether a problem (already checked by the caller: bf16, 16-byte aligned operands) should take the 256 x 128 LDS-DMA
-// kernel: the vector epilogue applies, conv modes have a block-uniform tap walk, the contraction is deep and there are
-// enough tiles for the chip.  Measured per ResNet-50 layer at 10 x 900 x 1600 (profiles/r02f_conv_layers_big_vs_128.txt):
-// +10..15 % where K >= 2048 (3x3 convolutions of layer3 / layer4, layer4's 1x1 reductions: 750 -> 850, 790 -> 900
-// TFLOP/s; 4096^3: 767 -> 952), break-even around K = 1024, and a LOSS on shallow or narrow problems (K <= 576 or
-// N = 64: the pipeline never fills / half the 128-wide tile is padding), which therefore stay on the 128-row kernel.
-bool big_applies(int mode, const NtParams& p) {
-  const char* env = getenv("FOD_NT_BIG");            // "0": never, "2": whenever legal (tests), default: large problems
-  if (env && env[0] == '0') return false;
-  if (!p.vec_epi || p.a_seg_len || p.c_seg_cols) return false;
-  if (mode == MODE_STEM) return false;
-  if (mode != MODE_DENSE && (p.Cs % BKB_EL != 0 || p.K < BKB_EL)) return false;
-  if (mode == MODE_DENSE && p.K % 8 != 0) return false;
-  if (p.N % 4 != 0) return false;
-  const long tiles = (long)ceil_div(p.M, BMB) * ceil_div(p.N, 128);
-  if (env && env[0] == '2') return true;                      // always (tests)
-  const char* env_k = getenv("FOD_NT_BIG256_MINK");           // experiment knob: contraction depth from which the square tile is taken
-  const int mink256 = env_k ? atoi(env_k) : 128;
-  // (convolution modes only: the encoder's 14 500 x 2048 x 256 GEMMs took 37.6 us on the square tile against 30.3 on the
-  // 128-row kernel -- four k-tiles per block do not pay for the two-pass epilogue)
-  if (mode != MODE_DENSE && p.K >= mink256 && p.K < 1536 && big256_applies(p)) return true;
-  const char* env_rk = getenv("FOD_NT_BIG_MINK");             // experiment knobs for the 256 x 128 tile's domain
-  const char* env_rn = getenv("FOD_NT_BIG_MINN");
-  return p.K >= (env_rk ? atoi(env_rk) : 1536) && p.N >= (env_rn ? atoi(env_rn) : 256) && tiles >= 200;
-}
-
-int launch_big_mode(int mode, const NtParams& p, hipStream_t stream) {
+int launch_big(int mode, const NtParams& p, const NtRoute& r, hipStream_t stream) {
   switch (mode) {
-    case MODE_DENSE: return launch_big_pick<MODE_DENSE>(p, stream);
-    case MODE_CONV: return launch_big_pick<MODE_CONV>(p, stream);
-    case MODE_DGRAD: return launch_big_pick<MODE_DGRAD>(p, stream);
-    case MODE_DGRAD_S2: return launch_big_pick<MODE_DGRAD_S2>(p, stream);
+    case MODE_DENSE: return launch_big_mode<MODE_DENSE>(p, r, stream);
+    case MODE_CONV: return launch_big_mode<MODE_CONV>(p, r, stream);
+    case MODE_DGRAD: return launch_big_mode<MODE_DGRAD>(p, r, stream);
+    case MODE_DGRAD_S2: return launch_big_mode<MODE_DGRAD_S2>(p, r, stream);
     default: break;
   }
   fod_set_error("gemm_nt_big: unsupported mode %d", mode);

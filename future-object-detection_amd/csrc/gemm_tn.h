@@ -1,6 +1,7 @@
 // Shared between gemm_tn.hip (128 x 128 tiles, register-staged ring) and gemm_tn_big.hip (8-wave tiles, LDS-DMA ring).
 #pragma once
 #include "common.h"
+#include "knobs.h"
 
 namespace fodtn {
 
@@ -32,9 +33,18 @@ struct TnParams {
   float* part_cs;                  // gemm_tn_big.hip: partial column sums [nsplit * waves along j][N1]
 };
 
-// gemm_tn_big.hip: the 8-wave LDS-DMA kernel for long bf16 reductions (conv weight gradients, the encoder's Linear
-// weight gradients).
-bool big_applies(int mode, int dtype, const TnParams& p);
-int launch_big_mode(int mode, const TnParams& p, hipStream_t stream);
+constexpr int MSTEP = 32;   // gemm_tn.hip: reduction rows per step of the 128 x 128 kernel
+constexpr int MS = 64;      // gemm_tn_big.hip: reduction rows per stage
+
+// Which kernel takes a weight gradient and how (tile, M-splits, block order, where the partial results go): decided by
+// route() (gemm_tn.hip) from the checked parameters -- p.det and the caller's workspace among them -- and a snapshot of
+// the knobs, and by nothing else; the launchers only launch what it says.
+typedef fod_tn_route TnRoute;
+TnRoute route(int mode, int dtype, const TnParams& p, const Knobs& kn);
+// gemm_tn_big.hip: r.kernel == FOD_ROUTE_TN_BIG, the 8-wave LDS-DMA kernel for long bf16 reductions (conv weight
+// gradients, the encoder's Linear weight gradients)
+int launch_big(int mode, const TnParams& p, const TnRoute& r, hipStream_t stream);
+// the FOD_CONV_WGRAD half of fod_conv2d_route
+int conv_wgrad_route(int dtype, const fod_conv_geom* g, int det, size_t ws_bytes, fod_tn_route* out);
 
 }  // namespace fodtn

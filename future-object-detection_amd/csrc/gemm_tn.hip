@@ -25,8 +25,6 @@ namespace {
 
 using namespace fodtn;
 
-constexpr int MSTEP = 32;
-
 template <typename T>
 struct TnCfg;
 template <>
@@ -697,66 +695,23 @@ __global__ __launch_bounds__(256) void gemm_tn_multi_kernel(const fod_tn_job* __
   tn_small_body(p, tile % tj, tile / tj, smem, jobs + head + 1, j.chain);
 }
 
-bool use_small_tn(int dtype, const TnParams& p) {
-  static const char* env = getenv("FOD_TN_SMALL");
-  if (env && env[0] == '0') return false;
-  if (dtype != FOD_BF16 || p.M > 512 || p.rscale) return false;
-  if (p.K2 % 4 != 0 || p.ldw % 4 != 0 || ((uintptr_t)p.dW % 16) != 0) return false;
-  if ((long)ceil_div(p.N1, 64) * ceil_div(p.K2, 64) > 256) return false;
-  if (((long)p.N1 * p.ldw + p.K2) * 4 >= 0x7FFFFFF0L) return false;
-  return true;
-}
-
-int pick_splits(int tiles, int M) {
-  // Cost model: a block pays ~12.8 us of f32 atomics for its 128x128 tile (per-CU atomic issue rate)
-  // unless it is the only M-split (then plain stores), and ~0.5 us per 32-row step.
-  //  - small M: one split, no atomics;
-  //  - long reductions (>= 1536 rows per split still left): ~1024 blocks, atomics are < 20 % of a block;
-  //  - otherwise ~1.5 blocks per CU with at least 512 rows each.
-  if (tiles < 1) tiles = 1;
-  if (M <= 512) return 1;
-  int s = 1024 / tiles;
-  if (s >= 1 && M / s >= 1536) return s;
-  s = (384 + tiles - 1) / tiles;
-  const int max_s = M / 512;
-  if (s > max_s) s = max_s;
-  if (s < 1) s = 1;
-  return s;
-}
-
+// Launches what route() decided for the checked parameters `p`.
 template <int MODE>
-int launch_tn(int dtype, TnParams& p, hipStream_t stream) {
-  // long bf16 reductions: the 8-wave LDS-DMA kernel (gemm_tn_big.hip; the bias gradient is fused there too)
-  // nn.Linear layers (MODE_DENSE) stay here by default: in isolation the encoder's feed-forward weight gradients run
-  // 38 -> 30 us on the other kernel, inside the step (graph replay, same box, alternating runs) the difference is within
-  // the noise (22.42 / 22.75 vs 22.60 / 22.69 ms) -- FOD_TN_BIG_DENSE=1 or FOD_TN_BIG=2 (tests) send them there.
-  const char* env_dense = getenv("FOD_TN_BIG_DENSE");
-  const char* env_big = getenv("FOD_TN_BIG");
-  const bool dense_ok = MODE != MODE_DENSE || (env_dense && env_dense[0] == '1') || (env_big && env_big[0] == '2');
-  if (dense_ok && big_applies(MODE, dtype, p)) return launch_big_mode(MODE, p, stream);
-  const int tj = ceil_div(p.K2, 128), ti = ceil_div(p.N1, 128);
-  int splits = pick_splits(ti * tj, p.M);
-  static const char* env_rows = getenv("FOD_TN_ROWS");       // experiment knobs (tools/): rows per split, XCD order
-  static const char* env_xcd = getenv("FOD_TN_XCD");
-  if (env_rows && atoi(env_rows) > 0 && p.M > 512) splits = ceil_div(p.M, atoi(env_rows));
-  // deterministic form: one partial [N1 * K2 (+ N1)] per split in the caller's workspace -- fewer, longer splits where
-  // the planned number would not fit (a single split needs no workspace: plain stores)
-  const long part_floats = (long)p.N1 * p.K2 + (p.colsum ? p.N1 : 0);
-  if (p.det) {
-    const long fit = (long)(p.ws_caller_bytes / sizeof(float)) / part_floats;
-    if (splits > fit) splits = fit < 2 ? 1 : (int)fit;
+int launch(int dtype, TnParams& p, hipStream_t stream) {
+  const TnRoute r = route(MODE, dtype, p, fod_knobs());
+  if (r.kernel == FOD_ROUTE_TN_SMALL) {
+    hipLaunchKernelGGL(gemm_tn_small_kernel, dim3(ceil_div(p.K2, 64), ceil_div(p.N1, 64)), dim3(256), 0, stream, p);
+    FOD_LAUNCH_CHECK();
+    return FOD_OK;
   }
-  // XCD-grouped order (all tiles of an M-split on one XCD, see the kernel): the splits are dealt to the 8 XCDs,
-  // so their count is floored to a multiple of 8; taken when that costs < 10 % of the blocks (measured on the
-  // backbone's wgrads: -25 % time on the 4..16-tile 1x1 / 3x3 layers, +10 % where flooring 28 -> 24 splits).
-  const int s8 = splits / 8 * 8;
-  const bool want_xcd = !(env_xcd && env_xcd[0] == '0') && s8 >= 8 && 10 * s8 >= 9 * splits;
-  if (want_xcd) splits = s8;
-  p.m_per_split = ((p.M + splits - 1) / splits + MSTEP - 1) / MSTEP * MSTEP;
+  if (r.kernel == FOD_ROUTE_TN_BIG) return launch_big(MODE, p, r, stream);
+  const int tj = ceil_div(p.K2, 128), ti = ceil_div(p.N1, 128);
+  const long part_floats = (long)p.N1 * p.K2 + (p.colsum ? p.N1 : 0);
+  p.m_per_split = r.m_per_split;
   p.tj = tj;
   p.ti = ti;
-  p.nsplit = ceil_div(p.M, p.m_per_split);
-  p.xcd_order = (want_xcd && p.nsplit >= 8) ? 1 : 0;
+  p.nsplit = r.nsplit;
+  p.xcd_order = r.xcd_order;
   const dim3 grid = p.xcd_order ? dim3(ti * tj * ((p.nsplit + 7) / 8 * 8)) : dim3(tj, ti, p.nsplit);
   if (p.det) {
     if (dtype != FOD_BF16 && dtype != FOD_F32) {
@@ -776,12 +731,12 @@ int launch_tn(int dtype, TnParams& p, hipStream_t stream) {
     }
     FOD_LAUNCH_CHECK();
     if (p.nsplit == 1) return FOD_OK;
-    foddet::ReduceParams r{};
-    r.part = p.part; r.part_stride = part_floats; r.part_total = (long)p.nsplit * part_floats; r.nparts = p.nsplit;
-    r.out0 = p.dW; r.n0 = p.N1 * p.K2; r.cols0 = p.K2; r.ld0 = p.ldw;
-    r.out1 = p.colsum; r.n1 = p.colsum ? p.N1 : 0;
-    r.accumulate = 1;                           // as the atomic form: added to what the outputs hold (zero or a gradient)
-    return det_reduce_launch(r, 1, stream);
+    foddet::ReduceParams red{};
+    red.part = p.part; red.part_stride = part_floats; red.part_total = (long)p.nsplit * part_floats; red.nparts = p.nsplit;
+    red.out0 = p.dW; red.n0 = p.N1 * p.K2; red.cols0 = p.K2; red.ld0 = p.ldw;
+    red.out1 = p.colsum; red.n1 = p.colsum ? p.N1 : 0;
+    red.accumulate = 1;                         // as the atomic form: added to what the outputs hold (zero or a gradient)
+    return det_reduce_launch(red, 1, stream);
   }
   if (dtype == FOD_BF16) {
     if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_kernel<__bf16>), grid, dim3(256), 0, stream, p);
@@ -799,6 +754,133 @@ int launch_tn(int dtype, TnParams& p, hipStream_t stream) {
 }
 
 }  // namespace
+
+namespace fodtn {
+namespace {
+bool small_applies(int dtype, const TnParams& p, const Knobs& kn) {
+  if (!kn.tn_small) return false;
+  if (dtype != FOD_BF16 || p.M > 512 || p.rscale) return false;
+  if (p.K2 % 4 != 0 || p.ldw % 4 != 0 || ((uintptr_t)p.dW % 16) != 0) return false;
+  if ((long)ceil_div(p.N1, 64) * ceil_div(p.K2, 64) > 256) return false;
+  if (((long)p.N1 * p.ldw + p.K2) * 4 >= 0x7FFFFFF0L) return false;
+  return true;
+}
+
+// M-splits of the 128 x 128 kernel
+int pick_splits(int tiles, int M) {
+  // Cost model: a block pays ~12.8 us of f32 atomics for its 128x128 tile (per-CU atomic issue rate)
+  // unless it is the only M-split (then plain stores), and ~0.5 us per 32-row step.
+  //  - small M: one split, no atomics;
+  //  - long reductions (>= 1536 rows per split still left): ~1024 blocks, atomics are < 20 % of a block;
+  //  - otherwise ~1.5 blocks per CU with at least 512 rows each.
+  if (tiles < 1) tiles = 1;
+  if (M <= 512) return 1;
+  int s = 1024 / tiles;
+  if (s >= 1 && M / s >= 1536) return s;
+  s = (384 + tiles - 1) / tiles;
+  const int max_s = M / 512;
+  if (s > max_s) s = max_s;
+  if (s < 1) s = 1;
+  return s;
+}
+
+// Whether a problem (operands 16-byte aligned, extents < 4 GiB) should take the 8-wave LDS-DMA kernel.
+bool big_applies(int mode, int dtype, const TnParams& p, const Knobs& kn) {
+  if (kn.tn_big == 0) return false;
+  // nn.Linear layers (MODE_DENSE) stay on the 128 x 128 kernel by default: in isolation the encoder's feed-forward weight
+  // gradients run 38 -> 30 us on this one, inside the step (graph replay, same box, alternating runs) the difference is
+  // within the noise (22.42 / 22.75 vs 22.60 / 22.69 ms) -- FOD_TN_BIG_DENSE=1 or FOD_TN_BIG=2 (tests) send them here.
+  if (mode == MODE_DENSE && kn.tn_big_dense != 1 && kn.tn_big != 2) return false;
+  if (dtype != FOD_BF16 || p.g_seg_cols) return false;
+  if (p.N1 % 8 != 0 || p.K2 % 8 != 0 || p.ldg % 8 != 0) return false;
+  if (mode == MODE_DENSE && p.ldx % 8 != 0) return false;
+  if (mode == MODE_CONV && p.Cs % 8 != 0) return false;
+  if (mode == MODE_CONV && (long)p.Hs * p.Ws * p.Cs * 2 >= (1L << 31)) return false;   // 32-bit walks inside one image
+  if (kn.tn_big == 2) return p.M >= 1;
+  // Measured per ResNet-50 layer at 10 x 900 x 1600 and on the encoder's shapes (tools/tn_big_probe.py,
+  // tools/probe_tn_big.hip): a block spends ~3 us in its prologue and ~1.0 us per 64-row stage (the L2 -> LDS stream of
+  // 48 KiB per stage and CU, ~12 TB/s over the chip, not the matrix pipe, sets that); its 32 K-element partial tile
+  // costs ~21 us as f32 atomics (the memory-side atomic rate, whatever the launch) or ~4 us as plain stores plus a
+  // ~6 us reduce launch.  With the partial tiles this kernel wins from ~3 GFLOP per launch upwards (3x3 convolutions
+  // 116 -> 91 us, the encoder's feed-forward weight gradients 38 -> 29 us); below that the 128 x 128 kernel's single
+  // round of small blocks is faster (14500 x 256 x 256: 13 vs 18 us), and so it is for short reductions (the decoder's
+  // memory-side projections, M = 2900 rows: a handful of stages per block).
+  return p.M >= 8192 && p.N1 >= 128 && p.K2 >= 128 && (double)p.M * p.N1 * p.K2 >= kn.tn_big_min;
+}
+
+// Tile shape and M-splits of the 8-wave kernel.  One block per CU (144 KiB of LDS): a launch should be ONE round of <= 256
+// blocks, as close to 256 as the tile count allows (each block pays ~13 us of f32 atomics for its 32 K-element tile
+// whatever its share of the rows); the tile shape with less padding wins, ties go to the one with more blocks in flight.
+void plan_big(TnRoute& r, const TnParams& p, const Knobs& kn) {
+  double best_cost = 1e30;
+  const bool square = (kn.tn_big256 == 2 && p.N1 >= 256 && p.K2 >= 256) ||
+                      (kn.tn_big256 == 1 && p.N1 % 256 == 0 && p.K2 % 256 == 0 && p.M >= 256 * 64);
+  for (int shape = square ? 2 : 0; shape < (square ? 3 : 2); ++shape) {
+    const int bi = shape == 0 ? 128 : 256, bj = shape == 2 ? 256 : 384 - bi;
+    const int ntile = ceil_div(p.N1, bi) * ceil_div(p.K2, bj);
+    int s = 256 / ntile;
+    const int max_s = p.M / 256;
+    if (s > max_s) s = max_s;
+    if (s < 1) s = 1;
+    const int mps = ceil_div(ceil_div(p.M, s), MS) * MS;
+    const int ns = ceil_div(p.M, mps);
+    const int rounds = ceil_div((long)ntile * ns, 256);
+    const double cost = rounds * (mps / MS * 0.55 + 17.0);
+    if (cost < best_cost) {
+      best_cost = cost;
+      r.bi = bi; r.bj = bj; r.nsplit = ns; r.m_per_split = mps;
+    }
+  }
+  if (kn.tn_big_splits > 0) {                   // experiment / test knob: force the split count
+    r.m_per_split = ceil_div(ceil_div(p.M, kn.tn_big_splits), MS) * MS;
+    r.nsplit = ceil_div(p.M, r.m_per_split);
+  }
+}
+}  // namespace
+
+TnRoute route(int mode, int dtype, const TnParams& p, const Knobs& kn) {
+  TnRoute r{};
+  if (mode == MODE_DENSE && small_applies(dtype, p, kn)) {
+    r.kernel = FOD_ROUTE_TN_SMALL;
+    r.bi = r.bj = 64;
+    r.nsplit = 1;
+    r.m_per_split = p.M;
+    return r;
+  }
+  if (big_applies(mode, dtype, p, kn)) {
+    r.kernel = FOD_ROUTE_TN_BIG;
+    plan_big(r, p, kn);
+    r.xcd_order = kn.tn_xcd != 0;
+    // partial tiles in the caller's workspace where it holds them (the deterministic form refuses the call otherwise)
+    const size_t need = (size_t)ceil_div(p.N1, r.bi) * ceil_div(p.K2, r.bj) * r.nsplit * r.bi * r.bj * sizeof(float);
+    r.uses_partials_ws = r.nsplit > 1 && (p.det || (p.ws_caller && need <= p.ws_caller_bytes && ((uintptr_t)p.dW % 16) == 0 &&
+                                                    p.ldw % 4 == 0 && ((uintptr_t)p.ws_caller % 16) == 0 && kn.tn_ws != 0));
+    return r;
+  }
+  r.kernel = FOD_ROUTE_TN_128;
+  r.bi = r.bj = 128;
+  int splits = pick_splits(ceil_div(p.K2, 128) * ceil_div(p.N1, 128), p.M);
+  if (kn.tn_rows > 0 && p.M > 512) splits = ceil_div(p.M, kn.tn_rows);      // experiment knob (tools/): rows per split
+  // deterministic form: one partial [N1 * K2 (+ N1)] per split in the caller's workspace -- fewer, longer splits where
+  // the planned number would not fit (a single split needs no workspace: plain stores)
+  if (p.det) {
+    const long part_floats = (long)p.N1 * p.K2 + (p.colsum ? p.N1 : 0);
+    const long fit = (long)(p.ws_caller_bytes / sizeof(float)) / part_floats;
+    if (splits > fit) splits = fit < 2 ? 1 : (int)fit;
+  }
+  // XCD-grouped order (all tiles of an M-split on one XCD, see the kernel): the splits are dealt to the 8 XCDs,
+  // so their count is floored to a multiple of 8; taken when that costs < 10 % of the blocks (measured on the
+  // backbone's wgrads: -25 % time on the 4..16-tile 1x1 / 3x3 layers, +10 % where flooring 28 -> 24 splits).
+  const int s8 = splits / 8 * 8;
+  const bool want_xcd = kn.tn_xcd != 0 && s8 >= 8 && 10 * s8 >= 9 * splits;
+  if (want_xcd) splits = s8;
+  r.m_per_split = ((p.M + splits - 1) / splits + MSTEP - 1) / MSTEP * MSTEP;
+  r.nsplit = ceil_div(p.M, r.m_per_split);
+  r.xcd_order = (want_xcd && r.nsplit >= 8) ? 1 : 0;
+  r.uses_partials_ws = p.det && r.nsplit > 1;
+  return r;
+}
+}  // namespace fodtn
 
 extern "C" int fod_gemm_tn_grouped(int dtype, const void* G, long ldg, int g_seg_cols, long g_seg_stride,
                                    const void* X, long ldx, float* dW, long ldw, int M, int N1, int K2,
@@ -873,16 +955,17 @@ extern "C" int fod_tn_plan_long(int M, int rows_hint, int* m_per_split, int* nsp
 }
 
 namespace {
-int tn_acc_impl(int det, int dtype, const void* G, long ldg, const void* X, long ldx, float* dW, long ldw, int M, int N1,
-                int K2, const float* row_scale, float* colsum, int accumulate, void* ws, size_t ws_bytes,
-                hipStream_t stream) {
+// A stand-in for an operand that a route query says is there: 16-byte aligned, never dereferenced.
+float* const SOMEWHERE = reinterpret_cast<float*>(uintptr_t(16));
+
+// Checks the arguments of fod_gemm_tn_acc(_det) and fills the launch parameters.  G, X, dW may be NULL (a route query).
+int tn_dense_params(TnParams& p, int det, int dtype, const void* G, long ldg, const void* X, long ldx, float* dW, long ldw,
+                    int M, int N1, int K2, const float* row_scale, float* colsum, int accumulate, void* ws, size_t ws_bytes) {
   const int vec = dtype == FOD_BF16 ? 8 : 4;
-  FOD_REQUIRE(G && X && dW, "gemm_tn: null operand");
   FOD_REQUIRE(M > 0 && N1 > 0 && K2 > 0, "gemm_tn: empty problem");
   FOD_REQUIRE(N1 % vec == 0 && K2 % vec == 0 && ldg % vec == 0 && ldx % vec == 0,
               "gemm_tn: N1=%d K2=%d ldg=%ld ldx=%ld must be multiples of %d", N1, K2, ldg, ldx, vec);
   FOD_REQUIRE(((uintptr_t)G % 16) == 0 && ((uintptr_t)X % 16) == 0, "gemm_tn: operands must be 16-byte aligned");
-  TnParams p{};
   p.G = G; p.X = X; p.dW = dW;
   p.ldg = ldg; p.ldx = ldx; p.ldw = ldw;
   p.M = M; p.N1 = N1; p.K2 = K2;
@@ -897,14 +980,31 @@ int tn_acc_impl(int det, int dtype, const void* G, long ldg, const void* X, long
   FOD_REQUIRE(gb < 0xFFFFFFF0L - 16 && xb < 0xFFFFFFF0L - 16, "gemm_tn: operand larger than 4 GiB");
   p.g_bytes = (unsigned)gb;
   p.x_bytes = (unsigned)xb;
-  if (use_small_tn(dtype, p)) {
-    hipLaunchKernelGGL(gemm_tn_small_kernel, dim3(ceil_div(K2, 64), ceil_div(N1, 64)), dim3(256), 0, stream, p);
-    FOD_LAUNCH_CHECK();
-    return FOD_OK;
-  }
-  return launch_tn<MODE_DENSE>(dtype, p, stream);
+  return FOD_OK;
+}
+
+int tn_acc_impl(int det, int dtype, const void* G, long ldg, const void* X, long ldx, float* dW, long ldw, int M, int N1,
+                int K2, const float* row_scale, float* colsum, int accumulate, void* ws, size_t ws_bytes,
+                hipStream_t stream) {
+  FOD_REQUIRE(G && X && dW, "gemm_tn: null operand");
+  TnParams p{};
+  if (int rc = tn_dense_params(p, det, dtype, G, ldg, X, ldx, dW, ldw, M, N1, K2, row_scale, colsum, accumulate, ws, ws_bytes))
+    return rc;
+  return launch<MODE_DENSE>(dtype, p, stream);
 }
 }  // namespace
+
+extern "C" int fod_gemm_tn_route(int dtype, int M, int N1, int K2, long ldg, long ldx, long ldw, int has_row_scale,
+                                 int has_colsum, int det, size_t ws_bytes, fod_tn_route* out) {
+  FOD_REQUIRE(out && (dtype == FOD_BF16 || dtype == FOD_F32), "gemm_tn_route: bad args");
+  TnParams p{};
+  if (int rc = tn_dense_params(p, det, dtype, nullptr, ldg, nullptr, ldx, nullptr, ldw, M, N1, K2,
+                               has_row_scale ? SOMEWHERE : nullptr, has_colsum ? SOMEWHERE : nullptr, 1,
+                               ws_bytes ? SOMEWHERE : nullptr, ws_bytes))
+    return rc;
+  *out = route(MODE_DENSE, dtype, p, fod_knobs());
+  return FOD_OK;
+}
 
 extern "C" int fod_gemm_tn_acc(int dtype, const void* G, long ldg, const void* X, long ldx, float* dW,
                                long ldw, int M, int N1, int K2, const float* row_scale, float* colsum,
@@ -920,17 +1020,16 @@ extern "C" int fod_gemm_tn_acc_det(int dtype, const void* G, long ldg, const voi
 }
 
 namespace {
-int conv_wgrad_impl(int det, int dtype, const void* dy, const void* x, float* dw, const fod_conv_geom* g,
-                    const float* row_scale, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
+// Checks the arguments of fod_conv2d_wgrad_acc(_det) and fills the launch parameters.  dy, x, dw may be NULL (a route query).
+int tn_conv_params(TnParams& p, int det, int dtype, const void* dy, const void* x, float* dw, const fod_conv_geom* g,
+                   const float* row_scale, int accumulate, void* ws, size_t ws_bytes) {
   const int vec = dtype == FOD_BF16 ? 8 : 4;
-  FOD_REQUIRE(dy && x && dw && g, "conv_wgrad: null operand");
   FOD_REQUIRE(g->Cin % vec == 0 && g->Cout % vec == 0, "conv_wgrad: channels %d/%d must be multiples of %d",
               g->Cin, g->Cout, vec);
   const int Ho = (g->H + 2 * g->pad - g->kh) / g->stride + 1;
   const int Wo = (g->W + 2 * g->pad - g->kw) / g->stride + 1;
   FOD_REQUIRE(Ho == g->Ho && Wo == g->Wo, "conv_wgrad: geometry mismatch");
   FOD_REQUIRE((long)g->Nimg * g->Ho * g->Wo < (1L << 31), "conv_wgrad: pixel count overflows int");
-  TnParams p{};
   p.G = dy; p.X = x; p.dW = dw;
   p.M = g->Nimg * g->Ho * g->Wo;
   p.N1 = g->Cout;
@@ -950,9 +1049,26 @@ int conv_wgrad_impl(int det, int dtype, const void* dy, const void* x, float* dw
   FOD_REQUIRE(gb < 0xFFFFFFF0L - 16 && xb < 0xFFFFFFF0L - 16, "conv_wgrad: operand larger than 4 GiB");
   p.g_bytes = (unsigned)gb;
   p.x_bytes = (unsigned)xb;
-  return launch_tn<MODE_CONV>(dtype, p, stream);
+  return FOD_OK;
+}
+
+int conv_wgrad_impl(int det, int dtype, const void* dy, const void* x, float* dw, const fod_conv_geom* g,
+                    const float* row_scale, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream) {
+  FOD_REQUIRE(dy && x && dw && g, "conv_wgrad: null operand");
+  TnParams p{};
+  if (int rc = tn_conv_params(p, det, dtype, dy, x, dw, g, row_scale, accumulate, ws, ws_bytes)) return rc;
+  return launch<MODE_CONV>(dtype, p, stream);
 }
 }  // namespace
+
+int fodtn::conv_wgrad_route(int dtype, const fod_conv_geom* g, int det, size_t ws_bytes, fod_tn_route* out) {
+  FOD_REQUIRE(out && g && (dtype == FOD_BF16 || dtype == FOD_F32), "conv2d_route: bad args");
+  TnParams p{};
+  if (int rc = tn_conv_params(p, det, dtype, nullptr, nullptr, nullptr, g, nullptr, 1, ws_bytes ? SOMEWHERE : nullptr, ws_bytes))
+    return rc;
+  *out = route(MODE_CONV, dtype, p, fod_knobs());
+  return FOD_OK;
+}
 
 extern "C" int fod_conv2d_wgrad_acc(int dtype, const void* dy, const void* x, float* dw,
                                     const fod_conv_geom* g, const float* row_scale, int accumulate,

@@ -19,8 +19,6 @@
 // Replaces autograd's conv2d / linear weight-gradient kernels behind reference future_od/trainer.py:180
 // (loss.backward()) for the large layers: torchvision ResNet convs via future_od/models/paper.py:114-116, the
 // encoder's nn.Linear layers future_od/models/transformer.py:407-411.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -32,7 +30,6 @@ namespace {
 
 using namespace fodtn;
 
-constexpr int MS = 64;                          // reduction rows per stage
 // 128 x 256 / 256 x 128 tiles: three stages of 48 KiB (BI + BJ = 384 bf16 columns per row), 6 DMA instructions per wave and
 // stage; the 256 x 256 tile (FOD_TN_BIG256): two stages of 64 KiB (three do not fit the 160 KiB of LDS), 8 per wave and stage
 constexpr int tn_stages(int bi, int bj) { return bi + bj == 512 ? 2 : 3; }
@@ -410,6 +407,7 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const TnParams p) {
 // The partial tiles live in the CALLER's workspace (fod_gemm_tn_acc / fod_conv2d_wgrad_acc `ws`, FOD_TN_WS_BYTES = 256
 // blocks x 256 KiB: one round of blocks with room to spare; future_od/native/ops.py keeps one per device and stream).
 // The library allocates nothing; without a workspace (or with one too small for the launch) the atomic epilogue runs.
+// p.ws is set (to that workspace) where the route says so.
 template <int MODE, int BI, int BJ>
 int launch_shape(const TnParams& p, hipStream_t stream) {
   static LdsLimitOnce lds_once;                    // one per instantiation
@@ -418,10 +416,7 @@ int launch_shape(const TnParams& p, hipStream_t stream) {
   const int ntile = p.ti * p.tj;
   const dim3 grid(p.xcd_order ? 8 * ceil_div((long)ntile * p.nsplit, 8) : ntile * p.nsplit);
   TnParams q = p;
-  q.ws = nullptr;
-  const char* env_ws = getenv("FOD_TN_WS");                      // "0": f32 atomics straight into dW (experiments)
   const size_t need = (size_t)ntile * p.nsplit * BI * BJ * sizeof(float);
-  const bool aligned = ((uintptr_t)p.dW % 16) == 0 && p.ldw % 4 == 0;
   if (p.det) {
     // deterministic form: the partial tiles of a split launch and every wave's share of the bias gradient (the WJ waves
     // along j of a block add to the same column sums, also in a launch with one split) go to the workspace or the call
@@ -430,12 +425,9 @@ int launch_shape(const TnParams& p, hipStream_t stream) {
     const size_t need_tiles = p.nsplit > 1 ? need : 0;
     const size_t need_cs = p.colsum ? (size_t)p.nsplit * WJ * p.N1 * sizeof(float) : 0;
     FOD_REQUIRE_SCRATCH("gemm_tn_big (deterministic)", p.ws_caller, p.ws_caller_bytes, need_tiles + need_cs);
-    FOD_REQUIRE(p.nsplit == 1 || aligned, "gemm_tn_big (deterministic): dW must be 16-byte aligned with ldw %% 4 == 0");
-    if (p.nsplit > 1) q.ws = p.ws_caller;
+    FOD_REQUIRE(p.nsplit == 1 || (((uintptr_t)p.dW % 16) == 0 && p.ldw % 4 == 0),
+                "gemm_tn_big (deterministic): dW must be 16-byte aligned with ldw %% 4 == 0");
     if (p.colsum) q.part_cs = p.ws_caller + need_tiles / sizeof(float);
-  } else if (p.nsplit > 1 && p.ws_caller && need <= p.ws_caller_bytes && aligned && ((uintptr_t)p.ws_caller % 16) == 0 &&
-             !(env_ws && env_ws[0] == '0')) {
-    q.ws = p.ws_caller;
   }
   if constexpr (MODE == MODE_DENSE) {
     if (q.part_cs) {
@@ -464,86 +456,23 @@ int launch_shape(const TnParams& p, hipStream_t stream) {
   return FOD_OK;
 }
 
-// Tile shape and M-splits.  One block per CU (144 KiB of LDS): a launch should be ONE round of <= 256 blocks, as close
-// to 256 as the tile count allows (each block pays ~13 us of f32 atomics for its 32 K-element tile whatever its share of
-// the rows); the tile shape with less padding wins, ties go to the one with more blocks in flight.
-struct Plan {
-  int bi, bj, ti, tj, nsplit, m_per_split;
-};
-Plan plan(const TnParams& p) {
-  Plan best{};
-  double best_cost = 1e30;
-  // FOD_TN_BIG256: "1" = the 256 x 256 tile when both output dimensions are multiples of 256 and the reduction is long,
-  // "2" = whenever both are >= 256 (tests), unset / "0" = never
-  const char* env_sq = getenv("FOD_TN_BIG256");
-  const int sq = env_sq ? atoi(env_sq) : 0;
-  const bool square = (sq == 2 && p.N1 >= 256 && p.K2 >= 256) ||
-                      (sq == 1 && p.N1 % 256 == 0 && p.K2 % 256 == 0 && p.M >= 256 * 64);
-  for (int shape = square ? 2 : 0; shape < (square ? 3 : 2); ++shape) {
-    const int bi = shape == 0 ? 128 : 256, bj = shape == 2 ? 256 : 384 - bi;
-    const int ti = ceil_div(p.N1, bi), tj = ceil_div(p.K2, bj);
-    const int ntile = ti * tj;
-    int s = 256 / ntile;
-    const int max_s = p.M / 256;
-    if (s > max_s) s = max_s;
-    if (s < 1) s = 1;
-    const int mps = ceil_div(ceil_div(p.M, s), MS) * MS;
-    const int ns = ceil_div(p.M, mps);
-    const int rounds = ceil_div((long)ntile * ns, 256);
-    const double cost = rounds * (mps / MS * 0.55 + 17.0);
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = Plan{bi, bj, ti, tj, ns, mps};
-    }
-  }
-  return best;
-}
-
 }  // namespace
 
 namespace fodtn {
 
-// Whether a problem (operands already checked by the caller: 16-byte aligned, extents < 4 GiB) should take this kernel.
-bool big_applies(int mode, int dtype, const TnParams& p) {
-  const char* env = getenv("FOD_TN_BIG");            // "0": never, "2": whenever legal (tests), default: long reductions
-  if (env && env[0] == '0') return false;
-  if (dtype != FOD_BF16 || p.g_seg_cols) return false;
-  if (p.N1 % 8 != 0 || p.K2 % 8 != 0 || p.ldg % 8 != 0) return false;
-  if (mode == MODE_DENSE && p.ldx % 8 != 0) return false;
-  if (mode == MODE_CONV && p.Cs % 8 != 0) return false;
-  if (mode == MODE_CONV && (long)p.Hs * p.Ws * p.Cs * 2 >= (1L << 31)) return false;   // 32-bit walks inside one image
-  if (env && env[0] == '2') return p.M >= 1;
-  // Measured per ResNet-50 layer at 10 x 900 x 1600 and on the encoder's shapes (tools/tn_big_probe.py,
-  // tools/probe_tn_big.hip): a block spends ~3 us in its prologue and ~1.0 us per 64-row stage (the L2 -> LDS stream of
-  // 48 KiB per stage and CU, ~12 TB/s over the chip, not the matrix pipe, sets that); its 32 K-element partial tile
-  // costs ~21 us as f32 atomics (the memory-side atomic rate, whatever the launch) or ~4 us as plain stores plus a
-  // ~6 us reduce launch.  With the partial tiles this kernel wins from ~3 GFLOP per launch upwards (3x3 convolutions
-  // 116 -> 91 us, the encoder's feed-forward weight gradients 38 -> 29 us); below that the 128 x 128 kernel's single
-  // round of small blocks is faster (14500 x 256 x 256: 13 vs 18 us), and so it is for short reductions (the decoder's
-  // memory-side projections, M = 2900 rows: a handful of stages per block).
-  const char* env_min = getenv("FOD_TN_BIG_MIN");               // experiment knob: M * N1 * K2 threshold
-  return p.M >= 8192 && p.N1 >= 128 && p.K2 >= 128 && (double)p.M * p.N1 * p.K2 >= (env_min ? atof(env_min) : 2.0e9);
-}
-
-int launch_big_mode(int mode, const TnParams& p, hipStream_t stream) {
+int launch_big(int mode, const TnParams& p, const TnRoute& r, hipStream_t stream) {
   TnParams q = p;
-  const Plan pl = plan(p);
-  q.ti = pl.ti; q.tj = pl.tj; q.nsplit = pl.nsplit; q.m_per_split = pl.m_per_split;
-  const char* env_x = getenv("FOD_TN_XCD");                       // "0": plain block order (experiments)
-  q.xcd_order = (env_x && env_x[0] == '0') ? 0 : 1;
-  const char* env_s = getenv("FOD_TN_BIG_SPLITS");             // experiment / test knob: force the split count
-  if (env_s && atoi(env_s) > 0) {
-    const int s = atoi(env_s);
-    q.m_per_split = ceil_div(ceil_div(p.M, s), MS) * MS;
-    q.nsplit = ceil_div(p.M, q.m_per_split);
-  }
+  q.ti = ceil_div(p.N1, r.bi); q.tj = ceil_div(p.K2, r.bj);
+  q.nsplit = r.nsplit; q.m_per_split = r.m_per_split;
+  q.xcd_order = r.xcd_order;
+  q.ws = r.uses_partials_ws ? p.ws_caller : nullptr;
   if (mode == MODE_DENSE) {
-    if (pl.bj == 256 && pl.bi == 256) return launch_shape<MODE_DENSE, 256, 256>(q, stream);
-    return pl.bi == 128 ? launch_shape<MODE_DENSE, 128, 256>(q, stream) : launch_shape<MODE_DENSE, 256, 128>(q, stream);
+    if (r.bj == 256 && r.bi == 256) return launch_shape<MODE_DENSE, 256, 256>(q, stream);
+    return r.bi == 128 ? launch_shape<MODE_DENSE, 128, 256>(q, stream) : launch_shape<MODE_DENSE, 256, 128>(q, stream);
   }
   if (mode == MODE_CONV) {
-    if (pl.bj == 256 && pl.bi == 256) return launch_shape<MODE_CONV, 256, 256>(q, stream);
-    return pl.bi == 128 ? launch_shape<MODE_CONV, 128, 256>(q, stream) : launch_shape<MODE_CONV, 256, 128>(q, stream);
+    if (r.bj == 256 && r.bi == 256) return launch_shape<MODE_CONV, 256, 256>(q, stream);
+    return r.bi == 128 ? launch_shape<MODE_CONV, 128, 256>(q, stream) : launch_shape<MODE_CONV, 256, 128>(q, stream);
   }
   fod_set_error("gemm_tn_big: unsupported mode %d", mode);
   return FOD_ERR_ARG;

@@ -261,7 +261,7 @@ class _WgradQueue:
 
     def __init__(self):
         import os
-        self.enabled = os.environ.get("FOD_WGRAD_QUEUE", "1") != "0" and os.environ.get("FOD_TN_SMALL", "1") != "0"
+        self.enabled = os.environ.get("FOD_WGRAD_QUEUE", "1") != "0" and L.knob("FOD_TN_SMALL") != "0"
         if not hasattr(torch._C, "_current_graph_task_id"):      # (private API: how the end of a backward pass is found)
             self.enabled = False
         # the LONG weight gradients (nn.Linear layers applied to more than 512 rows: the encoder, the memory side of
@@ -589,7 +589,7 @@ class _WgradQueue:
         if long:
             for G, X, dW, cs, ldg, ldx, ldw, M, N1, K2, acc, _sc, _ss in jobs:
                 det = ops.is_deterministic()
-                ws, ws_bytes = ops.tn_workspace(torch.device("cuda", torch.cuda.current_device())) if M >= 8192 or det else (None, 0)
+                ws, ws_bytes = ops.tn_workspace(torch.device("cuda", torch.cuda.current_device())) if ops.tn_may_use_partials_ws(M) or det else (None, 0)
                 L.call("fod_gemm_tn_acc_det" if det else "fod_gemm_tn_acc", L.BF16, G, ldg, X, ldx, dW, ldw, M, N1, K2, 0, cs, 1, ws, ws_bytes, ops.stream(),
                        work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
             return

@@ -3,12 +3,13 @@
 The HIP library IS the compute path: if it is missing or its ABI disagrees, importing this
 module raises -- there is no CPU or eager-PyTorch fallback behind these calls.
 """
+import contextlib
 import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libfod_hip.so"))
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 F32, BF16 = 0, 1
 EW_ADD, EW_MUL, EW_RELU_MASK, EW_SCALE, EW_ADD3, EW_RELU, EW_COPY_B = range(7)
@@ -60,6 +61,20 @@ class TnJob(C.Structure):          # fod_tn_job (include/fod.h)
                 ("g_seg_cols", C.c_int), ("chain", C.c_int), ("g_seg_stride", C.c_long),
                 ("m_per_split", C.c_int), ("nsplit", C.c_int)]
 
+
+class NtRoute(C.Structure):        # fod_nt_route: kernel is one of NT_SMALL / NT_128 / NT_BIG
+    _fields_ = [("kernel", C.c_int), ("tile_n", C.c_int), ("stages", C.c_int), ("interleave", C.c_int),
+                ("ksplit", C.c_int), ("wants_split_ws", C.c_int)]
+
+
+class TnRoute(C.Structure):        # fod_tn_route: kernel is one of TN_SMALL / TN_128 / TN_BIG
+    _fields_ = [("kernel", C.c_int), ("bi", C.c_int), ("bj", C.c_int), ("nsplit", C.c_int), ("m_per_split", C.c_int),
+                ("xcd_order", C.c_int), ("uses_partials_ws", C.c_int)]
+
+
+NT_SMALL, NT_128, NT_BIG = range(3)           # FOD_ROUTE_NT_*
+TN_SMALL, TN_128, TN_BIG = range(3)           # FOD_ROUTE_TN_*
+CONV_FWD, CONV_DGRAD, CONV_WGRAD = range(3)   # fod_conv2d_route(which, ...)
 
 _i, _l, _f, _p = C.c_int, C.c_long, C.c_float, C.c_void_p
 # struct arguments travel as addresses (C.addressof / None): plain ints are what the fast-call wrappers take
@@ -143,6 +158,12 @@ SIGNATURES = {
     "fod_linear_add_norm_bwd_det": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, C.c_size_t, _p],
     "fod_mlp2_mul_bwd_det": [_i, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, C.c_size_t, _p],
     "fod_layernorm_bwd_det": [_i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, C.c_size_t, _p],
+    # host only: the knob table (csrc/knobs.h) and the route queries
+    "fod_knob_set": [_p, _p],
+    "fod_knob_get": [_p, _p, C.c_size_t],
+    "fod_gemm_nt_route": [_i, _l, _i, _l, _l, _i, _i, _i, _EP, _p],
+    "fod_gemm_tn_route": [_i, _i, _i, _i, _l, _l, _l, _i, _i, _i, C.c_size_t, _p],
+    "fod_conv2d_route": [_i, _i, _CG, _EP, _i, C.c_size_t, _p],
 }
 EXPORTS = sorted(list(SIGNATURES) + ["fod_last_error", "fod_abi_version", "fod_multi_chunk", "fod_workspace_bytes"])
 WS_NT_SPLIT, WS_NT_SPLIT_TICKETS, WS_TN_PARTIALS, WS_ATTN_SPLIT_PER_TILE, WS_DET, WS_TN_MULTI_DET = range(6)   # fod_workspace_bytes(kind)
@@ -181,6 +202,35 @@ def last_error():
     buf = C.create_string_buffer(512)
     LIB.fod_last_error(buf, 512)
     return buf.value.decode("utf-8", "replace")
+
+
+# ---- kernel-selection knobs (csrc/knobs.h): the library reads the FOD_* variables it looks at ONCE, at its first use;
+# afterwards os.environ does not reach it -- these do.  A captured graph keeps the kernels of its capture.
+def knob(name):
+    """The value in effect of a C-side knob, as text ("auto" where a rule decides)."""
+    buf = C.create_string_buffer(32)
+    if LIB.fod_knob_get(name.encode(), buf, 32) != 0:
+        raise FodError(f"fod_knob_get failed: {last_error()}")
+    return buf.value.decode()
+
+
+def set_knob(name, value):
+    """value None: back to the default."""
+    if LIB.fod_knob_set(name.encode(), None if value is None else str(value).encode()) != 0:
+        raise FodError(f"fod_knob_set failed: {last_error()}")
+
+
+@contextlib.contextmanager
+def knobs(**values):
+    """with knobs(FOD_TN_BIG=2, FOD_TN_WS=0): ...  -- the previous values come back on exit."""
+    old = {name: knob(name) for name in values}
+    try:
+        for name, value in values.items():
+            set_knob(name, value)
+        yield
+    finally:
+        for name, value in old.items():
+            set_knob(name, value)
 
 
 def _load_fast():

@@ -124,12 +124,24 @@ def det_workspace(device, kind=L.WS_DET):
     return ws.data_ptr(), ws.numel() * 4
 
 
+# The two places where this module must know what the library will decide, because the scratch is the caller's to hand
+# over.  tests/test_dispatch_cpu.py holds them against the library's own answer (fod_gemm_nt_route / fod_gemm_tn_route):
+# if a threshold moves in csrc/, the test fails instead of the launches silently going without scratch.
+def nt_wants_split_ws(M, N, K):
+    """A bf16 fod_gemm_nt problem the library splits along K when it is handed the scratch: deep K on few tiles."""
+    return K >= 1024 and ((M + 63) // 64) * ((N + 63) // 64) <= 64
+
+
+def tn_may_use_partials_ws(M):
+    """Only long reductions take partial tiles (fod_gemm_tn_acc / fod_conv2d_wgrad_acc with M rows to reduce over)."""
+    return M >= 8192
+
+
 def _epi(scale=None, shift=None, residual=None, ld_residual=0, residual_row_mod=0, relu_mask=None,
          ld_mask=0, relu=False, out_f32=False, split_for=None):
-    """split_for = (device, M, N, K) of a fod_gemm_nt call: attaches the split-K scratch when the problem is one the
-    library would split (deep K on few tiles, the condition of csrc/gemm_nt.hip: fod_gemm_nt)."""
-    want_split = (split_for is not None and split_for[3] >= 1024
-                  and ((split_for[1] + 63) // 64) * ((split_for[2] + 63) // 64) <= 64)
+    """split_for = (device, M, N, K) of a bf16 fod_gemm_nt call: attaches the split-K scratch when the problem is one the
+    library would split."""
+    want_split = split_for is not None and nt_wants_split_ws(*split_for[1:])
     if (scale is None and shift is None and residual is None and relu_mask is None and not relu and not out_f32
             and not want_split):
         return None
@@ -145,6 +157,41 @@ def tn_workspace(device):
     """(address, bytes) of the partial-tile workspace of the long weight gradients for the current stream."""
     ws = _workspace(L.WS_TN_PARTIALS, device)
     return ws.data_ptr(), ws.numel() * 4
+
+
+# ---- which kernel a call of the wrappers below takes: the library's own answer (host only, no GPU needed) ------------
+_THERE = 16      # stands for scratch that would be handed over: the queries read no pointer
+
+
+def gemm_nt_route(M, N, K, dtype=torch.bfloat16):
+    """L.NtRoute of gemm_nt(a [M, K], b [N, K]) under the knobs in effect.  (The epilogue's operands do not change it,
+    short of a residual or mask beyond 2 GiB.)"""
+    e, r = Epilogue(), L.NtRoute()
+    if dtype == torch.bfloat16 and nt_wants_split_ws(M, N, K):
+        e.split_ws = e.split_tickets = _THERE
+    call("fod_gemm_nt_route", _DT[dtype], K, 0, K, N, M, N, K, C.addressof(e), C.addressof(r))
+    return r
+
+
+def _tn_ws_bytes(M):
+    return L.LIB.fod_workspace_bytes(L.WS_TN_PARTIALS) if tn_may_use_partials_ws(M) or _DETERMINISTIC else 0
+
+
+def gemm_tn_route(M, N1, K2, dtype=torch.bfloat16, row_scale=False, colsum=False):
+    """L.TnRoute of gemm_tn_acc(g [M, N1], x [M, K2], dw, row_scale, colsum) under the knobs and the mode in effect."""
+    r = L.TnRoute()
+    call("fod_gemm_tn_route", _DT[dtype], M, N1, K2, N1, K2, K2, int(row_scale), int(colsum), int(_DETERMINISTIC),
+         _tn_ws_bytes(M), C.addressof(r))
+    return r
+
+
+def conv2d_route(which, geom, dtype=torch.bfloat16):
+    """Route of conv2d_fwd / conv2d_dgrad (L.CONV_FWD / L.CONV_DGRAD: an L.NtRoute; stride 2: of the first parity class)
+    or conv2d_wgrad_acc (L.CONV_WGRAD: an L.TnRoute) for `geom`."""
+    r = L.TnRoute() if which == L.CONV_WGRAD else L.NtRoute()
+    call("fod_conv2d_route", which, _DT[dtype], C.addressof(geom), None, int(_DETERMINISTIC),
+         _tn_ws_bytes(geom.Nimg * geom.Ho * geom.Wo), C.addressof(r))
+    return r
 
 
 # ------------------------------------------------------------------------------------------------ GEMM
@@ -219,7 +266,7 @@ def gemm_tn_acc(g, x, dw, row_scale=None, colsum=None, zeroed=False):
         _chk(row_scale, "row_scale", torch.float32); assert row_scale.numel() == N1
     if colsum is not None:
         _chk(colsum, "colsum", torch.float32); assert colsum.numel() == N1
-    ws, ws_bytes = tn_workspace(g.device) if M >= 8192 or _DETERMINISTIC else (None, 0)   # only long reductions take partial tiles
+    ws, ws_bytes = tn_workspace(g.device) if _tn_ws_bytes(M) else (None, 0)
     call("fod_gemm_tn_acc_det" if _DETERMINISTIC else "fod_gemm_tn_acc", dt(g), ptr(g), N1, ptr(x), K2, ptr(dw), K2, M, N1, K2, ptr(row_scale), ptr(colsum),
          0 if zeroed else 1, ws, ws_bytes, stream(),
          work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
@@ -433,7 +480,7 @@ def conv2d_wgrad_acc(dy, x, dw, geom, row_scale=None, zeroed=False):
     assert dw.numel() == geom.Cout * geom.kh * geom.kw * geom.Cin
     if row_scale is not None:
         _chk(row_scale, "row_scale", torch.float32); assert row_scale.numel() == geom.Cout
-    ws, ws_bytes = tn_workspace(dy.device) if dy.numel() // geom.Cout >= 8192 or _DETERMINISTIC else (None, 0)
+    ws, ws_bytes = tn_workspace(dy.device) if _tn_ws_bytes(dy.numel() // geom.Cout) else (None, 0)
     call("fod_conv2d_wgrad_acc_det" if _DETERMINISTIC else "fod_conv2d_wgrad_acc", dt(dy), ptr(dy), ptr(x), ptr(dw), _Addr(geom), ptr(row_scale),
          0 if zeroed else 1, ws, ws_bytes, stream(),
          work=_conv_flops(geom), tag="fod_conv2d_wgrad_acc")

@@ -45,7 +45,42 @@ enum { FOD_OK = 0, FOD_ERR_ARG = 1, FOD_ERR_LAUNCH = 2, FOD_ERR_RUNTIME = 3 };
 size_t fod_last_error(char* buf, size_t cap);
 /* ABI version of this header; the loader refuses a library that disagrees. */
 int fod_abi_version(void);
-#define FOD_ABI_VERSION 6
+#define FOD_ABI_VERSION 7
+
+/* Kernel-selection knobs: the FOD_* variables the library looks at (listed with their values and defaults in
+ * csrc/knobs.h) live in one process-wide host table that is filled from the environment ONCE, at its first use; a
+ * variable exported later is not seen.  `name` is the environment name ("FOD_TN_BIG").  fod_knob_set: value == NULL puts
+ * the default back; an unknown name or a value that does not parse returns FOD_ERR_ARG.  fod_knob_get writes the value
+ * in effect as text ("auto" where a rule decides).  Host state only, thread-safe; a captured graph keeps the kernels
+ * that were chosen when it was captured. */
+int fod_knob_set(const char* name, const char* value);
+int fod_knob_get(const char* name, char* out, size_t out_bytes);
+
+/* Which kernel a call would take under the knobs in effect.  The queries below are host-only: no stream, no device
+ * access, no pointer is read; the parts of a decision that depend on addresses are answered as for 16-byte aligned
+ * operands.  They check their arguments like the entry point they stand for. */
+enum { FOD_ROUTE_NT_SMALL = 0, /* short launch: 64 x 64 tiles, optionally K split over ksplit blocks */
+       FOD_ROUTE_NT_128 = 1,   /* 128-row tiles, register-staged ring */
+       FOD_ROUTE_NT_BIG = 2 }; /* 256-row tiles, LDS-DMA ring */
+typedef struct fod_nt_route {
+  int kernel;
+  int tile_n;          /* columns per tile: 64 | 128 | 256 */
+  int stages;          /* depth of the LDS ring (0 for the short launch) */
+  int interleave;      /* FOD_ROUTE_NT_BIG: DMA requests issued between the MFMAs */
+  int ksplit;          /* K-splits of the launch (1 = none; needs fod_epilogue.split_ws / split_tickets) */
+  int wants_split_ws;  /* the problem is one that is split when the scratch is handed over */
+} fod_nt_route;
+enum { FOD_ROUTE_TN_SMALL = 0, /* short reduction: 64 x 64 tiles, one M-split */
+       FOD_ROUTE_TN_128 = 1,   /* 128 x 128 tiles, register-staged ring */
+       FOD_ROUTE_TN_BIG = 2 }; /* 8-wave tiles, LDS-DMA ring */
+typedef struct fod_tn_route {
+  int kernel;
+  int bi, bj;             /* tile: rows (N1) x columns (K2) of dW */
+  int nsplit;             /* M-splits */
+  int m_per_split;
+  int xcd_order;          /* 1: one XCD per M-split (1-D launch) */
+  int uses_partials_ws;   /* partial results go to the caller's workspace and a second launch adds them */
+} fod_tn_route;
 
 /* Fused epilogue of the NT contraction family.  In order:
  *   v = acc * scale[n] + shift[n];  v += residual[row(m), n];  v = relu ? max(v,0) : v;
@@ -101,6 +136,10 @@ size_t fod_workspace_bytes(int kind);
 int fod_gemm_nt(int dtype, const void* A, long lda, int a_row_mod, const void* B, long ldb, void* C,
                 long ldc, int M, int N, int K, const fod_epilogue* epi, fod_stream_t stream);
 
+/* The route of fod_gemm_nt(dtype, ..., lda, a_row_mod, ..., ldb, ..., ldc, M, N, K, epi, ...). */
+int fod_gemm_nt_route(int dtype, long lda, int a_row_mod, long ldb, long ldc, int M, int N, int K,
+                      const fod_epilogue* epi, fod_nt_route* out);
+
 /* dW[i,j] += row_scale[i] * sum_m G[m,i] * X[m,j]     G:[M,N1] ldg, X:[M,K2] ldx, dW f32 [N1,K2] ldw
  * colsum (optional, f32 [N1]) += sum_m G[m,i]: the bias gradient from the same pass over G.
  * Replaces autograd's Linear weight/bias gradients (loss.backward(), future_od/trainer.py:180).
@@ -110,6 +149,9 @@ int fod_gemm_tn_acc(int dtype, const void* G, long ldg, const void* X, long ldx,
                     int M, int N1, int K2, const float* row_scale, float* colsum, int accumulate,
                     void* ws /* optional, FOD_TN_WS_BYTES: deterministic partial tiles instead of atomics */,
                     size_t ws_bytes, fod_stream_t stream);
+/* The route of fod_gemm_tn_acc (det = 0) / fod_gemm_tn_acc_det (det = 1) with a workspace of ws_bytes (0 = none). */
+int fod_gemm_tn_route(int dtype, int M, int N1, int K2, long ldg, long ldx, long ldw, int has_row_scale,
+                      int has_colsum, int det, size_t ws_bytes, fod_tn_route* out);
 
 /* Grouped forms for P same-shaped Linear layers that share their input (the decoder's query-side projections:
  * query_content / key_content / value of future_od/models/transformer.py:66-70, the per-image query_sine
@@ -244,6 +286,13 @@ int fod_conv2d_wgrad_acc(int dtype, const void* dy, const void* x, float* dw, co
                          size_t ws_bytes, fod_stream_t stream);
 int fod_conv2d_wgrad_acc_det(int dtype, const void* dy, const void* x, float* dw, const fod_conv_geom* g,
                              const float* row_scale, int accumulate, void* ws, size_t ws_bytes, fod_stream_t stream);
+/* The route of a convolution pass.  FOD_CONV_FWD / FOD_CONV_DGRAD: `out` is a fod_nt_route (epi as in the call; det and
+ * ws_bytes are not looked at; a stride-2 input gradient is one launch per input-pixel parity class and the answer is
+ * that of class (0, 0)).  FOD_CONV_WGRAD: `out` is a fod_tn_route (epi is not looked at; det, ws_bytes as for
+ * fod_gemm_tn_route). */
+enum { FOD_CONV_FWD = 0, FOD_CONV_DGRAD = 1, FOD_CONV_WGRAD = 2 };
+int fod_conv2d_route(int which, int dtype, const fod_conv_geom* g, const fod_epilogue* epi, int det, size_t ws_bytes,
+                     void* out);
 
 /* One FROZEN 64-channel bottleneck block in one launch (csrc/bottleneck_fused.hip; torchvision Bottleneck with
  * FrozenBatchNorm2d, reference paper.py:94-98, for the blocks that keep nothing for backward, paper.py:102-109):

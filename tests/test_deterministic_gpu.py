@@ -3,10 +3,11 @@ f32 atomics is summed in a fixed order instead, so gradients, parameters and Ada
 run on one GPU.  Bit equality below is torch.equal on every tensor: no tolerance, no tensor left out.
 
 Per entry point: shapes of the headline workload (10 frames x 1450 tokens, D = 256, FFN 2048; ResNet-50 at 900 x 1600),
-for which the host-side mirror of the launch geometry shows more than one contributing workgroup per output element
-(otherwise a case shows nothing); three calls on the same operands, starting from zero and from a previous value; and
+for which the launch geometry -- for the weight gradients: the route the library reports for the very call -- shows more
+than one contributing workgroup per output element (otherwise a case shows nothing); three calls on the same operands, starting from zero and from a previous value; and
 the deterministic result within the tolerance the entry's own test in test_kernels_gpu.py uses, against the default
 form.  Then whole steps: small model eager / replayed / train mode with dropout, the real extent, two fresh processes."""
+import contextlib
 import hashlib
 import math
 import os
@@ -33,6 +34,14 @@ def _mode_is_restored():
     ops.set_deterministic(prev)
 
 
+@pytest.fixture
+def knobs():
+    """knobs(FOD_X=v, ...): sets selection knobs of the library (csrc/knobs.h) for the rest of the test; the values
+    they had come back at teardown."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(L.knobs(**values))
+
+
 def _thrice(run):
     """run() -> tuple of output tensors; three calls, bit-equal."""
     outs = [tuple(t.clone() for t in run()) for _ in range(3)]
@@ -51,49 +60,13 @@ def _default(run):
     return out
 
 
-# ---- host-side mirrors of the launch geometry (csrc/gemm_tn.hip, gemm_tn_big.hip, elementwise.hip, linear_norm.hip) ----
-def _pick_splits(tiles, M):
-    if M <= 512:
-        return 1
-    s = 1024 // tiles
-    if s >= 1 and M // s >= 1536:
-        return s
-    return max(1, min(-(-384 // tiles), M // 512))
-
-
-def _tn_splits(M, N1, K2, colsum):
-    """M-splits of the 128 x 128 kernel in deterministic mode: pick_splits, capped by the scratch, XCD flooring."""
-    s = _pick_splits(-(-N1 // 128) * -(-K2 // 128), M)
-    fit = (L.LIB.fod_workspace_bytes(L.WS_TN_PARTIALS) // 4) // (N1 * K2 + (N1 if colsum else 0))
-    if s > fit:
-        s = 1 if fit < 2 else fit
-    s8 = s // 8 * 8
-    if s8 >= 8 and 10 * s8 >= 9 * s:
-        s = s8
-    mps = -(-(-(-M // s)) // 32) * 32
-    return -(-M // mps)
-
-
-def _big_applies(M, N1, K2):
-    return M >= 8192 and N1 >= 128 and K2 >= 128 and float(M) * N1 * K2 >= 2.0e9
-
-
-def _big_splits(M, N1, K2):
-    """M-splits of the 8-wave kernel for its two default tile shapes (the plan takes one of them)."""
-    out = []
-    for bi, bj in ((128, 256), (256, 128)):
-        ntile = -(-N1 // bi) * -(-K2 // bj)
-        s = max(1, min(256 // ntile, M // 256))
-        mps = -(-(-(-M // s)) // 64) * 64
-        out.append(-(-M // mps))
-    return out
-
-
 # ---- per entry point --------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 def test_gemm_tn_acc_det(dtype):
     M, N1, K2 = 14500, 2048, 256                  # the encoder's first feed-forward weight at 10 x 1450 tokens
-    assert _tn_splits(M, N1, K2, True) == 12      # 12 M-splits add into every dW / colsum element
+    ops.set_deterministic(True)
+    r = ops.gemm_tn_route(M, N1, K2, dtype, row_scale=True, colsum=True)
+    assert (r.kernel, r.nsplit, r.uses_partials_ws) == (L.TN_128, 12, 1)     # 12 M-splits add into every dW / colsum element
     g, x = rnd((M, N1), dtype, 1).to(DEV), rnd((M, K2), dtype, 2).to(DEV)
     rs = (torch.rand(N1) + 0.5).to(DEV)
     dw0, cs0 = torch.randn(N1, K2, device=DEV), torch.randn(N1, device=DEV)
@@ -110,12 +83,14 @@ def test_gemm_tn_acc_det(dtype):
         check(cs, cs_d, torch.float32, math.sqrt(M), "gemm_tn_acc_det colsum")
 
 
-def test_gemm_tn_acc_det_eight_wave_kernel(monkeypatch):
+def test_gemm_tn_acc_det_eight_wave_kernel(knobs):
     """The same entry through the 8-wave kernel (FOD_TN_BIG_DENSE=1): its fused bias gradient is added by several waves
     per workgroup and by every M-split."""
-    monkeypatch.setenv("FOD_TN_BIG_DENSE", "1")
+    knobs(FOD_TN_BIG_DENSE=1)
     M, N1, K2 = 14500, 2048, 256
-    assert _big_applies(M, N1, K2) and min(_big_splits(M, N1, K2)) > 1
+    ops.set_deterministic(True)
+    r = ops.gemm_tn_route(M, N1, K2, colsum=True)
+    assert r.kernel == L.TN_BIG and r.nsplit > 1 and r.uses_partials_ws      # takes the 8-wave kernel, several M-splits
     dtype = torch.bfloat16
     g, x = rnd((M, N1), dtype, 3).to(DEV), rnd((M, K2), dtype, 4).to(DEV)
     dw0, cs0 = torch.randn(N1, K2, device=DEV), torch.randn(N1, device=DEV)
@@ -172,6 +147,7 @@ CONVS = [   # (Nimg, H, W, Cin, Cout, k, stride, pad): ResNet-50 at 900 x 1600, 
     (10, 57, 100, 1024, 256, 1, 1, 0),     # layer3 1x1
     (2, 29, 50, 512, 512, 3, 1, 1),        # layer4 3x3 on two frames: the 128 x 128 kernel (M < 8192)
 ]
+CONV_KERNELS = ["TN_BIG", "TN_BIG", "TN_128"]
 
 
 @pytest.mark.parametrize("case", CONVS)
@@ -179,11 +155,10 @@ def test_conv2d_wgrad_acc_det(case):
     n, h, w_, cin, cout, k, stride, pad = case
     dtype = torch.bfloat16
     geom = ops.conv_geom((n, h, w_, cin), cout, k, stride, pad)
-    M, K2 = n * geom.Ho * geom.Wo, k * k * cin
-    if _big_applies(M, cout, K2):
-        assert min(_big_splits(M, cout, K2)) > 1
-    else:
-        assert _tn_splits(M, cout, K2, False) > 1
+    M = n * geom.Ho * geom.Wo
+    ops.set_deterministic(True)
+    r = ops.conv2d_route(L.CONV_WGRAD, geom)
+    assert r.kernel == getattr(L, CONV_KERNELS[CONVS.index(case)]) and r.nsplit > 1 and r.uses_partials_ws
     x = rnd((n, h, w_, cin), dtype, 1).to(DEV)
     dy = rnd((n, geom.Ho, geom.Wo, cout), dtype, 4).to(DEV)
     rs = (torch.rand(cout) + 0.5).to(DEV)

@@ -6,6 +6,7 @@ Tolerances (stated per dtype, checked as max|a-b| <= atol + rtol*|b| ):
   bf16 mode: inputs rounded to bf16 (the reference is computed from the SAME rounded inputs in
              fp32), output rounded to bf16                               -> rtol 1.6e-2 (2 bf16 ulp)
 """
+import contextlib
 import math
 
 import numpy as np
@@ -21,6 +22,14 @@ if torch.cuda.is_available():
 
 DEV = "cuda:0"
 DTYPES = [torch.float32, torch.bfloat16]
+
+
+@pytest.fixture
+def knobs():
+    """knobs(FOD_X=v, ...): sets selection knobs of the library (csrc/knobs.h) for the rest of the test; the values
+    they had come back at teardown.  (The library reads the environment once: setting a variable here would do nothing.)"""
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(L.knobs(**values))
 
 
 def tol(dtype, scale=1.0):
@@ -865,6 +874,18 @@ def test_group_linear_kernels(shape):
 
 # The 256 x 128 LDS-DMA kernel (gemm_nt_big.hip) normally takes only large problems; FOD_NT_BIG=2 routes every legal
 # problem through it so that ragged tiles, every conv mode and every epilogue variant are checked on small shapes.
+# Legal, for the conv modes: a 64-deep k-tile never straddles two taps, i.e. the channel count of the tensor the taps
+# are gathered from (forward: Cin, input gradient: Cout) is a multiple of 64 -- the other passes of these cases stay on
+# the 128-row kernel, and every test below asserts which of the two the library reports for the call that follows.
+def _nt_conv_route(which, geom):
+    r = ops.conv2d_route(which, geom)
+    return r.kernel, r.tile_n if r.kernel == L.NT_BIG else None
+
+
+def _nt_big_or_128(gathered_channels, tile_n):
+    return (L.NT_BIG, tile_n) if gathered_channels % 64 == 0 else (L.NT_128, None)
+
+
 BIG_CONV_CASES = [  # (Nimg, H, W, Cin, Cout, k, stride, pad)
     (2, 15, 20, 64, 64, 3, 1, 1),
     (1, 15, 21, 64, 128, 3, 2, 1),
@@ -875,8 +896,8 @@ BIG_CONV_CASES = [  # (Nimg, H, W, Cin, Cout, k, stride, pad)
 
 
 @pytest.mark.parametrize("case", BIG_CONV_CASES)
-def test_big_tile_kernel_conv_modes(monkeypatch, case):
-    monkeypatch.setenv("FOD_NT_BIG", "2")
+def test_big_tile_kernel_conv_modes(knobs, case):
+    knobs(FOD_NT_BIG=2)
     dtype = torch.bfloat16
     n, h, w_, cin, cout, k, stride, pad = case
     x = rnd((n, h, w_, cin), dtype, 1)
@@ -888,19 +909,21 @@ def test_big_tile_kernel_conv_modes(monkeypatch, case):
     y_lin = _conv_ref(x32, w32, stride, pad)
     res = rnd((n, geom.Ho, geom.Wo, cout), dtype, 3)
     y_ref = (y_lin * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1) + res.float().permute(0, 3, 1, 2)).clamp(min=0)
+    assert _nt_conv_route(L.CONV_FWD, geom) == _nt_big_or_128(cin, 128)
     y = ops.conv2d_fwd(x.to(DEV), w.to(DEV), geom, scale=scale.to(DEV), shift=shift.to(DEV), residual=res.to(DEV),
                        relu=True)
     check(y, y_ref.permute(0, 2, 3, 1), dtype, 2, f"big conv fwd {case}")
-    monkeypatch.setenv("FOD_NT_BIG", "0")
-    y_small = ops.conv2d_fwd(x.to(DEV), w.to(DEV), geom, scale=scale.to(DEV), shift=shift.to(DEV),
-                             residual=res.to(DEV), relu=True)
-    monkeypatch.setenv("FOD_NT_BIG", "2")
+    with L.knobs(FOD_NT_BIG=0):
+        assert _nt_conv_route(L.CONV_FWD, geom)[0] == L.NT_128
+        y_small = ops.conv2d_fwd(x.to(DEV), w.to(DEV), geom, scale=scale.to(DEV), shift=shift.to(DEV),
+                                 residual=res.to(DEV), relu=True)
     assert torch.equal(y, y_small), "both tilings accumulate k in the same order: identical results expected"
     dy = rnd((n, geom.Ho, geom.Wo, cout), dtype, 4)
     y_lin.backward(dy.float().permute(0, 3, 1, 2))
     w_t = w.permute(3, 1, 2, 0).contiguous()
     dres = rnd((n, h, w_, cin), dtype, 5)
     mask = rnd((n, h, w_, cin), dtype, 6)
+    assert _nt_conv_route(L.CONV_DGRAD, geom) == _nt_big_or_128(cout, 128)
     dx = ops.conv2d_dgrad(dy.to(DEV), w_t.to(DEV), geom, residual=dres.to(DEV), relu_mask=mask.to(DEV))
     dx_ref = torch.where(mask.float() > 0, x32.grad + dres.float(), torch.zeros(()))
     check(dx, dx_ref, dtype, 4, f"big conv dgrad {case}")
@@ -916,11 +939,10 @@ BIG256_CONV_CASES = [  # (Nimg, H, W, Cin, Cout, k, stride, pad): Cout and / or 
 
 
 @pytest.mark.parametrize("case", BIG256_CONV_CASES)
-def test_big_square_tile_kernel_conv_modes(monkeypatch, case):
+def test_big_square_tile_kernel_conv_modes(knobs, case):
     """The 256 x 256 tile of gemm_nt_big.hip (two-stage ring, epilogue in two row halves; FOD_NT_BIG256) on small shapes:
     every conv mode with ragged tiles in both directions, full epilogue; bit-equal to the 128-row kernel (same k order)."""
-    monkeypatch.setenv("FOD_NT_BIG", "2")
-    monkeypatch.setenv("FOD_NT_BIG256", "2")
+    knobs(FOD_NT_BIG=2, FOD_NT_BIG256=2)
     dtype = torch.bfloat16
     n, h, w_, cin, cout, k, stride, pad = case
     x = rnd((n, h, w_, cin), dtype, 1)
@@ -933,32 +955,35 @@ def test_big_square_tile_kernel_conv_modes(monkeypatch, case):
     res = rnd((n, geom.Ho, geom.Wo, cout), dtype, 3)
     y_ref = (y_lin * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1) + res.float().permute(0, 3, 1, 2)).clamp(min=0)
     args = dict(scale=scale.to(DEV), shift=shift.to(DEV), residual=res.to(DEV), relu=True)
+    assert _nt_conv_route(L.CONV_FWD, geom) == _nt_big_or_128(cin, 256 if cout >= 256 else 128)
     y = ops.conv2d_fwd(x.to(DEV), w.to(DEV), geom, **args)
     check(y, y_ref.permute(0, 2, 3, 1), dtype, 2, f"big256 conv fwd {case}")
-    monkeypatch.setenv("FOD_NT_BIG", "0")
-    y_small = ops.conv2d_fwd(x.to(DEV), w.to(DEV), geom, **args)
-    monkeypatch.setenv("FOD_NT_BIG", "2")
+    with L.knobs(FOD_NT_BIG=0):
+        assert _nt_conv_route(L.CONV_FWD, geom)[0] == L.NT_128
+        y_small = ops.conv2d_fwd(x.to(DEV), w.to(DEV), geom, **args)
     assert torch.equal(y, y_small), float((y.float() - y_small.float()).abs().max())
     dy = rnd((n, geom.Ho, geom.Wo, cout), dtype, 4)
     y_lin.backward(dy.float().permute(0, 3, 1, 2))
     w_t = w.permute(3, 1, 2, 0).contiguous()
     dres = rnd((n, h, w_, cin), dtype, 5)
     mask = rnd((n, h, w_, cin), dtype, 6)
+    assert _nt_conv_route(L.CONV_DGRAD, geom) == _nt_big_or_128(cout, 256 if cin >= 256 else 128)
     dx = ops.conv2d_dgrad(dy.to(DEV), w_t.to(DEV), geom, residual=dres.to(DEV), relu_mask=mask.to(DEV))
     dx_ref = torch.where(mask.float() > 0, x32.grad + dres.float(), torch.zeros(()))
     check(dx, dx_ref, dtype, 4, f"big256 conv dgrad {case}")
-    monkeypatch.setenv("FOD_NT_BIG", "0")
+    knobs(FOD_NT_BIG=0)
+    assert _nt_conv_route(L.CONV_DGRAD, geom)[0] == L.NT_128
     dx_small = ops.conv2d_dgrad(dy.to(DEV), w_t.to(DEV), geom, residual=dres.to(DEV), relu_mask=mask.to(DEV))
     assert torch.equal(dx, dx_small), float((dx.float() - dx_small.float()).abs().max())
 
 
 @pytest.mark.parametrize("mnk", [(300, 256, 128), (1000, 264, 72), (257, 512, 256), (4097, 260, 64), (515, 768, 1536)])
-def test_big_square_tile_kernel_dense(monkeypatch, mnk):
-    monkeypatch.setenv("FOD_NT_BIG", "2")
-    monkeypatch.setenv("FOD_NT_BIG256", "2")
-    monkeypatch.setenv("FOD_NT_SMALL", "0")
+def test_big_square_tile_kernel_dense(knobs, mnk):
+    knobs(FOD_NT_BIG=2, FOD_NT_BIG256=2, FOD_NT_SMALL=0)
     dtype = torch.bfloat16
     M, N, K = mnk
+    r = ops.gemm_nt_route(M, N, K)                 # of both calls below: the epilogue does not change it
+    assert (r.kernel, r.tile_n, r.stages) == (L.NT_BIG, 256, 2)
     a, b = rnd((M, K), dtype, 1), rnd((N, K), dtype, 2)
     shift = torch.randn(N)
     res = rnd((50, N), dtype, 3)
@@ -973,11 +998,12 @@ def test_big_square_tile_kernel_dense(monkeypatch, mnk):
 
 
 @pytest.mark.parametrize("mnk", [(300, 128, 128), (1000, 40, 72), (257, 132, 256), (513, 64, 96), (4097, 8, 64)])
-def test_big_tile_kernel_dense(monkeypatch, mnk):
-    monkeypatch.setenv("FOD_NT_BIG", "2")
-    monkeypatch.setenv("FOD_NT_SMALL", "0")
+def test_big_tile_kernel_dense(knobs, mnk):
+    knobs(FOD_NT_BIG=2, FOD_NT_SMALL=0)
     dtype = torch.bfloat16
     M, N, K = mnk
+    r = ops.gemm_nt_route(M, N, K)                 # of both calls below: the epilogue does not change it
+    assert (r.kernel, r.tile_n, r.stages) == (L.NT_BIG, 128, 3)
     a, b = rnd((M, K), dtype, 1), rnd((N, K), dtype, 2)
     shift = torch.randn(N)
     res = rnd((50, N), dtype, 3)
@@ -1024,14 +1050,27 @@ def test_same_padded_dilated_conv_with_gradients(dtype, case):
 # The 8-wave LDS-DMA weight-gradient kernel (gemm_tn_big.hip) normally takes only long reductions; FOD_TN_BIG=2 routes
 # every legal bf16 problem through it: ragged tiles in both tile shapes, M-splits (plain and XCD-grouped order), the
 # conv gather with stride / padding / image wrap inside a stage, row scales, accumulation into a non-zero buffer.
+def _forced_splits(M, splits):
+    """FOD_TN_BIG_SPLITS=n: n M-splits of whole 64-row stages -- fewer where M does not reach that far."""
+    rows = -(-(-(-M // splits)) // 64) * 64
+    return -(-M // rows)
+
+
+def _tn_big_route(r, M, splits, square):
+    """The route names the 8-wave kernel, the tile family the test is about and the forced number of M-splits."""
+    assert r.kernel == L.TN_BIG, r.kernel
+    assert ((r.bi, r.bj) == (256, 256)) if square else ((r.bi, r.bj) in ((128, 256), (256, 128))), (r.bi, r.bj)
+    if splits:
+        assert r.nsplit == _forced_splits(M, splits), (r.nsplit, splits)
+    # the wrappers hand the workspace over from 8192 rows on: partial tiles there, atomics below
+    assert bool(r.uses_partials_ws) == (M >= 8192 and r.nsplit > 1)
+
+
 @pytest.mark.parametrize("splits", [0, 3, 8])
 @pytest.mark.parametrize("mnk", [(1000, 40, 72), (4097, 8, 64), (777, 264, 136), (3000, 384, 520), (130, 256, 128),
                                  (64, 128, 256), (2111, 512, 128)])
-def test_tn_big_kernel_dense(monkeypatch, mnk, splits):
-    monkeypatch.setenv("FOD_TN_BIG", "2")
-    monkeypatch.setenv("FOD_TN_SMALL", "0")
-    if splits:
-        monkeypatch.setenv("FOD_TN_BIG_SPLITS", str(splits))
+def test_tn_big_kernel_dense(knobs, mnk, splits):
+    knobs(FOD_TN_BIG=2, FOD_TN_SMALL=0, FOD_TN_BIG_SPLITS=splits)
     dtype = torch.bfloat16
     M, N1, K2 = mnk
     g, x = rnd((M, N1), dtype, 1), rnd((M, K2), dtype, 2)
@@ -1039,9 +1078,11 @@ def test_tn_big_kernel_dense(monkeypatch, mnk, splits):
     dw0 = torch.randn(N1, K2)
     ref = dw0 + (g.float().t() @ x.float()) * rs[:, None]
     dw = dw0.clone().to(DEV)
+    _tn_big_route(ops.gemm_tn_route(M, N1, K2, row_scale=True), M, splits, square=False)
     ops.gemm_tn_acc(g.to(DEV), x.to(DEV), dw, row_scale=rs.to(DEV))
     check(dw, ref, dtype, math.sqrt(M), f"tn big {mnk}")
     dw2, cs = torch.zeros(N1, K2, device=DEV), torch.zeros(N1, device=DEV)
+    _tn_big_route(ops.gemm_tn_route(M, N1, K2, colsum=True), M, splits, square=False)
     ops.gemm_tn_acc(g.to(DEV), x.to(DEV), dw2, colsum=cs, zeroed=True)
     check(dw2, g.float().t() @ x.float(), dtype, math.sqrt(M), f"tn big {mnk} zeroed")
     check(cs, g.float().sum(0), torch.float32, math.sqrt(M), "tn big colsum")
@@ -1050,15 +1091,11 @@ def test_tn_big_kernel_dense(monkeypatch, mnk, splits):
 @pytest.mark.parametrize("splits", [0, 3, 8])
 @pytest.mark.parametrize("mnk", [(777, 264, 296), (3000, 384, 520), (130, 256, 256), (64, 512, 256), (2111, 256, 768),
                                  (9000, 520, 264)])
-def test_tn_big_square_tile_dense(monkeypatch, mnk, splits):
+def test_tn_big_square_tile_dense(knobs, mnk, splits):
     """The 256 x 256 tile of gemm_tn_big.hip (two-stage ring, 8 DMA pieces per wave and stage; FOD_TN_BIG256=2 takes it
     whenever both output dimensions are >= 256): ragged tiles, M-splits with partial tiles and with atomics (gemm_tn_acc
     hands the workspace over from 8192 rows on), row scales, accumulation, the fused column sums."""
-    monkeypatch.setenv("FOD_TN_BIG", "2")
-    monkeypatch.setenv("FOD_TN_BIG256", "2")
-    monkeypatch.setenv("FOD_TN_SMALL", "0")
-    if splits:
-        monkeypatch.setenv("FOD_TN_BIG_SPLITS", str(splits))
+    knobs(FOD_TN_BIG=2, FOD_TN_BIG256=2, FOD_TN_SMALL=0, FOD_TN_BIG_SPLITS=splits)
     dtype = torch.bfloat16
     M, N1, K2 = mnk
     g, x = rnd((M, N1), dtype, 1), rnd((M, K2), dtype, 2)
@@ -1066,9 +1103,11 @@ def test_tn_big_square_tile_dense(monkeypatch, mnk, splits):
     dw0 = torch.randn(N1, K2)
     ref = dw0 + (g.float().t() @ x.float()) * rs[:, None]
     dw = dw0.clone().to(DEV)
+    _tn_big_route(ops.gemm_tn_route(M, N1, K2, row_scale=True), M, splits, square=True)
     ops.gemm_tn_acc(g.to(DEV), x.to(DEV), dw, row_scale=rs.to(DEV))
     check(dw, ref, dtype, math.sqrt(M), f"tn big square {mnk}")
     dw2, cs = torch.zeros(N1, K2, device=DEV), torch.zeros(N1, device=DEV)
+    _tn_big_route(ops.gemm_tn_route(M, N1, K2, colsum=True), M, splits, square=True)
     ops.gemm_tn_acc(g.to(DEV), x.to(DEV), dw2, colsum=cs, zeroed=True)
     check(dw2, g.float().t() @ x.float(), dtype, math.sqrt(M), f"tn big square {mnk} zeroed")
     check(cs, g.float().sum(0), torch.float32, math.sqrt(M), "tn big square colsum")
@@ -1080,7 +1119,7 @@ TN_BIG_SQUARE_CONV_CASES = [(2, 57, 100, 256, 256, 3, 1, 1), (2, 9, 12, 256, 512
 
 @pytest.mark.parametrize("splits", [0, 5])
 @pytest.mark.parametrize("case", TN_BIG_SQUARE_CONV_CASES)
-def test_tn_big_square_tile_conv(monkeypatch, case, splits):
+def test_tn_big_square_tile_conv(knobs, case, splits):
     dtype = torch.bfloat16
     n, h, w_, cin, cout, k, stride, pad = case
     x = rnd((n, h, w_, cin), dtype, 1)
@@ -1091,15 +1130,14 @@ def test_tn_big_square_tile_conv(monkeypatch, case, splits):
     F.conv2d(x32, w32, None, stride, pad).backward(dy.float().permute(0, 3, 1, 2))
     rs = torch.rand(cout) + 0.5
     ref = (w32.grad * rs.view(-1, 1, 1, 1)).permute(0, 2, 3, 1)
-    monkeypatch.setenv("FOD_TN_BIG", "2")
-    monkeypatch.setenv("FOD_TN_BIG256", "2")
-    if splits:
-        monkeypatch.setenv("FOD_TN_BIG_SPLITS", str(splits))
+    knobs(FOD_TN_BIG=2, FOD_TN_BIG256=2, FOD_TN_BIG_SPLITS=splits)
     dw = torch.zeros((cout, k, k, cin), device=DEV)
+    _tn_big_route(ops.conv2d_route(L.CONV_WGRAD, geom), n * geom.Ho * geom.Wo, splits, square=True)
     ops.conv2d_wgrad_acc(dy.to(DEV), x.to(DEV), dw, geom, row_scale=rs.to(DEV))
     check(dw, ref, dtype, math.sqrt(n * geom.Ho * geom.Wo), f"tn big square conv wgrad {case}")
-    monkeypatch.setenv("FOD_TN_BIG256", "0")
+    knobs(FOD_TN_BIG256=0)
     dw_rect = torch.zeros((cout, k, k, cin), device=DEV)
+    _tn_big_route(ops.conv2d_route(L.CONV_WGRAD, geom), n * geom.Ho * geom.Wo, splits, square=False)
     ops.conv2d_wgrad_acc(dy.to(DEV), x.to(DEV), dw_rect, geom, row_scale=rs.to(DEV))
     check(dw, dw_rect, torch.float32, math.sqrt(n * geom.Ho * geom.Wo) * 8, "square vs 128 x 256 tile (f32 summation order only)")
 
@@ -1110,7 +1148,7 @@ TN_BIG_CONV_CASES = BIG_CONV_CASES + [(2, 17, 23, 8, 64, 7, 2, 3), (1, 29, 50, 3
 
 @pytest.mark.parametrize("splits", [0, 5])
 @pytest.mark.parametrize("case", TN_BIG_CONV_CASES)
-def test_tn_big_kernel_conv(monkeypatch, case, splits):
+def test_tn_big_kernel_conv(knobs, case, splits):
     dtype = torch.bfloat16
     n, h, w_, cin, cout, k, stride, pad = case
     x = rnd((n, h, w_, cin), dtype, 1)
@@ -1121,14 +1159,14 @@ def test_tn_big_kernel_conv(monkeypatch, case, splits):
     F.conv2d(x32, w32, None, stride, pad).backward(dy.float().permute(0, 3, 1, 2))
     rs = torch.rand(cout) + 0.5
     ref = (w32.grad * rs.view(-1, 1, 1, 1)).permute(0, 2, 3, 1)
-    monkeypatch.setenv("FOD_TN_BIG", "2")
-    if splits:
-        monkeypatch.setenv("FOD_TN_BIG_SPLITS", str(splits))
+    knobs(FOD_TN_BIG=2, FOD_TN_BIG_SPLITS=splits)
     dw = torch.zeros((cout, k, k, cin), device=DEV)
+    _tn_big_route(ops.conv2d_route(L.CONV_WGRAD, geom), n * geom.Ho * geom.Wo, splits, square=False)
     ops.conv2d_wgrad_acc(dy.to(DEV), x.to(DEV), dw, geom, row_scale=rs.to(DEV))
     check(dw, ref, dtype, math.sqrt(n * geom.Ho * geom.Wo), f"tn big conv wgrad {case}")
-    monkeypatch.setenv("FOD_TN_BIG", "0")
+    knobs(FOD_TN_BIG=0)
     dw_small = torch.zeros((cout, k, k, cin), device=DEV)
+    assert ops.conv2d_route(L.CONV_WGRAD, geom).kernel == L.TN_128
     ops.conv2d_wgrad_acc(dy.to(DEV), x.to(DEV), dw_small, geom, row_scale=rs.to(DEV))
     check(dw, dw_small, torch.float32, math.sqrt(n * geom.Ho * geom.Wo) * 8, "tn big vs 128 x 128 kernel (f32 summation order only)")
 
@@ -1360,14 +1398,14 @@ print("TWO_THREADS_OK")
     (64, (2, 3, 5), "4"), (256, (3, 1, 1), "4"), (256, (1, 2, 33), "4"), (64, (1, 13, 2), "4"),
     # the non-persistent kernel that stays as the path for inputs of 4 GiB and more (64-bit addressing)
     (64, (2, 23, 41), "2"), (256, (3, 13, 64), "2")])
-def test_fused_frozen_bottleneck_matches_the_layer_by_layer_path(cin, shape, version, monkeypatch):
+def test_fused_frozen_bottleneck_matches_the_layer_by_layer_path(cin, shape, version, knobs):
     """fod_bottleneck_fused_fwd (one launch per frozen 64-channel bottleneck block) against the
     same block as three (four) fod_conv2d_fwd launches and against fp32 torch: ragged tiles (6 x 30 output tiles, 8 x 32
     halos), image borders (the 3x3's zero padding applies to conv1's OUTPUT), identity and projection shortcuts.
     Both HIP paths round the two 64-channel intermediates to bf16 at the same points; the projection shortcut is
     rounded once more on the layer-by-layer path (it is a tensor there), hence 'within bf16 tolerance', not bit-equal."""
     from future_od.native import backbone as BB
-    monkeypatch.setenv("FOD_BNK_VERSION", version)                  # read by the entry point at every call
+    knobs(FOD_BNK_VERSION=version)
     torch.manual_seed(5)
     n, h, w = shape
     blk = BB._Block("bottleneck", cin, 64, 1, 4).to(DEV)

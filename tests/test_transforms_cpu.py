@@ -346,6 +346,6 @@ def test_clip_crop_resize_has_no_cpu_fallback():
     with pytest.raises(L.FodError):
         ops.clip_crop_resize(torch.zeros(1, 1, 3, 8, 8, dtype=torch.uint8), torch.zeros(1, 5, dtype=torch.int32), (4, 4),
                              torch.zeros(3), torch.ones(3))
-    assert "fod_clip_crop_resize" in L.FAST and L.ABI_VERSION == 6
+    assert "fod_clip_crop_resize" in L.FAST and L.ABI_VERSION >= 6          # the entry point came with ABI 6
     rc = L.LIB.fod_clip_crop_resize(None, None, 1, 1, 3, 8, 8, 4, 4, 192, 192, None, None, None, None)
     assert rc != 0 and "null" in L.last_error()
