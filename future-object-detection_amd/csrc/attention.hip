@@ -1489,35 +1489,64 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_pf_multi_kernel(const AttnPa
   attn_bwd_dkv_pf_body<PARTS, false>(p, blockIdx.x, blockIdx.y, b);
 }
 
-template <typename T, int PARTS, bool DROP>
-int launch_all(int which, const AttnParams& p, hipStream_t stream) {
-  const dim3 block(256);
+// Which kernels a call takes: decided by route() from the checked extents, whether dropout is on, whether the caller
+// handed the key-split scratch over, and a snapshot of the knob table (knobs.h).  Pure host code; launch_all() launches
+// exactly what it names, fill() takes ksplit / kchunk from it, and fod_attn_route reports it.
+typedef fod_attn_kernels AttnRoute;
+AttnRoute route(int dtype, int B, int H, int Tq, int S, bool drop, bool scratch, const Knobs& kn) {
+  AttnRoute r{};
   // few queries: spend the block's four waves on the key dimension instead (see attn_fwd_kernel)
-  const bool split = p.Tq <= 512 && p.S >= 128;
-  const Knobs kn = fod_knobs();
+  const bool split = Tq <= 512 && S >= 128;
+  // the three LDS kernels go together: they share the score arithmetic
+  const bool lds = dtype == FOD_BF16 && !drop && !split && kn.attn_lds != 0;
+  r.fwd = r.dq = lds ? FOD_ATTN_LDS : FOD_ATTN_PLAIN;
+  r.dkv = lds ? FOD_ATTN_LDS : dtype == FOD_BF16 && kn.attn_pf != 0 ? FOD_ATTN_PREFETCH : FOD_ATTN_PLAIN;
+  r.fwd_waves = lds && kn.attn_lds != 4 ? 8 : 4;
+  r.key_split = split;
+  // Key split across blocks for the few-query launches (the decoder's 128 queries: 64 blocks of 4 waves on 256 CUs,
+  // one wave per SIMD walking 12 tiles -- a quarter of the chip's vector units busy, 14 us).  With the caller's
+  // workspace: as many splits as fill the chip, each at least 128 keys (one tile per wave), at most 8.
+  r.ksplit = 1;
+  r.kchunk = S;
+  if (scratch && Tq <= 512 && S >= 256) {
+    const long tiles = (long)ceil_div(Tq, 32) * H * B;
+    int ks = (int)(256 / (tiles > 0 ? tiles : 1));
+    ks = ks > 8 ? 8 : ks;
+    ks = ks > S / 128 ? S / 128 : ks;
+    if (ks > 1) {
+      r.kchunk = ceil_div(ceil_div(S, ks), 128) * 128;
+      r.ksplit = ceil_div(S, r.kchunk);
+    }
+  }
+  return r;
+}
+
+template <typename T, int PARTS, bool DROP>
+int launch_all(int which, const AttnParams& p, const AttnRoute& r, hipStream_t stream) {
+  const dim3 block(256);
+  // (the LDS kernels exist for bf16 without dropout, the prefetching one for bf16: route() names them only there)
   if (which == 0) {
-    if (sizeof(T) == 2 && !DROP && !split && kn.attn_lds != 0) {
-      if (kn.attn_lds == 4)
+    if (r.fwd == FOD_ATTN_LDS) {
+      if (r.fwd_waves == 4)
         hipLaunchKernelGGL((attn_fwd_lds_kernel<PARTS, 4>), dim3(ceil_div(p.Tq, 128), p.H, p.B), dim3(256), 0, stream, p);
       else
         hipLaunchKernelGGL((attn_fwd_lds_kernel<PARTS, 8>), dim3(ceil_div(p.Tq, 256), p.H, p.B), dim3(512), 0, stream, p);
-    } else if (split)
+    } else if (r.key_split)
       hipLaunchKernelGGL((attn_fwd_kernel<T, PARTS, true, DROP>), dim3(ceil_div(p.Tq, 32) * p.ksplit, p.H, p.B), block, 0, stream, p);
     else
       hipLaunchKernelGGL((attn_fwd_kernel<T, PARTS, false, DROP>), dim3(ceil_div(p.Tq, 128), p.H, p.B), block, 0, stream, p);
   } else if (which == 1) {
-    if (sizeof(T) == 2 && !DROP && !split && kn.attn_lds != 0)
+    if (r.dq == FOD_ATTN_LDS)
       hipLaunchKernelGGL((attn_bwd_dq_lds_kernel<PARTS, 4>), dim3(ceil_div(p.Tq, 128), p.H, p.B), dim3(256), 0, stream, p);
-    else if (split)
+    else if (r.key_split)
       hipLaunchKernelGGL((attn_bwd_dq_kernel<T, PARTS, true, DROP>), dim3(ceil_div(p.Tq, 32) * p.ksplit, p.H, p.B), block, 0, stream, p);
     else
       hipLaunchKernelGGL((attn_bwd_dq_kernel<T, PARTS, false, DROP>), dim3(ceil_div(p.Tq, 128), p.H, p.B), block, 0, stream, p);
   } else {
     const dim3 grid(ceil_div(p.S, 128), p.H, p.B);
-    // the three LDS kernels go together (same predicate as the forward and dq passes): they share the score arithmetic
-    if (sizeof(T) == 2 && !DROP && !split && kn.attn_lds != 0)
+    if (r.dkv == FOD_ATTN_LDS)
       hipLaunchKernelGGL((attn_bwd_dkv_lds_kernel<PARTS, 4>), grid, block, 0, stream, p);
-    else if (sizeof(T) == 2 && kn.attn_pf != 0)
+    else if (r.dkv == FOD_ATTN_PREFETCH)
       hipLaunchKernelGGL((attn_bwd_dkv_pf_kernel<PARTS, DROP>), grid, block, 0, stream, p);
     else
       hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, PARTS, DROP>), grid, block, 0, stream, p);
@@ -1527,19 +1556,19 @@ int launch_all(int which, const AttnParams& p, hipStream_t stream) {
 }
 
 template <typename T, int PARTS>
-int launch_parts(int which, const AttnParams& p, hipStream_t stream) {
+int launch_parts(int which, const AttnParams& p, const AttnRoute& r, hipStream_t stream) {
   // dropout on the probabilities (train mode) is a compile-time variant: the plain kernels carry none of its code
-  return p.drop_threshold ? launch_all<T, PARTS, true>(which, p, stream) : launch_all<T, PARTS, false>(which, p, stream);
+  return p.drop_threshold ? launch_all<T, PARTS, true>(which, p, r, stream) : launch_all<T, PARTS, false>(which, p, r, stream);
 }
 
-int dispatch(int dtype, int parts, int which, const AttnParams& p, hipStream_t stream) {
-  if (dtype == FOD_BF16) return parts == 2 ? launch_parts<__bf16, 2>(which, p, stream) : launch_parts<__bf16, 1>(which, p, stream);
-  if (dtype == FOD_F32) return parts == 2 ? launch_parts<float, 2>(which, p, stream) : launch_parts<float, 1>(which, p, stream);
-  fod_set_error("attention: bad dtype %d", dtype);
-  return FOD_ERR_ARG;
+int dispatch(int dtype, int parts, int which, const AttnParams& p, const AttnRoute& r, hipStream_t stream) {
+  if (dtype == FOD_BF16) return parts == 2 ? launch_parts<__bf16, 2>(which, p, r, stream) : launch_parts<__bf16, 1>(which, p, r, stream);
+  return parts == 2 ? launch_parts<float, 2>(which, p, r, stream) : launch_parts<float, 1>(which, p, r, stream);
 }
 
-int fill(AttnParams& p, const fod_attn_shape* s) {
+// Checks the shape and fills the launch parameters and the route of a call.  No pointer of the shape is read.
+int fill(AttnParams& p, AttnRoute& r, int dtype, const fod_attn_shape* s) {
+  FOD_REQUIRE(dtype == FOD_BF16 || dtype == FOD_F32, "attention: bad dtype %d", dtype);
   FOD_REQUIRE(s, "attention: null shape");
   FOD_REQUIRE(s->B > 0 && s->H > 0 && s->Tq > 0 && s->S > 0, "attention: empty shape");
   FOD_REQUIRE(s->B <= 65535 && s->H <= 65535, "attention: grid too large");
@@ -1562,23 +1591,11 @@ int fill(AttnParams& p, const fod_attn_shape* s) {
   p.drop_seed_lo = (unsigned)(s->drop_seed & 0xFFFFFFFFu);
   p.drop_seed_hi = (unsigned)(s->drop_seed >> 32);
   p.drop_seed_dev = s->drop_seed_dev;
-  // Key split across blocks for the few-query launches (the decoder's 128 queries: 64 blocks of 4 waves on 256 CUs,
-  // one wave per SIMD walking 12 tiles -- a quarter of the chip's vector units busy, 14 us).  With the caller's
-  // workspace: as many splits as fill the chip, each at least 128 keys (one tile per wave), at most 8.
-  p.ksplit = 1;
-  p.kchunk = p.S;
   p.split_ws = reinterpret_cast<float*>(s->split_ws);
   p.split_tickets = reinterpret_cast<unsigned*>(s->split_tickets);
-  if (s->split_ws && s->split_tickets && p.Tq <= 512 && p.S >= 256) {
-    const long tiles = (long)ceil_div(p.Tq, 32) * p.H * p.B;
-    int ks = (int)(256 / (tiles > 0 ? tiles : 1));
-    ks = ks > 8 ? 8 : ks;
-    ks = ks > p.S / 128 ? p.S / 128 : ks;
-    if (ks > 1) {
-      p.kchunk = ceil_div(ceil_div(p.S, ks), 128) * 128;
-      p.ksplit = ceil_div(p.S, p.kchunk);
-    }
-  }
+  r = route(dtype, p.B, p.H, p.Tq, p.S, p.drop_threshold != 0, s->split_ws && s->split_tickets, fod_knobs());
+  p.ksplit = r.ksplit;
+  p.kchunk = r.kchunk;
   FOD_REQUIRE(p.drop_threshold == 0 || (long)s->Tq * s->S < (1L << 32), "attention: Tq * S too large for dropout indexing");
   FOD_REQUIRE(p.q_ts % 8 == 0 && p.k_ts % 8 == 0 && p.v_ts % 8 == 0 && p.o_ts % 8 == 0 && p.q_bs % 8 == 0 &&
                   p.k_bs % 8 == 0 && p.v_bs % 8 == 0 && p.o_bs % 8 == 0 && p.k2_bs % 8 == 0 && p.k2_ts % 8 == 0 &&
@@ -1589,30 +1606,38 @@ int fill(AttnParams& p, const fod_attn_shape* s) {
 
 }  // namespace
 
+extern "C" int fod_attn_route(int dtype, int parts, const fod_attn_shape* shape, fod_attn_kernels* out) {
+  FOD_REQUIRE(out && (dtype == FOD_BF16 || dtype == FOD_F32) && (parts == 1 || parts == 2), "attn_route: bad args");
+  AttnParams p{};
+  return fill(p, *out, dtype, shape);
+}
+
 extern "C" int fod_attn_fwd(int dtype, const void* q1, const void* k1, const void* q2, const void* k2,
                             const void* v, void* o, float* lse2, const fod_attn_shape* shape,
                             hipStream_t stream) {
   AttnParams p{};
-  int rc = fill(p, shape);
+  AttnRoute r{};
+  int rc = fill(p, r, dtype, shape);
   if (rc) return rc;
   FOD_REQUIRE(q1 && k1 && v && o && lse2, "attn_fwd: null operand");
   FOD_REQUIRE((q2 == nullptr) == (k2 == nullptr), "attn_fwd: q2/k2 must come together");
   p.q1 = q1; p.k1 = k1; p.q2 = q2; p.k2 = k2; p.v = v; p.o = o; p.lse2 = lse2;
-  return dispatch(dtype, q2 ? 2 : 1, 0, p, stream);
+  return dispatch(dtype, q2 ? 2 : 1, 0, p, r, stream);
 }
 
 extern "C" int fod_attn_bwd_dq(int dtype, const void* q1, const void* k1, const void* q2, const void* k2, const void* v,
                                const void* o, const void* dout, const float* lse2, float* delta, void* dq1, void* dq2,
                                const fod_attn_shape* shape, hipStream_t stream) {
   AttnParams p{};
-  int rc = fill(p, shape);
+  AttnRoute r{};
+  int rc = fill(p, r, dtype, shape);
   if (rc) return rc;
   FOD_REQUIRE(q1 && k1 && v && o && dout && lse2 && delta && dq1, "attn_bwd_dq: null operand");
   FOD_REQUIRE((q2 == nullptr) == (k2 == nullptr) && (q2 == nullptr) == (dq2 == nullptr), "attn_bwd_dq: part-2 pointers must come together");
   p.q1 = q1; p.k1 = k1; p.q2 = q2; p.k2 = k2; p.v = v; p.out = o; p.dout = dout;
   p.lse2 = const_cast<float*>(lse2); p.delta = delta;
   p.dq1 = dq1; p.dq2 = dq2;
-  return dispatch(dtype, q2 ? 2 : 1, 1, p, stream);
+  return dispatch(dtype, q2 ? 2 : 1, 1, p, r, stream);
 }
 
 extern "C" int fod_attn_bwd_dkv_multi(int dtype, int njobs, const void* const* ptrs, const fod_attn_shape* shape,
@@ -1620,7 +1645,8 @@ extern "C" int fod_attn_bwd_dkv_multi(int dtype, int njobs, const void* const* p
   FOD_REQUIRE(dtype == FOD_BF16, "attn_bwd_dkv_multi: bf16 only (dtype %d)", dtype);
   FOD_REQUIRE(ptrs && njobs > 0 && njobs <= DKV_MAX_JOBS, "attn_bwd_dkv_multi: 1 .. %d jobs (%d)", DKV_MAX_JOBS, njobs);
   AttnParams p{};
-  int rc = fill(p, shape);
+  AttnRoute r{};
+  int rc = fill(p, r, dtype, shape);
   if (rc) return rc;
   FOD_REQUIRE(p.drop_threshold == 0, "attn_bwd_dkv_multi: no dropout variant");
   FOD_REQUIRE((long)njobs * p.B <= 65535, "attn_bwd_dkv_multi: grid too large");
@@ -1649,7 +1675,8 @@ extern "C" int fod_attn_bwd(int dtype, const void* q1, const void* k1, const voi
                             void* dq1, void* dk1, void* dq2, void* dk2, void* dv,
                             const fod_attn_shape* shape, hipStream_t stream) {
   AttnParams p{};
-  int rc = fill(p, shape);
+  AttnRoute r{};
+  int rc = fill(p, r, dtype, shape);
   if (rc) return rc;
   FOD_REQUIRE(q1 && k1 && v && o && dout && lse2 && delta && dq1 && dk1 && dv, "attn_bwd: null operand");
   FOD_REQUIRE((q2 == nullptr) == (k2 == nullptr) && (q2 == nullptr) == (dq2 == nullptr) &&
@@ -1658,7 +1685,7 @@ extern "C" int fod_attn_bwd(int dtype, const void* q1, const void* k1, const voi
   p.lse2 = const_cast<float*>(lse2); p.delta = delta;
   p.dq1 = dq1; p.dk1 = dk1; p.dq2 = dq2; p.dk2 = dk2; p.dv = dv;
   const int parts = q2 ? 2 : 1;
-  rc = dispatch(dtype, parts, 1, p, stream);
+  rc = dispatch(dtype, parts, 1, p, r, stream);
   if (rc) return rc;
-  return dispatch(dtype, parts, 2, p, stream);
+  return dispatch(dtype, parts, 2, p, r, stream);
 }

@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libfod_hip.so"))
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 F32, BF16 = 0, 1
 EW_ADD, EW_MUL, EW_RELU_MASK, EW_SCALE, EW_ADD3, EW_RELU, EW_COPY_B = range(7)
@@ -72,9 +72,15 @@ class TnRoute(C.Structure):        # fod_tn_route: kernel is one of TN_SMALL / T
                 ("xcd_order", C.c_int), ("uses_partials_ws", C.c_int)]
 
 
+class AttnRoute(C.Structure):      # fod_attn_kernels: fwd / dq / dkv are one of ATTN_PLAIN / ATTN_LDS / ATTN_PREFETCH
+    _fields_ = [("fwd", C.c_int), ("dq", C.c_int), ("dkv", C.c_int), ("fwd_waves", C.c_int), ("key_split", C.c_int),
+                ("ksplit", C.c_int), ("kchunk", C.c_int)]
+
+
 NT_SMALL, NT_128, NT_BIG = range(3)           # FOD_ROUTE_NT_*
 TN_SMALL, TN_128, TN_BIG = range(3)           # FOD_ROUTE_TN_*
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = range(3)   # fod_conv2d_route(which, ...)
+ATTN_PLAIN, ATTN_LDS, ATTN_PREFETCH = range(3)   # FOD_ATTN_*
 
 _i, _l, _f, _p = C.c_int, C.c_long, C.c_float, C.c_void_p
 # struct arguments travel as addresses (C.addressof / None): plain ints are what the fast-call wrappers take
@@ -164,6 +170,7 @@ SIGNATURES = {
     "fod_gemm_nt_route": [_i, _l, _i, _l, _l, _i, _i, _i, _EP, _p],
     "fod_gemm_tn_route": [_i, _i, _i, _i, _l, _l, _l, _i, _i, _i, C.c_size_t, _p],
     "fod_conv2d_route": [_i, _i, _CG, _EP, _i, C.c_size_t, _p],
+    "fod_attn_route": [_i, _i, _AS, _p],
 }
 EXPORTS = sorted(list(SIGNATURES) + ["fod_last_error", "fod_abi_version", "fod_multi_chunk", "fod_workspace_bytes"])
 WS_NT_SPLIT, WS_NT_SPLIT_TICKETS, WS_TN_PARTIALS, WS_ATTN_SPLIT_PER_TILE, WS_DET, WS_TN_MULTI_DET = range(6)   # fod_workspace_bytes(kind)

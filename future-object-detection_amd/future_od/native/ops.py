@@ -580,6 +580,23 @@ def _bt(t, name, dtype):
     return bs, ts
 
 
+def attn_wants_split_ws(Tq, S):
+    """A launch with few queries whose keys the library may split across blocks when it is handed the scratch."""
+    return Tq <= 512 and S >= 256
+
+
+def attn_route(B, H, Tq, S, parts=1, dtype=torch.bfloat16, drop_p=0.0):
+    """L.AttnRoute of attn_fwd / attn_bwd on q [B, Tq, H*32], k / v [B, S, H*32] under the knobs in effect: the shape is
+    built as _attn_shape builds it for contiguous operands, the key-split scratch included (host only, no GPU needed)."""
+    E = H * 32
+    there = _THERE if attn_wants_split_ws(Tq, S) else None
+    shp = AttnShape(B, H, Tq, S, Tq * E, E, S * E, E, S * E, E, Tq * E, E, 1.0 / math.sqrt(32 * parts), 0, 0, 0, 0,
+                    float(drop_p), 0, None, there, there, 0.0)
+    r = L.AttnRoute()
+    call("fod_attn_route", _DT[dtype], parts, C.addressof(shp), C.addressof(r))
+    return r
+
+
 def _attn_shape(q1, k1, v, o, scale, k2=None, dk2=None, drop_p=0.0, drop_seed=0, dq_scale=0.0):
     dtp = q1.dtype
     B, Tq, E = q1.shape
@@ -599,7 +616,7 @@ def _attn_shape(q1, k1, v, o, scale, k2=None, dk2=None, drop_p=0.0, drop_seed=0,
         assert dk2.shape == (B, S, E)
         d2b, d2t = _bt(dk2, "dk2", dtp)
     ws = tk = None
-    if Tq <= 512 and S >= 256:
+    if attn_wants_split_ws(Tq, S):
         ws, tk = _attn_split_workspace(q1.device, B * H * ((Tq + 31) // 32))
     return AttnShape(B, H, Tq, S, qb, qt, kb, kt, vb, vt, ob, ot, scale, k2b, k2t, d2b, d2t, float(drop_p),
                      int(drop_seed) & 0xFFFFFFFFFFFFFFFF, ptr(DROP_BASE) if drop_p > 0.0 else None, ptr(ws), ptr(tk),

@@ -45,7 +45,7 @@ enum { FOD_OK = 0, FOD_ERR_ARG = 1, FOD_ERR_LAUNCH = 2, FOD_ERR_RUNTIME = 3 };
 size_t fod_last_error(char* buf, size_t cap);
 /* ABI version of this header; the loader refuses a library that disagrees. */
 int fod_abi_version(void);
-#define FOD_ABI_VERSION 7
+#define FOD_ABI_VERSION 8
 
 /* Kernel-selection knobs: the FOD_* variables the library looks at (listed with their values and defaults in
  * csrc/knobs.h) live in one process-wide host table that is filled from the environment ONCE, at its first use; a
@@ -402,6 +402,21 @@ int fod_attn_bwd_dq(int dtype, const void* q1, const void* k1, const void* q2, c
                     const fod_attn_shape* shape, fod_stream_t stream);
 int fod_attn_bwd_dkv_multi(int dtype, int njobs, const void* const* ptrs, const fod_attn_shape* shape,
                            fod_stream_t stream);
+/* The route of fod_attn_fwd / fod_attn_bwd / fod_attn_bwd_dq (dtype, q2 given: parts = 2, else 1, shape) under the knobs
+ * in effect; host-only like the queries above.  Of the shape's pointers only split_ws / split_tickets are looked at, and
+ * only for NULL / non-NULL (any non-NULL value stands for scratch that would be handed over).  fod_attn_bwd_dkv_multi is
+ * always the prefetching kernel. */
+enum { FOD_ATTN_PLAIN = 0,      /* registers only; with key_split: a block's four waves share the keys of 32 queries */
+       FOD_ATTN_LDS = 1,        /* bf16, no dropout: K / V tiles staged through LDS (forward, dq and dk/dv go together) */
+       FOD_ATTN_PREFETCH = 2 }; /* dk/dv pass only, bf16: the next query tile in flight */
+typedef struct fod_attn_kernels {
+  int fwd, dq, dkv;   /* FOD_ATTN_* of the forward, dq and dk/dv passes */
+  int fwd_waves;      /* waves per block of the forward: 4 | 8 */
+  int key_split;      /* forward and dq: the keys are split over the waves of a block (few queries) */
+  int ksplit;         /* ... and over this many blocks (1 = none; needs fod_attn_shape.split_ws / split_tickets) */
+  int kchunk;         /* keys per block-level split (S when ksplit = 1) */
+} fod_attn_kernels;
+int fod_attn_route(int dtype, int parts, const fod_attn_shape* shape, fod_attn_kernels* out);
 
 /* fp8 attention forward (BASELINE.json configs[4]; csrc/attention_fp8.hip): OCP e4m3 operands with one E8M0 scale per
  * 32-element block (a token's head slice for q / k, 32 keys of a channel for v), v_mfma_scale_f32_32x32x64_f8f6f4.

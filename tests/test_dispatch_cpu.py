@@ -11,6 +11,8 @@ import torch
 from future_od.native import lib as L
 from future_od.native import ops
 
+import variant_cases as V
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "future-object-detection_amd")
 C_KNOBS = ["FOD_NT_SMALL", "FOD_NT_NARROW", "FOD_NT_SPLITK", "FOD_NT_BIG", "FOD_NT_BIG256", "FOD_NT_BIG_ILV",
@@ -181,3 +183,174 @@ def test_route_queries_check_their_arguments():
     assert L.LIB.fod_gemm_nt_route(L.BF16, 250, 0, 250, 256, 64, 256, 250, None, C_addr(r)) != 0 and "multiples" in L.last_error()
     assert L.LIB.fod_gemm_nt_route(L.BF16, 256, 0, 256, 256, 64, 256, 256, None, None) != 0
     assert L.LIB.fod_conv2d_route(7, L.BF16, C_addr(_conv(64, 64, 3, 8, 8)), None, 0, 0, C_addr(r)) != 0
+    a, shp = L.AttnRoute(), L.AttnShape(1, 2, 64, 64, 4096, 64, 4096, 64, 4096, 64, 4096, 64, 0.1)
+    assert L.LIB.fod_attn_route(L.BF16, 1, C_addr(shp), C_addr(a)) == 0
+    assert L.LIB.fod_attn_route(L.BF16, 3, C_addr(shp), C_addr(a)) != 0 and L.LIB.fod_attn_route(7, 1, C_addr(shp), C_addr(a)) != 0
+    assert L.LIB.fod_attn_route(L.BF16, 1, None, C_addr(a)) != 0 and L.LIB.fod_attn_route(L.BF16, 1, C_addr(shp), None) != 0
+    shp.q_token_stride = 60
+    assert L.LIB.fod_attn_route(L.BF16, 1, C_addr(shp), C_addr(a)) != 0 and "multiples of 8" in L.last_error()
+
+
+# ---- the attention route (fod_attn_route) -------------------------------------------------------------------------------
+def _attn(r):
+    return (r.fwd, r.dq, r.dkv, r.fwd_waves, r.key_split)
+
+
+PLAIN, LDS, PF = L.ATTN_PLAIN, L.ATTN_LDS, L.ATTN_PREFETCH
+ATTN_GRID = [(B, H, Tq, S) for B in (1, 2) for H in (1, 8) for Tq in (1, 33, 128, 512, 513, 1450)
+             for S in (1, 127, 128, 255, 256, 1450)]
+
+
+def test_attention_default_routes():
+    """DESIGN.md §3 / launch_all in a table.  bf16 with Tq > 512 or S < 128: the three LDS kernels, eight-wave forward;
+    Tq <= 512 and S >= 128: the keys split over a block's waves, prefetching dK/dV; f32: the plain kernels everywhere;
+    dropout: never the LDS kernels.  Keys are split across blocks only for Tq <= 512 and S >= 256, in whole 128-key
+    tiles, at most 8 ways, and only while the launch stays within one round of 256 blocks."""
+    for B, H, Tq, S in ATTN_GRID:
+        split = int(Tq <= 512 and S >= 128)
+        for parts in (1, 2):
+            r = ops.attn_route(B, H, Tq, S, parts)
+            assert _attn(r) == ((PLAIN, PLAIN, PF, 4, 1) if split else (LDS, LDS, LDS, 8, 0)), (B, H, Tq, S)
+            assert _attn(ops.attn_route(B, H, Tq, S, parts, torch.float32)) == (PLAIN, PLAIN, PLAIN, 4, split)
+            assert _attn(ops.attn_route(B, H, Tq, S, parts, drop_p=0.1)) == (PLAIN, PLAIN, PF, 4, split)
+            assert _attn(ops.attn_route(B, H, Tq, S, parts, torch.float32, drop_p=0.1)) == (PLAIN, PLAIN, PLAIN, 4, split)
+            for q in (r, ops.attn_route(B, H, Tq, S, parts, torch.float32), ops.attn_route(B, H, Tq, S, parts, drop_p=0.1)):
+                assert (q.ksplit, q.kchunk) == (r.ksplit, r.kchunk)        # the split across blocks is the shape's alone
+            tiles = B * H * ((Tq + 31) // 32)
+            if Tq > 512 or S < 256:
+                assert (r.ksplit, r.kchunk) == (1, S)
+            else:
+                assert 1 <= r.ksplit <= min(8, S // 128) and r.ksplit * tiles <= max(256, tiles)
+                assert r.kchunk % 128 == 0 or r.ksplit == 1
+                assert (r.ksplit - 1) * r.kchunk < S <= r.ksplit * r.kchunk
+    r = ops.attn_route(2, 8, 128, 1450, 2)                                 # the decoder's cross-attention
+    assert (r.ksplit, r.kchunk) == (4, 384)
+
+
+def test_attention_scratch_decides_the_split_across_blocks():
+    """Without the caller's scratch (either pointer NULL) the keys are not split across blocks; the query looks at the
+    pointers for NULL / non-NULL only (the addresses handed over here are not mapped)."""
+    E = 32
+    for ws, tk, want in ((None, None, 1), (4096, None, 1), (None, 4096, 1), (4096, 8, 8)):
+        shp = L.AttnShape(1, 1, 33, 2000, 33 * E, E, 2000 * E, E, 2000 * E, E, 33 * E, E, 0.1, 0, 0, 0, 0, 0.0, 0, None, ws, tk)
+        r = L.AttnRoute()
+        ops.call("fod_attn_route", L.BF16, 1, C_addr(shp), C_addr(r))
+        assert r.ksplit == want and r.key_split == 1
+
+
+def test_attention_knobs_move_the_routes():
+    """FOD_ATTN_LDS / FOD_ATTN_PF as csrc/knobs.h describes them: 0 = no LDS-staged kernels (forward, dq and dK/dV
+    together), 4 = the four-wave forward, 8 = the eight-wave one; FOD_ATTN_PF=0 = no prefetching dK/dV kernel.  Neither
+    touches a launch the other family owns, f32, or the split across blocks."""
+    long_, few = (1, 2, 600, 333), (1, 2, 128, 300)
+    assert (L.knob("FOD_ATTN_LDS"), L.knob("FOD_ATTN_PF")) == ("8", "1")
+    base_few = ops.attn_route(*few)
+    with L.knobs(FOD_ATTN_LDS=0):
+        assert _attn(ops.attn_route(*long_)) == (PLAIN, PLAIN, PF, 4, 0)
+        assert _attn(ops.attn_route(*few)) == _attn(base_few)
+        with L.knobs(FOD_ATTN_PF=0):
+            assert _attn(ops.attn_route(*long_)) == (PLAIN, PLAIN, PLAIN, 4, 0)
+    with L.knobs(FOD_ATTN_LDS=4):
+        assert _attn(ops.attn_route(*long_)) == (LDS, LDS, LDS, 4, 0)
+        assert _attn(ops.attn_route(*long_, drop_p=0.1)) == (PLAIN, PLAIN, PF, 4, 0)
+    with L.knobs(FOD_ATTN_LDS=8):
+        assert _attn(ops.attn_route(*long_)) == (LDS, LDS, LDS, 8, 0)
+    with L.knobs(FOD_ATTN_PF=0):
+        assert _attn(ops.attn_route(*long_)) == (LDS, LDS, LDS, 8, 0)
+        assert _attn(ops.attn_route(*few)) == (PLAIN, PLAIN, PLAIN, 4, 1)
+        assert _attn(ops.attn_route(*long_, drop_p=0.1)) == (PLAIN, PLAIN, PLAIN, 4, 0)
+        r = ops.attn_route(*few)
+        assert (r.ksplit, r.kchunk) == (base_few.ksplit, base_few.kchunk) and base_few.ksplit > 1
+    for knobs in (dict(FOD_ATTN_LDS=0), dict(FOD_ATTN_LDS=4), dict(FOD_ATTN_PF=0)):
+        with L.knobs(**knobs):
+            for shape in (long_, few):
+                assert _attn(ops.attn_route(*shape, dtype=torch.float32))[:3] == (PLAIN, PLAIN, PLAIN)
+
+
+def test_python_mirror_of_the_attention_scratch_agrees_with_the_library():
+    """ops.attn_wants_split_ws decides whether _attn_shape hands the key-split scratch over: the library never splits
+    across blocks where the wrapper would not have attached it."""
+    E = 32
+    for B, H, Tq, S in ATTN_GRID:
+        shp = L.AttnShape(B, H, Tq, S, Tq * H * E, H * E, S * H * E, H * E, S * H * E, H * E, Tq * H * E, H * E, 0.1, 0, 0, 0,
+                          0, 0.0, 0, None, 16, 16)
+        r = L.AttnRoute()
+        ops.call("fod_attn_route", L.BF16, 1, C_addr(shp), C_addr(r))
+        assert r.ksplit == 1 or ops.attn_wants_split_ws(Tq, S), (B, H, Tq, S)
+        assert r.ksplit == ops.attn_route(B, H, Tq, S).ksplit
+
+
+# ---- the table of variant cases (tests/variant_cases.py) ------------------------------------------------------------------
+@pytest.mark.parametrize("family", sorted({c.family for c in V.CASES}))
+def test_variant_table_routes(family):
+    """Every case of tests/test_variants_gpu.py takes, under its knobs and mode, the kernel the table says: held against
+    the library here, before any GPU visit."""
+    mine = V.cases(family)
+    assert mine
+    for c in mine:
+        assert V.route_mismatches(c) == [], V.case_id(c)
+        for name, value in c.knobs.items():                  # ... and the knobs are values the library takes
+            with L.knobs(**{name: value}):
+                assert L.knob(name) == str(value)
+    assert len({V.case_id(c) for c in mine}) == len(mine)
+
+
+def test_variant_table_census():
+    """The table as a whole reaches every selectable variant: a variant cannot drop out when a threshold moves, because
+    the route of each case is the library's (test_variant_table_routes) and the set of routes is counted here."""
+    def routes(family, *fields, **where):
+        return {tuple(c.expect[f] for f in fields) for c in V.cases(family, **where)}
+
+    # NT_128 with the 128-wide tile: dense with the vector and the scalar epilogue, conv forward, dgrad, stride-2 dgrad
+    for dt in V.BOTH:
+        for where in (dict(call="gemm_nt", epilogue="vector"), dict(call="gemm_nt", epilogue="scalar"), dict(call="conv_fwd"),
+                      dict(call="conv_dgrad", stride=1), dict(call="conv_dgrad", stride=2)):
+            assert routes("nt128", "kernel", "tile_n", dtype=dt, **where) == {(L.NT_128, 128)}, (dt, where)
+        assert any(c.shape[1] % 128 and c.shape[1] % 4 == 0 for c in V.cases("nt128", call="gemm_nt", dtype=dt))   # ragged last tile
+        assert all(c.shape[1] % 4 for c in V.cases("nt128", epilogue="scalar"))
+        assert V.cases("nt128", dtype=dt, full_epilogue=True)
+    assert routes("nt_splitk", "kernel") == {(L.NT_SMALL,)}
+    assert {k for (k,) in routes("nt_splitk", "ksplit")} >= {1, 2, 3, 4, 8}
+    assert any(c.shape[2] % (256 * c.expect["ksplit"]) for c in V.cases("nt_splitk"))          # K chunks that do not divide K
+    assert routes("nt_big", "kernel", "stages", "interleave") == {(L.NT_BIG, 3, 1), (L.NT_BIG, 3, 0), (L.NT_BIG, 2, 0), (L.NT_BIG, 2, 1)}
+    for call in ("gemm_nt", "conv_fwd", "conv_dgrad"):
+        assert routes("nt_big", "stages", "interleave", call=call) >= {(3, 0), (2, 1)}
+    # TN_128: both block orders, an XCD-ordered launch whose split count is no multiple of 8, plain and deterministic
+    for dt in V.BOTH:
+        assert routes("tn128", "kernel", "xcd_order", dtype=dt) == {(L.TN_128, 0), (L.TN_128, 1)}
+        ragged = [c for c in V.cases("tn128", dtype=dt) if c.expect["xcd_order"] and c.expect["nsplit"] % 8]
+        assert {bool(c.extra.get("det")) for c in ragged} == {False, True}
+        assert {23, 15} <= {c.expect["nsplit"] for c in ragged}
+    # TN_BIG with several M-splits: partial tiles and atomics, dense and conv, the square tile, deterministic
+    big = V.cases("tn_big")
+    assert all(c.expect["kernel"] == L.TN_BIG and c.expect["nsplit"] > 1 for c in big)
+    for call in ("gemm_tn", "conv_wgrad"):
+        assert routes("tn_big", "uses_partials_ws", call=call) == {(0,), (1,)}
+    assert any((c.expect.get("bi"), c.expect.get("bj")) == (256, 256) and c.expect["uses_partials_ws"] for c in big)
+    assert any(c.extra.get("det") for c in big)
+    assert any(c.shape[1] % 128 and c.shape[2] % 128 for c in V.cases("tn_big", call="gemm_tn"))     # ragged N1 and K2
+    # layer norm: every width at the four row counts, the group knob at the many-row ones
+    for dt in V.BOTH:
+        seen = {(c.shape, c.knobs.get("FOD_LN_BWD_GROUPS")) for c in V.cases("layernorm", dtype=dt)}
+        want = {((rows, D), g) for D in range(64, 513, 64) for rows in (37, 8191) for g in (None,)}
+        want |= {((rows, D), g) for D in range(64, 513, 64) for rows in (8192, 8200) for g in (1, 4, 16)}
+        assert seen == want
+    # attention: the six (forward, dq, dK/dV) families and the split across blocks
+    fams = set()
+    for family in ("attn_family", "attn_ksplit", "attn_strided"):
+        for c in V.cases(family, dtype="bf16"):
+            e = c.expect
+            fwd = "lds%d" % e["fwd_waves"] if e["fwd"] == LDS else "split" if e["key_split"] else "plain"
+            dq = "lds" if e["dq"] == LDS else "split" if e["key_split"] else "plain"
+            fams.add((fwd, dq, {PLAIN: "plain", LDS: "lds", PF: "prefetch"}[e["dkv"]]))
+    assert fams == {("lds8", "lds", "lds"), ("lds4", "lds", "lds"), ("plain", "plain", "prefetch"), ("plain", "plain", "plain"),
+                    ("split", "split", "prefetch"), ("split", "split", "plain")}
+    drop = {(c.expect["key_split"], c.expect["dkv"]) for c in V.cases("attn_family") if c.extra.get("drop")}
+    assert drop == {(0, PLAIN), (1, PLAIN)}
+    for dt in V.BOTH:
+        assert {k for (k,) in routes("attn_ksplit", "ksplit", dtype=dt)} >= {1, 2, 3, 4, 8}
+    assert {(c.expect["fwd"], c.expect["key_split"], c.expect["ksplit"] > 1) for c in V.cases("attn_strided")} == \
+        {(LDS, 0, False), (PLAIN, 1, True), (PLAIN, 0, False)}
+    assert {c.expect["fwd_waves"] for c in V.cases("attn_extreme")} == {4, 8} and V.cases("attn_saturated")
+    # no route query sees these two knobs: the cases exist, and the knob reads back (test_variant_table_routes)
+    assert len(V.cases("fp8_stage2")) == 8 and all(c.knobs == dict(FOD_FP8_STAGE=2) for c in V.cases("fp8_stage2"))

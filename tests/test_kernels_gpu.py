@@ -513,8 +513,17 @@ def test_attention_forward_deferred_max_and_extreme_scores(parts):
     it by 2^6, and biases its score accumulators by that maximum: force the rare branches.  Keys whose scores jump
     by far more than the threshold at several tiles (for some queries only), rows of hugely negative and hugely
     positive scores, and a check of the log-sum-exp itself."""
+    deferred_max_and_extreme_scores(parts)
+
+
+def deferred_max_and_extreme_scores(parts, shape=(1, 2, 300, 460)):
+    """The body of the test above for a (B, H, Tq >= 300, S = 460) shape.  At the 300 queries of the test above the call
+    takes the kernel that splits the keys over a block's waves (Tq <= 512, S >= 128: ops.attn_route), whose running
+    maximum meets the same scores; tests/test_variants_gpu.py runs this body at 600 queries, where the LDS forwards
+    (four and eight waves) are what the route names."""
     dtype = torch.bfloat16
-    B, H, Tq, S = 1, 2, 300, 460
+    B, H, Tq, S = shape
+    assert B == 1 and Tq >= 300 and S == 460              # the forced rows and keys below
     E = H * 32
     g = torch.Generator().manual_seed(77)
     q1 = torch.randn(B, Tq, E, generator=g)
@@ -556,6 +565,11 @@ def test_attention_saturated_softmax_forward_backward_consistency(shape):
     their scores from queries pre-multiplied by scale * log2(e) and rounded to bf16 -- all three passes must use the
     SAME rounded scores, or exp2(score - lse) in the backward explodes (observed: NaN loss at the headline size).
     Reference: the same rounding with a straight-through gradient, in float64."""
+    saturated_softmax_forward_backward(shape)
+
+
+def saturated_softmax_forward_backward(shape):
+    """The body of the test above (tests/test_variants_gpu.py runs it on the kernels the knobs select)."""
     dtype = torch.bfloat16
     B, H, Tq, S, parts = shape
     E = H * 32
@@ -632,6 +646,11 @@ def test_attention_fp8_forward_and_backward(shape, peaked):
       * backward (bf16 kernels on the dequantised operands, the same quantised scores) vs float64 autograd of the
         quantised-operand attention with straight-through quantisers: ||error|| <= 6e-2 ||gradient|| (+ 1e-2 per element).
     `peaked`: queries x 4, a softmax with a few dominant keys (the averaging that hides P's rounding is gone)."""
+    attention_fp8_forward_and_backward(shape, peaked)
+
+
+def attention_fp8_forward_and_backward(shape, peaked):
+    """The body of the test above (tests/test_variants_gpu.py runs it with two key tiles per barrier)."""
     dtype = torch.bfloat16
     B, H, Tq, S, parts = shape
     E = H * 32
