@@ -91,6 +91,15 @@ class _Prepared:
             e.vers = tuple(p._version for p in e.params)
             e.epoch = self.epoch if any(p.requires_grad for p in e.params) else -2
 
+    @staticmethod
+    def _takes_rows_path(j):
+        """The rows condition of multi_permute_body (csrc/elementwise.hip), on the host."""
+        d0, d1, d2 = j.dims
+        s0, s1, s2 = j.sstr
+        return ((s2 == 1 or d2 == 1) and d2 % 4 == 0 and j.valid2 % 4 == 0 and j.src.dtype == torch.float32
+                and j.src.data_ptr() % 16 == 0 and s0 % 4 == 0 and s1 % 4 == 0
+                and j.dstr[0] % 4 == 0 and j.dstr[1] % 4 == 0 and j.dst.data_ptr() % 16 == 0)
+
     def _build_tables(self, jobs):
         import ctypes as C
         import numpy as np
@@ -100,6 +109,9 @@ class _Prepared:
         bj, bc = [], []
         for i, j in enumerate(jobs):
             d0, d1, d2 = j.dims
+            if j.scale is not None and j.axis == 2 and j.scale.data_ptr() % 16 and self._takes_rows_path(j):
+                raise L.FodError(f"permute job {j.dims}: it takes the kernel's rows path, which reads a scale along "
+                                 f"dim 2 with 16-byte loads: the scale must be 16-byte aligned")
             arr[i] = L.PermuteJob(j.src.data_ptr(), j.dst.data_ptr(), 0 if j.scale is None else j.scale.data_ptr(),
                                   ops._DT[j.src.dtype], ops._DT[j.dst.dtype], d0, d1, d2, j.valid1, j.valid2, j.axis,
                                   j.sstr[0], j.sstr[1], j.sstr[2], j.dstr[0], j.dstr[1])

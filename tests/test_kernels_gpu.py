@@ -5,6 +5,11 @@ Tolerances (stated per dtype, checked as max|a-b| <= atol + rtol*|b| ):
   f32  mode: exact-f32 MFMA, differs from torch only by summation order  -> rtol 2e-5 / atol scaled
   bf16 mode: inputs rounded to bf16 (the reference is computed from the SAME rounded inputs in
              fp32), output rounded to bf16                               -> rtol 1.6e-2 (2 bf16 ulp)
+
+The siblings of the variant the default rule picks are in tests/test_variants_gpu.py; the branches of the kernels that
+move and reshape data (csrc/elementwise.hip: fod_multi_permute3, fod_eltwise, fod_permute3_cast, the layout and pooling
+kernels, fod_colsum_groups_multi, the reference-point / box-head kernels) and of csrc/optim.hip are in
+tests/test_layout_gpu.py, which compares them bit for bit with the same f32 operations done on the CPU.
 """
 import contextlib
 import math
