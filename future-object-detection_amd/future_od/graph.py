@@ -32,9 +32,12 @@ Restrictions (checked): one device per process, static shapes -- a batch with ot
 import torch
 import torch.distributed as dist
 
+from future_od.native import arena
 from future_od.native import capture
 from future_od.native import functional as Fn
 from future_od.native import ops
+from future_od.native import prepared
+from future_od.native import wgrad
 
 
 def _stage_inputs(g, data):
@@ -235,7 +238,7 @@ class GraphedStep:
         `arena_from` / `skip`: only arena gradients from that element offset on, none of the tensors whose data_ptr is
         in `skip` -- the second piece of a split backward."""
         grads = [p.grad for p in self.core.parameters() if p.requires_grad and p.grad is not None]
-        buf = Fn.ARENA.buf if Fn.ARENA.active else None
+        buf = arena.ARENA.buf if arena.ARENA.active else None
         targets, lo, hi = [], None, None
         for g in grads:
             inside = (buf is not None and g.is_cuda and g.dtype == torch.float32
@@ -279,7 +282,7 @@ class GraphedStep:
         opt._step_no = snap["step_no"]
         if getattr(opt, "_dev_step", None) is not None:
             opt._dev_step.fill_(float(snap["step_no"]))
-        Fn.PREP.mark_stale()
+        prepared.PREP.mark_stale()
 
     def _capture(self, data):
         # the capture's eager warm-up steps are real optimizer steps: with rollback_warmup they are undone whether the
@@ -333,7 +336,7 @@ class GraphedStep:
                 self._eager(static)               # one eager step through the device-side bias corrections
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        Fn.WGRADS.prepare(dev)                    # pinned job tables for the captures below (none can be made inside)
+        wgrad.WGRADS.prepare(dev)                    # pinned job tables for the captures below (none can be made inside)
         ops.preallocate_graph_workspaces(dev)     # scratch of the captured launches: allocated and zeroed out here
         if not self.ddp:
             graph = torch.cuda.CUDAGraph()
@@ -364,7 +367,7 @@ class GraphedStep:
             first = self._reduce_targets()
             graph_a2, second = None, []
             if cut is not None and cut.pairs:
-                off1 = Fn.ARENA.off if Fn.ARENA.active else 0
+                off1 = arena.ARENA.off if arena.ARENA.active else 0
                 graph_a2 = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph_a2, pool=graph_a.pool(), capture_error_mode="thread_local"):
                     cut.finish()
@@ -441,7 +444,7 @@ class GraphedStep:
             g["graph_opt"].replay()
         self.opt._step_no += 1
         self.replays += 1
-        Fn.PREP.mark_stale()          # the replay changed the parameters without bumping their python-side versions
+        prepared.PREP.mark_stale()          # the replay changed the parameters without bumping their python-side versions
         return g["outs"]
 
 
@@ -492,12 +495,12 @@ class GraphedForward:
                 # the second pass refreshes every prepared weight copy eagerly: its job table (pinned upload) must
                 # exist before the capture -- nothing may be allocated on the host inside one
                 self._run(static)
-                Fn.PREP.mark_stale()
+                prepared.PREP.mark_stale()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         ops.preallocate_graph_workspaces(dev)
-        Fn.PREP.refresh()                         # the graph reads the prepared weight copies; they are refreshed
+        prepared.PREP.refresh()                         # the graph reads the prepared weight copies; they are refreshed
         with capture.Record() as record, torch.cuda.graph(graph):      # eagerly before a replay, and only when a
             outs = self._run(static)                                    # parameter has changed
         torch.cuda.synchronize(dev)
@@ -519,7 +522,7 @@ class GraphedForward:
             self._graphs[sig] = g
         _check_matcher(g)
         _stage_inputs(g, data)
-        Fn.PREP.refresh()                             # one launch if an optimizer step happened since, nothing otherwise
+        prepared.PREP.refresh()                             # one launch if an optimizer step happened since, nothing otherwise
         g["graph"].replay()
         self.replays += 1
         return g["outs"]

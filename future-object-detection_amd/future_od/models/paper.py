@@ -24,6 +24,7 @@ from torch import Tensor
 from future_od.models.transformer import MLP, TransformerEncoder
 from future_od.native import functional as Fn
 from future_od.native import ops
+from future_od.native import prepared
 from future_od.native.backbone import ConvWeight, ResNetBody, run_backbone
 
 
@@ -145,7 +146,7 @@ class _PaddedInLinear(torch.autograd.Function):
         def build():
             out = torch.empty((N, Ip), dtype=x.dtype, device=wd.device)          # columns >= I zero
             return out, [Fn._Job(wd, out, (1, N, Ip), (0, wd.stride(0), wd.stride(1)), valid2=I)]
-        wp = Fn.PREP.get(Fn._wkey(weight, f"lin_pad{Ip}", x.dtype), [weight], build)
+        wp = prepared.PREP.get(Fn._wkey(weight, f"lin_pad{Ip}", x.dtype), [weight], build)
         y = ops.gemm_nt(x, wp, shift=bias, relu=relu)
         ctx.save_for_backward(x, y)
         ctx.meta = (I, relu, N, Ip)

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
+from . import arena
 from . import functional as Fn
 from . import ops
 
@@ -335,7 +336,7 @@ class BackboneFn(Function):
         if sync is not None:
             # data parallel: the backbone is the first node of the graph, so it runs last in backward and every
             # transformer gradient is final by now -- their average over ranks travels during the whole sweep below
-            sync.flush(Fn.ARENA)
+            sync.flush(arena.ARENA)
 
         def wgrad(gy, xin, cw, geom, scale):
             co, ci, kh, kw = cw.weight.shape
@@ -393,7 +394,7 @@ class BackboneFn(Function):
                         d_idt = g_out
                     g = ops.conv2d_dgrad(gcur, w1t, geoms[0], residual=d_idt, relu_mask=acts[0])
             if sync is not None:
-                sync.maybe_flush(Fn.ARENA)        # this block's weight gradients are final (weights are used once)
+                sync.maybe_flush(arena.ARENA)        # this block's weight gradients are final (weights are used once)
         ctx.tape = None
         out = [None, None, None, None]
         for w in ctx.train_weights:

@@ -1,206 +1,21 @@
 """Autograd glue: each Function's forward and backward are calls into libfod_hip.so.
 
-Parameters stay fp32 `nn.Parameter`s with the reference's names and shapes; kernels consume
-prepared copies (cast to the compute dtype, transposed for input-gradients, BN scale folded for
-convs) that are cached per parameter version, so a copy is rebuilt only after an optimizer step.
-Activations and their gradients are in the compute dtype (torch.float32 = parity mode,
-torch.bfloat16 = performance mode); parameter gradients are fp32.
+Parameters are fp32; kernels consume prepared copies of them (native/prepared.py).  Activations and their gradients are
+in the compute dtype (torch.float32 = parity mode, torch.bfloat16 = performance mode); parameter gradients are fp32
+slices of the zero arena (native/arena.py), the short and the long ones filled by the queue of native/wgrad.py.
 """
 import os
 
 import torch
 from torch.autograd import Function
 
-from . import capture
 from . import lib as L
 from . import ops
-
-_VEC = {torch.float32: 4, torch.bfloat16: 8}
-
-
-# ------------------------------------------------------------------------------------------------
-# prepared-weight registry
-#
-# Every kernel operand derived from a parameter (compute-dtype copy, transposed copy for input gradients, BN
-# scale folded in, several Linear layers stacked) is declared ONCE as a list of strided-copy jobs into persistent
-# buffers.  After an optimizer step (parameter `_version` bumped) the first request for any of them refreshes ALL
-# stale ones with a single `fod_multi_permute3` launch (one job table on the device, cached while the set is the
-# same) instead of ~75 small launches scattered over the next forward.
-# ------------------------------------------------------------------------------------------------
-class _Job:
-    __slots__ = ("src", "dst", "dims", "sstr", "dstr", "valid1", "valid2", "scale", "axis")
-
-    def __init__(self, src, dst, dims, sstr, dstr=None, valid1=None, valid2=None, scale=None, axis=-1):
-        d0, d1, d2 = dims
-        self.src, self.dst, self.dims, self.sstr = src, dst, dims, sstr
-        self.dstr = dstr if dstr is not None else (d1 * d2, d2)
-        self.valid1 = d1 if valid1 is None else valid1
-        self.valid2 = d2 if valid2 is None else valid2
-        self.scale, self.axis = scale, axis
-
-
-class _Entry:
-    __slots__ = ("params", "vers", "jobs", "value", "epoch")
-
-
-class _Prepared:
-    def __init__(self):
-        self._store = {}
-        self._tables = {}
-        self._chunk = None
-        # Bumped by every writer that changes parameters WITHOUT going through torch (the fused AdamW kernel and a
-        # replayed hipGraph write through raw pointers: `_version` does not move).  An operand is fresh only if both
-        # its parameters' versions and this epoch are the ones it was built at.
-        self.epoch = 0
-
-    def _fresh(self, e):
-        # (operands of frozen parameters -- stem, layer1, every frozen-BN fold -- are not touched by an optimizer)
-        return (e.epoch == self.epoch or e.epoch == -2) and e.vers == tuple(p._version for p in e.params)
-
-    def get(self, key, params, build):
-        """`build()` -> (value, jobs): allocates the persistent buffers and declares how they are filled."""
-        e = self._store.get(key)
-        if e is None:
-            e = _Entry()
-            e.params = [p for p in params if p is not None]
-            e.value, e.jobs = build()
-            e.vers = None
-            e.epoch = -1
-            if len(self._store) > 4096:
-                self.clear()
-            self._store[key] = e
-        if not self._fresh(e):
-            self.refresh()
-        return e.value
-
-    def refresh(self):
-        stale = [e for e in self._store.values() if not self._fresh(e)]
-        if not stale:
-            return
-        key = tuple(id(e) for e in stale)
-        tab = self._tables.get(key)
-        if tab is None:
-            tab = self._build_tables([j for e in stale for j in e.jobs])
-            if len(self._tables) > 16:
-                self._tables.clear()
-            self._tables[key] = tab
-        capture.hold_or_ask("refresh table", tab)      # raw pointers: a capture that records this launch keeps it
-        jobs_dev, blk_job, blk_chunk, nblocks, _keep = tab
-        L.call("fod_multi_permute3", ops.ptr(jobs_dev), ops.ptr(blk_job), ops.ptr(blk_chunk), nblocks, ops.stream())
-        for e in stale:
-            e.vers = tuple(p._version for p in e.params)
-            e.epoch = self.epoch if any(p.requires_grad for p in e.params) else -2
-
-    @staticmethod
-    def _takes_rows_path(j):
-        """The rows condition of multi_permute_body (csrc/elementwise.hip), on the host."""
-        d0, d1, d2 = j.dims
-        s0, s1, s2 = j.sstr
-        return ((s2 == 1 or d2 == 1) and d2 % 4 == 0 and j.valid2 % 4 == 0 and j.src.dtype == torch.float32
-                and j.src.data_ptr() % 16 == 0 and s0 % 4 == 0 and s1 % 4 == 0
-                and j.dstr[0] % 4 == 0 and j.dstr[1] % 4 == 0 and j.dst.data_ptr() % 16 == 0)
-
-    def _build_tables(self, jobs):
-        import ctypes as C
-        import numpy as np
-        if self._chunk is None:
-            self._chunk = int(L.LIB.fod_multi_permute_chunk())
-        arr = (L.PermuteJob * len(jobs))()
-        bj, bc = [], []
-        for i, j in enumerate(jobs):
-            d0, d1, d2 = j.dims
-            if j.scale is not None and j.axis == 2 and j.scale.data_ptr() % 16 and self._takes_rows_path(j):
-                raise L.FodError(f"permute job {j.dims}: it takes the kernel's rows path, which reads a scale along "
-                                 f"dim 2 with 16-byte loads: the scale must be 16-byte aligned")
-            arr[i] = L.PermuteJob(j.src.data_ptr(), j.dst.data_ptr(), 0 if j.scale is None else j.scale.data_ptr(),
-                                  ops._DT[j.src.dtype], ops._DT[j.dst.dtype], d0, d1, d2, j.valid1, j.valid2, j.axis,
-                                  j.sstr[0], j.sstr[1], j.sstr[2], j.dstr[0], j.dstr[1])
-            nchunks = int(L.LIB.fod_multi_permute_tiles(d0, d1, d2, j.sstr[0], j.sstr[1], j.sstr[2]))
-            assert nchunks >= 0, f"permute job {j.dims} too large"
-            bj.extend([i] * nchunks)
-            bc.extend(range(nchunks))
-        dev = jobs[0].dst.device
-        raw = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy())
-        up = lambda t: (t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t.to(dev))
-        return (up(raw), up(torch.tensor(bj, dtype=torch.int32)), up(torch.tensor(bc, dtype=torch.int32)), len(bj),
-                [(j.src, j.dst, j.scale) for j in jobs])       # keep the operands alive while the table exists
-
-    def mark_stale(self):
-        """Every prepared operand is out of date (parameters were changed behind autograd's back, e.g. by a replayed
-        hipGraph whose AdamW kernel does not bump `_version`): the next request refreshes them all."""
-        self.epoch += 1
-
-    def clear(self):
-        # buffers and job tables that a captured graph replays are held by that graph's record (native/capture.py: the
-        # store generation through the provider below, a table where its launch is recorded); the rest is freed here
-        capture.hold_or_ask("prepared operands", self._store)      # (cleared inside a capture that has read them)
-        self._store = {}                 # a NEW dict: per-parameter memos (prep_linear) compare its identity
-        self._tables.clear()
-
-
-PREP = _Prepared()
-
-
-class _ZeroArena:
-    """Zero-initialised f32 scratch for gradient accumulation targets (the `_acc` kernels add into
-    their output).  One big buffer is cleared with ONE fill per step instead of one fill launch per
-    gradient tensor (~1300 per step).  Slices stay valid until the next `recycle()`, which the
-    optimizer's zero_grad() calls once the gradients have been consumed; until the first recycle()
-    the arena is off and `zeros()` falls back to torch.zeros."""
-
-    def __init__(self):
-        self.buf = None
-        self.off = 0
-        self.high = 0
-        self.active = False
-        self.extra = []
-        self.cap = 0
-
-    def recycle(self, device):
-        device = torch.device(device)
-        need = max(self.high, 1 << 20)
-        if self.buf is None or self.buf.device != device or self.buf.numel() < need:
-            if self.buf is not None:
-                capture.hold_or_ask("gradient arena", self.buf)     # (outgrown inside a capture that wrote slices of it)
-            self.buf = torch.zeros(int(need * 1.25), dtype=torch.float32, device=device)
-        elif self.off:
-            self.buf[:self.off].zero_()
-        self.off = 0
-        self.high = 0
-        self.extra = []
-        self.active = True
-        self.cap = self.buf.numel()
-
-    def zeros(self, shape, device):
-        # ~800 calls per step: one aten call (as_strided) instead of slice + view, no torch.device() construction
-        nd = len(shape)
-        if nd == 1:
-            n = shape[0]
-            stride = (1,)
-        elif nd == 2:
-            n = shape[0] * shape[1]
-            stride = (shape[1], 1)
-        else:
-            n = 1
-            stride = [1] * nd
-            for i in range(nd - 1, -1, -1):
-                stride[i] = n
-                n *= shape[i]
-        n_al = (n + 63) // 64 * 64           # keep every slice 256-byte aligned
-        self.high += n_al
-        buf = self.buf
-        if not self.active or self.off + n_al > self.cap or (buf.device != device and buf.device != torch.device(device)):
-            return torch.zeros(shape, dtype=torch.float32, device=device)
-        out = buf.as_strided(shape, stride, self.off)
-        self.off += n_al
-        return out
-
-
-ARENA = _ZeroArena()
-
-# what every capture reads, held once per capture: the store generation (each entry's buffers and job operands) and
-# the buffer whose slices a captured backward writes
-capture.provide(lambda: (("prepared operands", PREP._store), ("gradient arena", ARENA.buf)))
+# re-exported for callers; a registry that may be REBOUND (a test swaps prepared.PREP) is read through its own module
+from .arena import ARENA, _ZeroArena, zeros_f32
+from .prepared import (CAT, PREP, STACK, _Job, _Prepared, _VEC, _pad_to, _wkey, prep_conv, prep_linear,
+                       prep_stem)
+from .wgrad import WGRADS, _WgradQueue
 
 # Data-parallel runs: the object that averages finished arena regions across ranks (parallel.GradientReducer),
 # installed by FodDataParallel.forward for the coming backward pass; None otherwise.
@@ -241,460 +56,6 @@ class BackboneCut:
 BACKBONE_CUT = None
 
 
-def zeros_f32(shape, device):
-    return ARENA.zeros(tuple(shape), device)
-
-
-class _WgradQueue:
-    """The SHORT weight gradients of a backward pass (dW = G^T X over at most 512 rows: every Linear on the decoder's
-    query side, ~130 per step) launched together instead of one by one.  None of them is on the critical path of the
-    backward pass -- their results are first read by the gradient norm -- but each is a launch (a ~5 us graph node for
-    ~1 us of work).  A site hands its operands to `tn` / `grouped`; the autograd node returns the still all-zero
-    destination as the gradient, and ONE fod_gemm_tn_multi launch fills every destination when the pass ends (engine
-    callback), before the data-parallel reducer averages a region (parallel.GradientReducer.flush), or before a
-    parameter that already has a pending gradient in this pass is used again (autograd sums the gradients of a shared
-    parameter when the second one arrives: the first must be real by then).  A plain Linear used several times in a pass
-    (the decoder's query_scale, once per layer) does better: its later uses join the FIRST use's job as further
-    (g, x) segments (`chain`) -- the block that owns a tile sums them in queue order and stores once, the autograd
-    node returns no gradient of its own, so there is neither a flush nor a gradient-sum kernel, and the parameter's
-    gradient stays inside the arena (one flat all-reduce in data-parallel runs).
-
-    Not deferred (the site launches at once, as without the queue): eagerly launched steps (see `eager` below),
-    parameters that already hold a .grad (autograd adds
-    the returned tensor to it on arrival), parameters with tensor hooks, operands outside the short kernel's domain,
-    FOD_WGRAD_QUEUE=0, torch's own DistributedDataParallel reducer (it copies gradients into buckets on arrival;
-    parallel.FodDataParallel switches the queue off for it).
-
-    Inside a stream capture the job table is written into a pinned host buffer set aside BEFORE the capture (allocating
-    pinned memory inside one hangs) and copied by a captured memcpy node; host and device side of such a table belong to
-    the capture (native/capture.py).  Without a spare the jobs are launched one by one."""
-
-    SPARE_BYTES = 1 << 18
-
-    def __init__(self):
-        import os
-        self.enabled = os.environ.get("FOD_WGRAD_QUEUE", "1") != "0" and L.knob("FOD_TN_SMALL") != "0"
-        if not hasattr(torch._C, "_current_graph_task_id"):      # (private API: how the end of a backward pass is found)
-            self.enabled = False
-        # the LONG weight gradients (nn.Linear layers applied to more than 512 rows: the encoder, the memory side of
-        # the decoder) wait too and share one fod_gemm_tn_multi_long launch; rows per M-split of that launch
-        # Only while a stream capture records the step (future_od/graph.py -- the product's launch mode): an eagerly
-        # launched step is bound by the launching thread, not by the GPU, and the queue's bookkeeping (~30 us per site)
-        # made it 5 ms slower (28.7 -> 34.0 ms).  `eager` = True (FOD_WGRAD_QUEUE_EAGER=1; tests, bench.py's profiling
-        # leg) queues there too.
-        self.eager = os.environ.get("FOD_WGRAD_QUEUE_EAGER", "0") == "1"
-        self.long_enabled = os.environ.get("FOD_WGRAD_QUEUE_LONG", "1") != "0"
-        self.long_rows = int(os.environ.get("FOD_WGRAD_LONG_ROWS", "2048"))
-        self.long_jobs = []
-        self._plans = {}
-        self._maps = {}
-        self.jobs = []
-        self.members = {}            # index into jobs -> further (G, X, M) contributions to that job's outputs
-        self.keep = []
-        self.serial = 0              # flushes so far: a job index is only meaningful within one
-        self.task = -1               # autograd graph task whose end-of-pass callback is installed
-        self.epoch = 1
-        self._tables = {}
-        self._spares = []
-        self.hold = False            # tests: collect jobs outside a backward pass until flush() is called
-        self.launches = 0            # multi launches / jobs they carried (tests, bench diagnostics)
-        self.carried = 0
-
-    # -- sites
-    def site(self, params):
-        """A backward node about to produce the gradients of `params`: True if its short weight gradients may wait."""
-        if not self.enabled or not (self.eager or torch.cuda.is_current_stream_capturing()):
-            return False
-        ok = True
-        for p in params:
-            if p is None:
-                continue
-            if not p.is_leaf:          # its gradient is read by further backward nodes as soon as it is returned
-                ok = False
-            elif p.__dict__.get("_fod_wq") == self.epoch:
-                self.flush()           # used again in this pass: the gradient handed out earlier must be real now
-                ok = False
-            elif (p.grad is not None or p._backward_hooks
-                  or getattr(p, "_post_accumulate_grad_hooks", None)):
-                ok = False
-        if ok:
-            for p in params:
-                if p is not None:
-                    p._fod_wq = self.epoch
-        return ok
-
-    @staticmethod
-    def _fits(g, x, dw, db, M, N1, K2, ldg, ldx):
-        if g.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or not g.is_cuda or M > 512 or M < 1:
-            return False
-        if N1 % 8 or K2 % 8 or ldg % 8 or ldx % 8 or (g.data_ptr() | x.data_ptr() | dw.data_ptr()) % 16:
-            return False
-        if ((N1 + 63) // 64) * ((K2 + 63) // 64) > 256 or not dw.is_contiguous():
-            return False
-        return db is None or db.is_contiguous()
-
-    @staticmethod
-    def _fits_long(g, x, dw, db, M, N1, K2):
-        if g.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or not g.is_cuda:
-            return False
-        if not (g.is_contiguous() and x.is_contiguous() and dw.is_contiguous() and (db is None or db.is_contiguous())):
-            return False
-        if N1 % 8 or K2 % 8 or (g.data_ptr() | x.data_ptr() | dw.data_ptr()) % 16:
-            return False
-        return 2 * M * max(N1, K2) < 0xFFFFFF00 and 4 * N1 * K2 < 0x7FFFFF00
-
-    def tn(self, ok, g, x, dw, db, owner=None):
-        """dw [N1, K2] = g [M, N1]^T x [M, K2], db [N1] = column sums of g (dw, db all-zero f32).  `owner`: the weight
-        parameter, if further uses of it in this pass may add to this job (`chain`)."""
-        N1, K2 = g.shape[-1], x.shape[-1]
-        M = g.numel() // N1
-        if ok and M > 512 and self.long_enabled and self._fits_long(g, x, dw, db, M, N1, K2):
-            return self._push((g.data_ptr(), x.data_ptr(), dw.data_ptr(), 0 if db is None else db.data_ptr(), N1, K2, K2,
-                               M, N1, K2, 0, 0, 0), g, x, dw, db, long=True)
-        if not (ok and g.is_contiguous() and x.is_contiguous() and self._fits(g, x, dw, db, M, N1, K2, N1, K2)):
-            return ops.gemm_tn_acc(g, x, dw, colsum=db, zeroed=True)
-        self._push((g.data_ptr(), x.data_ptr(), dw.data_ptr(), 0 if db is None else db.data_ptr(), N1, K2, K2,
-                    M, N1, K2, 0, 0, 0), g, x, dw, db)
-        if owner is not None and self.jobs:
-            owner._fod_wq_job = (self.epoch, self.serial, len(self.jobs) - 1)
-
-    def chain(self, owner, want_db, g, x):
-        """A FURTHER use of `owner` (a weight whose gradient job of this pass is still waiting): its g^T x -- and g's
-        column sums -- are added inside that job (summed in queue order by the block that owns the tile, one store).
-        True: done, the caller returns no gradient for the parameter (autograd would add a second tensor with a kernel
-        of its own, and could not, the first one being unfinished).  False: not possible, proceed as usual."""
-        rec = owner.__dict__.get("_fod_wq_job") if self.enabled else None
-        if rec is None or rec[0] != self.epoch or rec[1] != self.serial or rec[2] >= len(self.jobs):
-            return False
-        head = self.jobs[rec[2]]
-        N1, K2 = g.shape[-1], x.shape[-1]
-        M = g.numel() // N1
-        if (head[8], head[9]) != (N1, K2) or head[11] != 0 or (head[3] != 0) != bool(want_db):
-            return False
-        if not (g.is_contiguous() and x.is_contiguous() and g.dtype == torch.bfloat16 and x.dtype == torch.bfloat16
-                and 1 <= M <= 512 and (g.data_ptr() | x.data_ptr()) % 16 == 0):
-            return False
-        self.members.setdefault(rec[2], []).append((g.data_ptr(), x.data_ptr(), 0, 0, N1, K2, K2, M, N1, K2, 1, 0, 0))
-        self.keep.append((g, x, None, None))
-        return True
-
-    def grouped(self, ok, g, x, dw, db):
-        """g [P, rows, D] (P output gradients, each block contiguous), x [rows, K] -> dw [P*D, K], db [P*D]."""
-        P, rows, D = g.shape
-        K = x.shape[-1]
-        if not (ok and D % 64 == 0 and g.is_contiguous() and x.is_contiguous()
-                and self._fits(g, x, dw, db, rows, P * D, K, D, K)):
-            return ops.group_linear_wgrad(g, x, dw, db, zeroed=True)
-        self._push((g.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), D, K, K, rows, P * D, K, 0, D, rows * D),
-                   g, x, dw, db)
-
-    def _push(self, job, g, x, dw, db, long=False):
-        task = torch._C._current_graph_task_id()
-        if task != self.task and (self.jobs or self.long_jobs):    # left behind by a backward pass that raised
-            self.jobs, self.long_jobs, self.keep, self.members = [], [], [], {}
-            self.serial += 1
-        (self.long_jobs if long else self.jobs).append(job)
-        # detach(): a second handle on the same memory -- the gradient tensor itself must stay singly referenced, or
-        # autograd copies it instead of adopting it as .grad
-        self.keep.append((g, x, dw.detach(), None if db is None else db.detach()))
-        if task < 0:                     # not inside a backward pass (a backward function called directly)
-            self.task = -1
-            if not self.hold:
-                self.flush()
-        elif task != self.task:
-            self.task = task
-            torch.autograd.Variable._execution_engine.queue_callback(self._end_of_pass)
-
-    def _end_of_pass(self):
-        self.task = -1
-        self.epoch += 1
-        self.flush()
-
-    # -- launch
-    # A table = the job array (pointers: rebuilt per flush, one numpy call) + the block maps, which depend on the jobs'
-    # SHAPES only and are cached per shape list (building them is milliseconds of Python; eagerly launched steps, whose
-    # activation addresses differ from step to step, would pay that every time).
-    _JOB_DTYPE = None
-
-    @classmethod
-    def _job_array(cls, rows):
-        import ctypes as C
-        import numpy as np
-        if cls._JOB_DTYPE is None:
-            cls._JOB_DTYPE = np.dtype([(n, np.uint64 if t is C.c_void_p else (np.int64 if t is C.c_long else np.int32))
-                                       for n, t in L.TnJob._fields_])
-            assert cls._JOB_DTYPE.itemsize == C.sizeof(L.TnJob)
-        head = np.array(rows, dtype=cls._JOB_DTYPE).view(np.uint8)
-        pad = (-head.size) % 16
-        return head if pad == 0 else np.concatenate([head, np.zeros(pad, np.uint8)])
-
-    def _pack(self, jobs, members):
-        import numpy as np
-        key = tuple((j[7], j[8], j[9], tuple(m[7] for m in members.get(i, ()))) for i, j in enumerate(jobs))
-        cached = self._maps.get(key)
-        if cached is None:
-            rows = lambda i: jobs[i][7] + sum(m[7] for m in members.get(i, ()))
-            order = sorted(range(len(jobs)), key=lambda i: -rows(i))             # long reductions first
-            bj, bt, slot = [], [], 0
-            for i in order:
-                j = jobs[i]
-                tiles = ((j[8] + 63) // 64) * ((j[9] + 63) // 64)
-                bj.extend([slot] * tiles)
-                bt.extend(range(tiles))
-                slot += 1 + len(members.get(i, ()))
-            if len(self._maps) > 64:
-                self._maps.clear()
-            cached = self._maps[key] = (order, np.asarray(bj + bt, dtype=np.int32).view(np.uint8), len(bj))
-        order, maps, nblocks = cached
-        table = []
-        for i in order:
-            more = members.get(i, ())
-            for e, n in [(jobs[i], len(more))] + [(m, 0) for m in more]:
-                table.append(e[:12] + (n, e[12], 0, 0))
-        head = self._job_array(table)
-        return np.concatenate([head, maps]), head.size, nblocks
-
-    def _long_plan(self, M, det):
-        """(rows per M-split, M-splits) of a long job.  Deterministic mode keeps one partial result per split in scratch
-        of bounded size (include/fod.h: FOD_TN_MULTI_DET_WS_BYTES): at most L.TN_DET_MAX_SPLITS longer splits."""
-        import ctypes as C
-        key = ("det", M) if det else M
-        plan = self._plans.get(key)
-        if plan is None:
-            rows = max(self.long_rows, -(-M // L.TN_DET_MAX_SPLITS)) if det else self.long_rows
-            mps, ns = C.c_int(), C.c_int()
-            L.call("fod_tn_plan_long", M, rows, C.addressof(mps), C.addressof(ns))
-            plan = self._plans[key] = (mps.value, ns.value)
-        return plan
-
-    def _det_floats(self, job):
-        """Scratch floats of a long job in a deterministic launch: one [N1 x K2 (+ N1)] partial per M-split."""
-        ns = self._long_plan(job[7], True)[1]
-        return ns * (job[8] * job[9] + (job[8] if job[3] else 0)) if ns > 1 else 0
-
-    def det_groups(self, jobs):
-        """The long jobs of a flush cut into launches whose partial results fit the deterministic scratch (launches of
-        one stream are ordered: they share it)."""
-        cap = L.LIB.fod_workspace_bytes(L.WS_TN_MULTI_DET) // 4
-        groups, floats = [[]], 0
-        for j in jobs:
-            need = self._det_floats(j)
-            if need > cap:
-                raise L.FodError(f"deterministic mode: a {j[8]} x {j[9]} weight gradient needs {4 * need} bytes of scratch, "
-                                 f"more than fod_workspace_bytes(WS_TN_MULTI_DET) = {4 * cap}")
-            if groups[-1] and floats + need > cap:
-                groups.append([])
-                floats = 0
-            groups[-1].append(j)
-            floats += need
-        return groups
-
-    def _pack_long(self, jobs, det=False):
-        """Table + block maps of a fod_gemm_tn_multi_long launch.  The blocks of one M-split of a job re-read the same
-        rows of G and X: they go to ONE XCD (block ids congruent mod 8 share an L2), splits dealt round-robin; idle
-        blocks (job -1) pad the shorter XCD queues.  det: the plan of deterministic mode, and behind the maps one i64
-        per job (table order): where in the scratch its partial results start (floats)."""
-        import numpy as np
-        key = ("long-det" if det else "long",) + tuple((j[7], j[8], j[9]) + ((j[3] != 0,) if det else ()) for j in jobs)
-        cached = self._maps.get(key)
-        if cached is None:
-            order = sorted(range(len(jobs)), key=lambda i: -jobs[i][7] * jobs[i][8] * jobs[i][9])
-            plans = []
-            queues = [[] for _ in range(8)]
-            turn = 0
-            for slot, i in enumerate(order):
-                j = jobs[i]
-                plan = self._long_plan(j[7], det)
-                plans.append(plan)
-                ntile = ((j[8] + 127) // 128) * ((j[9] + 127) // 128)
-                for sp in range(plan[1]):
-                    queues[turn % 8].append((slot, sp * ntile, ntile))
-                    turn += 1
-            depth = max(sum(r[2] for r in q) for q in queues)
-            bj = np.full((depth, 8), -1, dtype=np.int32)
-            bl = np.zeros((depth, 8), dtype=np.int32)
-            for xcd, q in enumerate(queues):
-                at = 0
-                for slot, first, ntile in q:
-                    bj[at:at + ntile, xcd] = slot
-                    bl[at:at + ntile, xcd] = np.arange(first, first + ntile, dtype=np.int32)
-                    at += ntile
-            maps = np.concatenate([bj.reshape(-1), bl.reshape(-1)]).view(np.uint8)
-            part_floats = 0
-            if det:
-                offs = []
-                for i in order:
-                    offs.append(part_floats)
-                    part_floats += self._det_floats(jobs[i])
-                maps = np.concatenate([maps, np.asarray(offs, dtype=np.int64).view(np.uint8)])
-            if len(self._maps) > 64:
-                self._maps.clear()
-            cached = self._maps[key] = (order, plans, maps, depth * 8, part_floats)
-        order, plans, maps, nblocks, part_floats = cached
-        head = self._job_array([jobs[i][:12] + (0, jobs[i][12]) + plans[k] for k, i in enumerate(order)])
-        raw = np.concatenate([head, maps])
-        return (raw, head.size, nblocks, part_floats) if det else (raw, head.size, nblocks)
-
-    def _top_up(self, device):
-        while len(self._spares) < 8:
-            self._spares.append((torch.empty(self.SPARE_BYTES, dtype=torch.uint8).pin_memory(),
-                                 torch.empty(self.SPARE_BYTES, dtype=torch.uint8, device=device)))
-
-    def prepare(self, device):
-        """Set aside the capture-time tables (call outside a capture; future_od/graph.py does before it captures)."""
-        if self.enabled and torch.device(device).type == "cuda":
-            self._top_up(device)
-
-    def flush(self):
-        jobs, long_jobs = self.jobs, self.long_jobs
-        if not jobs and not long_jobs:
-            return
-        keep, members = self.keep, self.members
-        self.jobs, self.long_jobs, self.keep, self.members = [], [], [], {}
-        self.serial += 1
-        dev = keep[0][0].device
-        if jobs:
-            self._launch("fod_gemm_tn_multi", jobs, members, dev, keep)
-        if long_jobs and ops.is_deterministic():
-            for group in self.det_groups(long_jobs):
-                self._launch("fod_gemm_tn_multi_long_det", group, {}, dev, keep)
-        elif long_jobs:
-            self._launch("fod_gemm_tn_multi_long", long_jobs, {}, dev, keep)
-
-    def _launch(self, entry, jobs, members, dev, keep):
-        det = entry == "fod_gemm_tn_multi_long_det"
-        long = det or entry == "fod_gemm_tn_multi_long"
-        sig = (entry, tuple(jobs), tuple((i, tuple(m)) for i, m in sorted(members.items())))
-        tab = self._tables.get(sig)
-        if tab is None:
-            part_floats = 0
-            if det:
-                raw, off, nblocks, part_floats = self._pack_long(jobs, det=True)
-            else:
-                raw, off, nblocks = self._pack_long(jobs) if long else self._pack(jobs, members)
-            if torch.cuda.is_current_stream_capturing():
-                if not self._spares or raw.size > self.SPARE_BYTES or self._spares[-1][1].device != dev:
-                    return self._one_by_one(jobs, members, long)
-                pin, table = self._spares.pop()
-                capture.hold_or_ask("weight-gradient table", (pin, table))     # the graph reads both at every replay
-                pin[:raw.size].copy_(torch.from_numpy(raw))
-                table[:raw.size].copy_(pin[:raw.size], non_blocking=True)
-                tab = (table, off, nblocks, part_floats)
-            else:
-                table = torch.from_numpy(raw).pin_memory().to(dev, non_blocking=True)
-                tab = (table, off, nblocks, part_floats)
-                if len(self._tables) >= 32:
-                    self._tables.clear()
-                self._tables[sig] = tab
-                self._top_up(dev)
-        table, off, nblocks, part_floats = tab
-        base = table.data_ptr()
-        # deterministic: the per-job scratch offsets follow the two block maps; the scratch is the current stream's
-        extra = ((base + off + 8 * nblocks, len(jobs), part_floats) + ops.det_workspace(dev, L.WS_TN_MULTI_DET)) if det else ()
-        L.call(entry, base, base + off, base + off + 4 * nblocks, nblocks, *extra, ops.stream(),
-               work=sum(2.0 * j[7] * j[8] * j[9] for j in jobs)
-               + sum(2.0 * m[7] * m[8] * m[9] for ms in members.values() for m in ms), tag="fod_gemm_tn_acc")
-        self.launches += 1
-        self.carried += len(jobs) + sum(len(m) for m in members.values())
-
-    def _one_by_one(self, jobs, members, long=False):
-        if long:
-            for G, X, dW, cs, ldg, ldx, ldw, M, N1, K2, acc, _sc, _ss in jobs:
-                det = ops.is_deterministic()
-                ws, ws_bytes = ops.tn_workspace(torch.device("cuda", torch.cuda.current_device())) if ops.tn_may_use_partials_ws(M) or det else (None, 0)
-                L.call("fod_gemm_tn_acc_det" if det else "fod_gemm_tn_acc", L.BF16, G, ldg, X, ldx, dW, ldw, M, N1, K2, 0, cs, 1, ws, ws_bytes, ops.stream(),
-                       work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
-            return
-        for i, (G, X, dW, cs, ldg, ldx, ldw, M, N1, K2, acc, seg_cols, seg_stride) in enumerate(jobs):
-            L.call("fod_gemm_tn_grouped", L.BF16, G, ldg, seg_cols, seg_stride, X, ldx, dW, ldw, M, N1, K2, cs,
-                   acc, ops.stream(), work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
-            for m in members.get(i, ()):             # stream-ordered after the head: plain read-modify-write is safe
-                L.call("fod_gemm_tn_grouped", L.BF16, m[0], m[4], 0, 0, m[1], m[5], dW, ldw, m[7], N1, K2, cs, 1,
-                       ops.stream(), work=2.0 * m[7] * N1 * K2, tag="fod_gemm_tn_acc")
-
-
-WGRADS = _WgradQueue()
-
-
-def _pad_to(n, v):
-    return (n + v - 1) // v * v
-
-
-def _wkey(p, kind, dtype, extra=()):
-    return (p.data_ptr(), tuple(p.shape), tuple(p.stride()), kind, dtype) + tuple(extra)
-
-
-def prep_linear(weight, dtype, transposed):
-    """weight [N,K] f32 -> [Np,K] (rows zero-padded to the vector width) or its transpose [K,Np]."""
-    # fast path (~270 calls per step): the registry entry is remembered on the parameter object itself
-    memo = weight.__dict__.get("_fod_prep")
-    if memo is not None:
-        e = memo.get((transposed, dtype))
-        if (e is not None and e[0] is PREP._store and e[2] == weight.data_ptr()
-                and (e[1].epoch == PREP.epoch or e[1].epoch == -2) and e[1].vers == (weight._version,)):
-            return e[1].value
-    N, K = weight.shape
-    v = _VEC[dtype]
-    assert K % v == 0, f"Linear in_features {K} must be a multiple of {v} (pad the input)"
-    Np = _pad_to(N, v)
-    w = weight.detach()
-    sn, sk = w.stride()
-
-    def build():
-        if not transposed:   # dst[1][n][k], rows n >= N zero
-            out = torch.empty((Np, K), dtype=dtype, device=w.device)
-            return out, [_Job(w, out, (1, Np, K), (0, sn, sk), valid1=N)]
-        out = torch.empty((K, Np), dtype=dtype, device=w.device)      # dst[1][k][n] = w[n][k], columns n >= N zero
-        return out, [_Job(w, out, (1, K, Np), (0, sk, sn), valid2=N)]
-
-    key = _wkey(weight, "lin_t" if transposed else "lin", dtype)
-    value = PREP.get(key, [weight], build)
-    if weight.__dict__.get("_fod_prep") is None:
-        try:
-            weight._fod_prep = {}
-        except Exception:            # not an attribute-capable tensor (should not happen for Parameters)
-            return value
-    weight._fod_prep[(transposed, dtype)] = (PREP._store, PREP._store[key], weight.data_ptr())
-    return value
-
-
-def prep_conv(weight, dtype, scale, transposed, cin_pad=None):
-    """OIHW f32 (any strides) -> [Cout][kh*kw][Cin_p] * scale[co]  or  [Cin][kh*kw][Cout] * scale[co]."""
-    co, ci, kh, kw = weight.shape
-    s_co, s_ci, s_kh, s_kw = weight.stride()
-    assert s_kh == kw * s_kw, "conv weight must have a contiguous tap plane"
-    cp = ci if cin_pad is None else cin_pad
-    w = weight.detach()
-
-    def build():
-        if not transposed:
-            out = torch.empty((co, kh * kw, cp), dtype=dtype, device=w.device)
-            return out, [_Job(w, out, (co, kh * kw, cp), (s_co, s_kw, s_ci), valid2=ci, scale=scale,
-                              axis=0 if scale is not None else -1)]
-        out = torch.empty((ci, kh * kw, co), dtype=dtype, device=w.device)
-        return out, [_Job(w, out, (ci, kh * kw, co), (s_ci, s_kw, s_co), scale=scale,
-                          axis=2 if scale is not None else -1)]
-
-    tag = ("conv_t" if transposed else "conv") + ("_s" if scale is not None else "")
-    return PREP.get(_wkey(weight, tag, dtype, (cp, 0 if scale is None else scale.data_ptr())), [weight], build)
-
-
-def prep_stem(weight, dtype, scale7):
-    """Stem weight OIHW [Cout,3,7,7] f32 -> [Cout][7 tap rows][8 pixels][4 channels] * scale (zeros for pixel 7 /
-    channel 3): the k order of fod_conv_stem_fwd.  `scale7` = the frozen-BN scale repeated per tap row [Cout*7]."""
-    co, ci, kh, kw = weight.shape
-    s_co, s_ci, s_kh, s_kw = weight.stride()
-    assert (ci, kh, kw) == (3, 7, 7) and s_co == kh * s_kh, "stem weight: expected [Cout,3,7,7] with dense tap rows"
-    w = weight.detach()
-
-    def build():
-        out = torch.empty((co, 7, 8, 4), dtype=dtype, device=w.device)
-        return out, [_Job(w, out, (co * 7, 8, 4), (s_kh, s_kw, s_ci), valid1=7, valid2=3, scale=scale7,
-                          axis=0 if scale7 is not None else -1)]
-
-    return PREP.get(_wkey(weight, "stem", dtype, (0 if scale7 is None else scale7.data_ptr(),)), [weight], build)
-
-
 def cast(t, dtype, pad_cols=None):
     """[rows, cols] tensor -> dtype, optionally zero-padding the last dim."""
     cols = t.shape[-1]
@@ -702,6 +63,29 @@ def cast(t, dtype, pad_cols=None):
     t = t.contiguous()
     pc = cols if pad_cols is None else pad_cols
     return ops.permute3_cast(t, dtype, (1, rows, pc), (0, cols, 1), valid2=cols).view(*t.shape[:-1], pc)
+
+
+def _grad_rows(dy, cols, dtype):
+    """An incoming gradient as [rows, cols] in the compute dtype."""
+    g = dy.contiguous().view(-1, cols)
+    return g if g.dtype == dtype else cast(g, dtype)
+
+
+def _param_grads(weight, bias, g, x, need_w, need_b, shared):
+    """(dw, db) of y = x W^T + b from g = dy [rows, N] and x [rows, K]: the weight gradient through the queue, the bias
+    gradient from the same pass.  `shared`: the layer may be used several times in a backward pass; a further use is
+    summed inside the first use's job (WGRADS.chain) and gets (None, None)."""
+    want_db = bias is not None and need_b
+    if shared and need_w and WGRADS.chain(weight, want_db, g, x):
+        return None, None
+    db = zeros_f32((g.shape[-1],), x.device) if want_db else None
+    dw = None
+    if need_w:
+        dw = zeros_f32((g.shape[-1], x.shape[-1]), x.device)
+        WGRADS.tn(WGRADS.site((weight, bias)), g, x, dw, db, owner=weight if shared else None)
+    elif want_db:
+        ops.colsum_acc(g, db)
+    return dw, db
 
 
 # ------------------------------------------------------------------------------------------------
@@ -737,22 +121,12 @@ class LinearFn(Function):
         if ctx.relu:
             assert Np == N
             g = ops.eltwise(L.EW_RELU_MASK, g, y.view(-1, N))
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm_nt(g, prep_linear(weight, dtype, True)).view(x.shape)
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] and WGRADS.chain(weight, want_db, g, x.view(-1, K)):
-            return dx, None, None, None, None        # a further use of a shared layer: summed inside the first use's job
-        dbp = zeros_f32((Np,), x.device) if want_db else None
-        if ctx.needs_input_grad[1]:
-            dwp = zeros_f32((Np, K), x.device)
-            # bias gradient from the same pass
-            WGRADS.tn(WGRADS.site((weight, ctx.bias)), g, x.view(-1, K), dwp, dbp, owner=weight)
-            dw = dwp[:N] if Np != N else dwp
-        elif want_db:
-            ops.colsum_acc(g, dbp)
-        if want_db:
-            db = dbp[:N] if Np != N else dbp
+        dw, db = _param_grads(weight, ctx.bias, g, x.view(-1, K), ctx.needs_input_grad[1], ctx.needs_input_grad[2], True)
+        if Np != N:                                  # the gradients of the padded rows stay behind
+            dw, db = (None if dw is None else dw[:N]), (None if db is None else db[:N])
         return dx, dw, db, None, None
 
 
@@ -789,28 +163,18 @@ class LinearKeepFn(Function):
         dtype = x.dtype
         N, K = weight.shape
         assert N % _VEC[dtype] == 0
-        g = dy.contiguous().view(-1, N)
-        if g.dtype != dtype:
-            g = cast(g, dtype)
+        g = _grad_rows(dy, N, dtype)
         if ctx.mask_here:
             g = ops.eltwise(L.EW_RELU_MASK, g, y.view(-1, N))
-        dx = dw = db = None
+        dx = None
         if ctx.needs_input_grad[0]:
-            res = None if dkeep is None else dkeep.contiguous().view(-1, K)
-            if res is not None and res.dtype != dtype:
-                res = cast(res, dtype)
+            res = None if dkeep is None else _grad_rows(dkeep, K, dtype)
             dx = ops.gemm_nt(g, prep_linear(weight, dtype, True), residual=res).view(x.shape)
-        want_db = ctx.has_bias and ctx.needs_input_grad[2]
-        dbp = zeros_f32((N,), x.device) if want_db else None
-        if ctx.needs_input_grad[1]:
-            dw = zeros_f32((N, K), x.device)
-            WGRADS.tn(WGRADS.site((weight, ctx.bias)), g, x.view(-1, K), dw, dbp)
-        elif want_db:
-            ops.colsum_acc(g, dbp)
-        return dx, dw, dbp, None, None, None
+        dw, db = _param_grads(weight, ctx.bias, g, x.view(-1, K), ctx.needs_input_grad[1], ctx.needs_input_grad[2], False)
+        return dx, dw, db, None, None, None
 
 
-_LINEAR_KEEP = __import__("os").environ.get("FOD_LINEAR_KEEP", "1") != "0"       # "0": two autograd consumers (experiments)
+_LINEAR_KEEP = os.environ.get("FOD_LINEAR_KEEP", "1") != "0"       # "0": two autograd consumers (experiments)
 
 
 def linear_keep(x, weight, bias=None, relu=False, grad_masked=False, precomputed=None):
@@ -874,23 +238,6 @@ class MulFn(Function):
         return da, db, None
 
 
-def _queued_linear_wgrad(weight, bias, g, x, need_w, need_b):
-    """(dw, db) of a Linear layer as LinearFn.backward produces them: through the weight-gradient queue, a further use of a
-    shared layer inside the first use's job ((None, None) then)."""
-    N, K = weight.shape
-    want_db = bias is not None and need_b
-    if need_w and WGRADS.chain(weight, want_db, g, x):
-        return None, None
-    db = zeros_f32((N,), x.device) if want_db else None
-    dw = None
-    if need_w:
-        dw = zeros_f32((N, K), x.device)
-        WGRADS.tn(WGRADS.site((weight, bias)), g, x, dw, db, owner=weight)
-    elif want_db:
-        ops.colsum_acc(g, db)
-    return dw, db
-
-
 class TableGradAcc:
     """One f32 accumulation buffer for the gradient of a table that several Mlp2MulFn nodes multiply by (the decoder
     layers' query_scale(x) * sine embedding): every node's backward launch adds into it (atomics on the default path, row-ordered sums in deterministic mode); the node that runs
@@ -933,14 +280,12 @@ class Mlp2MulFn(Function):
         x2, h, q, table = ctx.saved_tensors
         w1, b1, w2, b2 = ctx.params
         D = x2.shape[-1]
-        g = g.contiguous().view(-1, D)
-        if g.dtype != x2.dtype:
-            g = cast(g, x2.dtype)
+        g = _grad_rows(g, D, x2.dtype)
         acc = ctx.acc if ctx.acc is not None else TableGradAcc()
         buf = acc.get(tuple(table.shape), x2.device)
         ds, dh, dx = ops.mlp2_mul_bwd(g, table, q, h, prep_linear(w2, x2.dtype, True), prep_linear(w1, x2.dtype, True), buf)
-        dw2, db2 = _queued_linear_wgrad(w2, b2, ds, h, ctx.needs_input_grad[4], ctx.needs_input_grad[5])
-        dw1, db1 = _queued_linear_wgrad(w1, b1, dh, x2, ctx.needs_input_grad[2], ctx.needs_input_grad[3])
+        dw2, db2 = _param_grads(w2, b2, ds, h, ctx.needs_input_grad[4], ctx.needs_input_grad[5], True)
+        dw1, db1 = _param_grads(w1, b1, dh, x2, ctx.needs_input_grad[2], ctx.needs_input_grad[3], True)
         dtable = None
         if ctx.needs_input_grad[1] and (ctx.acc is None or ctx.hands_on):
             dtable = cast(acc.take(), table.dtype).view(table.shape)
@@ -967,12 +312,8 @@ def mlp2_mul(x, mlp, table, acc=None, hands_on=True):
 
 def _sum_periodic(g, mod):
     """[rows, cols] -> [mod, cols]: sum of the rows congruent modulo `mod` (rows/mod is tiny)."""
-    cols = g.shape[-1]
-    parts = g.view(-1, mod, cols)
-    acc = parts[0]
-    for i in range(1, parts.shape[0]):
-        acc = ops.eltwise(L.EW_ADD, acc.contiguous(), parts[i].contiguous())
-    return acc.contiguous()
+    parts = g.view(-1, mod, g.shape[-1])
+    return _sum_leading(parts, parts.shape[0])
 
 
 def mul(a, b, b_row_mod=0):
@@ -1136,25 +477,16 @@ class LinearAddNormFn(Function):
         dg, dbeta = zeros_f32((N,), dev), zeros_f32((N,), dev)
         da = None
         rows = s.numel() // N
-        dw2 = db2 = None
-        pre_g = pre_wt = None
+        dw2 = db2 = pre_g = pre_wt = None
         if ctx.then is not None and dnxt is not None:
             # the THEN projection's own gradients: its weight / bias through the queue (dq^T y), its input gradient
             # dq . then_w joins dy inside the fused launch below (or through a GEMM epilogue on the fallback path)
             then_w, then_b = ctx.then
             y = ctx.saved_tensors[5]
-            pre_g = dnxt.contiguous().view(-1, N)
-            if pre_g.dtype != a.dtype:
-                pre_g = cast(pre_g, a.dtype)
+            pre_g = _grad_rows(dnxt, N, a.dtype)
             pre_wt = prep_linear(then_w, a.dtype, True)
-            want_db2 = then_b is not None and ctx.needs_input_grad[8]
-            if want_db2:
-                db2 = zeros_f32((N,), dev)
-            if ctx.needs_input_grad[7]:
-                dw2 = zeros_f32((N, N), dev)
-                WGRADS.tn(WGRADS.site((then_w, then_b)), pre_g, y.view(-1, N), dw2, db2)
-            elif want_db2:
-                ops.colsum_acc(pre_g, db2)
+            dw2, db2 = _param_grads(then_w, then_b, pre_g, y.view(-1, N), ctx.needs_input_grad[7], ctx.needs_input_grad[8],
+                                    False)
         if dy is not None:
             dy = dy.contiguous()
         if (FUSED_LINEAR_NORM and s.dtype == torch.bfloat16 and N == 256 and K == 256 and rows <= FUSED_LINEAR_NORM_ROWS
@@ -1173,15 +505,7 @@ class LinearAddNormFn(Function):
             if ctx.needs_input_grad[0]:
                 da = ops.gemm_nt(g, prep_linear(weight, a.dtype, True),
                                  relu_mask=a.view(-1, K) if ctx.a_relu else None).view(a.shape)
-        dw = db = None
-        want_db = ctx.has_bias and ctx.needs_input_grad[3]
-        if want_db:
-            db = zeros_f32((N,), dev)
-        if ctx.needs_input_grad[2]:
-            dw = zeros_f32((N, K), dev)
-            WGRADS.tn(WGRADS.site((weight, ctx.bias)), g, a.view(-1, K), dw, db)
-        elif want_db:
-            ops.colsum_acc(g, db)
+        dw, db = _param_grads(weight, ctx.bias, g, a.view(-1, K), ctx.needs_input_grad[2], ctx.needs_input_grad[3], False)
         return da, (dsum if ctx.needs_input_grad[1] else None), dw, db, dg, dbeta, None, dw2, db2
 
 
@@ -1411,9 +735,8 @@ def _strided_ok(t):
 def attention(q1, k1, v, scale, q2=None, k2=None, drop_p=0.0, training=False):
     """`drop_p` (with `training`): dropout on the attention probabilities, as MultiheadAttention(dropout=p)."""
     c = lambda t: None if t is None else (t if _strided_ok(t) else t.contiguous())
-    if training and drop_p > 0.0:
-        return AttentionFn.apply(c(q1), c(k1), c(v), c(q2), c(k2), scale, float(drop_p), DROP_SEEDS.next())
-    return AttentionFn.apply(c(q1), c(k1), c(v), c(q2), c(k2), scale)
+    drop = (float(drop_p), DROP_SEEDS.next()) if training and drop_p > 0.0 else ()
+    return AttentionFn.apply(c(q1), c(k1), c(v), c(q2), c(k2), scale, *drop)
 
 
 def _column_siblings(a, b):
@@ -1440,35 +763,51 @@ class InProjFn(Function):
 
     @staticmethod
     def forward(ctx, xp, src, w, b):
-        D = w.shape[1]
-        dtype = xp.dtype
-        wqk, wv = prep_linear(w[:2 * D], dtype, False), prep_linear(w[2 * D:], dtype, False)
-        qk = ops.gemm_nt(xp, wqk, shift=b[:2 * D]).view(*xp.shape[:-1], 2 * D)
-        v = ops.gemm_nt(src, wv, shift=b[2 * D:]).view(src.shape)
-        ctx.save_for_backward(xp, src)
-        ctx.w, ctx.b = w, b
-        return qk[..., :D], qk[..., D:], v
+        return _in_proj_forward(ctx, xp, src, w, b)
 
     @staticmethod
     def backward(ctx, dq, dk, dv):
-        xp, src = ctx.saved_tensors
-        w, b = ctx.w, ctx.b
-        D = w.shape[1]
-        dtype = xp.dtype
-        rows = xp.numel() // D
-        dqk = _column_siblings(dq, dk)
-        if dqk is None:
-            dqk = torch.cat([dq, dk], dim=-1)
-        dqk = dqk.reshape(rows, 2 * D)
-        dv = dv.contiguous().view(rows, D)
-        dxp = ops.gemm_nt(dqk, prep_linear(w[:2 * D], dtype, True)).view(xp.shape) if ctx.needs_input_grad[0] else None
-        dsrc = ops.gemm_nt(dv, prep_linear(w[2 * D:], dtype, True)).view(src.shape) if ctx.needs_input_grad[1] else None
-        dw = zeros_f32((3 * D, D), xp.device)
-        db = zeros_f32((3 * D,), xp.device)
-        wq = WGRADS.site((w, b))
-        WGRADS.tn(wq, dqk, xp.view(rows, D), dw[:2 * D], db[:2 * D])
-        WGRADS.tn(wq, dv, src.view(rows, D), dw[2 * D:], db[2 * D:])
-        return dxp, dsrc, dw, db
+        return _in_proj_backward(ctx, dq, dk, dv, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+def _in_proj_forward(ctx, xp, src, w, b):
+    """(q, k, v) of the packed projection: q | k = xp W_qk^T, v = src W_v^T."""
+    D = w.shape[1]
+    dtype = xp.dtype
+    wqk, wv = prep_linear(w[:2 * D], dtype, False), prep_linear(w[2 * D:], dtype, False)
+    qk = ops.gemm_nt(xp, wqk, shift=b[:2 * D]).view(*xp.shape[:-1], 2 * D)
+    v = ops.gemm_nt(src, wv, shift=b[2 * D:]).view(src.shape)
+    ctx.save_for_backward(xp, src)
+    ctx.w, ctx.b = w, b
+    return qk[..., :D], qk[..., D:], v
+
+
+def _in_proj_backward(ctx, dq, dk, dv, need_xp, need_src, chained=False, dkeep=None):
+    """(dxp, dsrc, dw, db) of the packed projection q | k = xp W_qk^T, v = src W_v^T.  `chained` (InProjSelfFn, where
+    xp = src + pos): the residual path's gradient `dkeep` rides in the q | k input-gradient GEMM's epilogue and that
+    result in the v one's, so dsrc is the whole gradient of src."""
+    xp, src = ctx.saved_tensors
+    w, b = ctx.w, ctx.b
+    D = w.shape[1]
+    dtype = xp.dtype
+    rows = xp.numel() // D
+    dqk = _column_siblings(dq, dk)
+    if dqk is None:
+        dqk = torch.cat([dq, dk], dim=-1)
+    dqk = dqk.reshape(rows, 2 * D)
+    dv = dv.contiguous().view(rows, D)
+    dxp = dsrc = None
+    if need_xp:
+        res = None if dkeep is None else _grad_rows(dkeep, D, dtype)
+        dxp = ops.gemm_nt(dqk, prep_linear(w[:2 * D], dtype, True), residual=res).view(xp.shape)
+    if need_src:
+        dsrc = ops.gemm_nt(dv, prep_linear(w[2 * D:], dtype, True), residual=dxp if chained else None).view(src.shape)
+    dw = zeros_f32((3 * D, D), xp.device)
+    db = zeros_f32((3 * D,), xp.device)
+    wq = WGRADS.site((w, b))
+    WGRADS.tn(wq, dqk, xp.view(rows, D), dw[:2 * D], db[:2 * D])
+    WGRADS.tn(wq, dv, src.view(rows, D), dw[2 * D:], db[2 * D:])
+    return dxp, dsrc, dw, db
 
 
 def in_proj(xp, src, weight, bias):
@@ -1484,40 +823,13 @@ class InProjSelfFn(Function):
 
     @staticmethod
     def forward(ctx, src, pos, w, b, row_mod):
-        D = w.shape[1]
-        dtype = src.dtype
         xp = ops.eltwise(L.EW_ADD, src, pos, b_row_mod=row_mod)
-        wqk, wv = prep_linear(w[:2 * D], dtype, False), prep_linear(w[2 * D:], dtype, False)
-        qk = ops.gemm_nt(xp, wqk, shift=b[:2 * D]).view(*xp.shape[:-1], 2 * D)
-        v = ops.gemm_nt(src, wv, shift=b[2 * D:]).view(src.shape)
-        ctx.save_for_backward(xp, src)
-        ctx.w, ctx.b = w, b
-        return src.view_as(src), qk[..., :D], qk[..., D:], v
+        return (src.view_as(src),) + _in_proj_forward(ctx, xp, src, w, b)
 
     @staticmethod
     def backward(ctx, dkeep, dq, dk, dv):
-        xp, src = ctx.saved_tensors
-        w, b = ctx.w, ctx.b
-        D = w.shape[1]
-        dtype = xp.dtype
-        rows = xp.numel() // D
-        dqk = _column_siblings(dq, dk)
-        if dqk is None:
-            dqk = torch.cat([dq, dk], dim=-1)
-        dqk = dqk.reshape(rows, 2 * D)
-        dv = dv.contiguous().view(rows, D)
-        dsrc = None
-        if ctx.needs_input_grad[0]:
-            res = None if dkeep is None else dkeep.contiguous().view(rows, D)
-            if res is not None and res.dtype != dtype:
-                res = cast(res, dtype)
-            dxp = ops.gemm_nt(dqk, prep_linear(w[:2 * D], dtype, True), residual=res)
-            dsrc = ops.gemm_nt(dv, prep_linear(w[2 * D:], dtype, True), residual=dxp).view(src.shape)
-        dw = zeros_f32((3 * D, D), xp.device)
-        db = zeros_f32((3 * D,), xp.device)
-        wq = WGRADS.site((w, b))
-        WGRADS.tn(wq, dqk, xp.view(rows, D), dw[:2 * D], db[:2 * D])
-        WGRADS.tn(wq, dv, src.view(rows, D), dw[2 * D:], db[2 * D:])
+        need = ctx.needs_input_grad[0]
+        _, dsrc, dw, db = _in_proj_backward(ctx, dq, dk, dv, need, need, chained=True, dkeep=dkeep)
         return dsrc, None, dw, db, None
 
 
@@ -1656,34 +968,6 @@ def cast_ad(x, dtype, pad_cols=None):
 # pairs, and each cross-attention reads / writes its [*, D] column slot of those wide buffers through
 # the attention kernels' stride arguments.
 # ------------------------------------------------------------------------------------------------
-class _CatCache:
-    """P same-shaped Linear layers stacked: (wcat [P*D_out, D_in], bcat f32 [P*D_out], wcat_t [D_in, P*D_out])."""
-
-    def get(self, weights, biases, dtype):
-        D_out, D_in = weights[0].shape
-        P = len(weights)
-
-        def build():
-            dev = weights[0].device
-            wcat = torch.empty((P * D_out, D_in), dtype=dtype, device=dev)
-            bcat = torch.empty((P * D_out,), dtype=torch.float32, device=dev)
-            wcat_t = torch.empty((D_in, P * D_out), dtype=dtype, device=dev)
-            jobs = []
-            for i, (w, b) in enumerate(zip(weights, biases)):
-                wd, bd = w.detach(), b.detach()
-                sn, sk = wd.stride()
-                jobs.append(_Job(wd, wcat[i * D_out:(i + 1) * D_out], (1, D_out, D_in), (0, sn, sk)))
-                jobs.append(_Job(bd, bcat[i * D_out:(i + 1) * D_out], (1, 1, D_out), (0, 0, bd.stride(0))))
-                # column block i of the transposed stack: dst[k][i*D_out + n] = w[n][k]
-                jobs.append(_Job(wd, wcat_t[:, i * D_out:(i + 1) * D_out], (1, D_in, D_out), (0, sk, sn),
-                                 dstr=(0, P * D_out)))
-            return (wcat, bcat, wcat_t), jobs
-
-        key = (tuple(w.data_ptr() for w in weights), dtype, "cat")
-        return PREP.get(key, list(weights) + list(biases), build)
-
-
-CAT = _CatCache()
 
 
 class WideLinearFn(Function):
@@ -1758,20 +1042,8 @@ class GroupLinearFn(Function):
         _, _, wcat_t = CAT.get(weights, biases, x.dtype)
         rows = x.numel() // K
         g = _as_segments(gs, rows, D)
-        if g is None:                                # gather the P gradients into the segment layout: ONE launch
-            g = torch.empty((P, rows, D), dtype=x.dtype, device=x.device)
-            dsts, srcs = [], []
-            for p_, gp in enumerate(gs):
-                if gp is None:
-                    g[p_].zero_()
-                else:
-                    dsts.append(g[p_])
-                    srcs.append(gp.reshape(rows, D))
-            if all(t.dtype == x.dtype and t.is_contiguous() for t in srcs):
-                torch._foreach_copy_(dsts, srcs)     # (17 separate copies of 64 KB were 17 graph nodes of ~5 us each)
-            else:
-                for d_, s_ in zip(dsts, srcs):
-                    d_.copy_(s_)
+        if g is None:
+            g = _gather_segments(gs, rows, D, x.dtype, x.device)
         dx = ops.group_linear_dgrad(g, wcat_t, P).view(x.shape) if ctx.needs_input_grad[0] else None
         dw = zeros_f32((P * D, K), x.device)
         db = zeros_f32((P * D,), x.device)
@@ -1800,6 +1072,24 @@ def _as_segments(gs, rows, D):
     return torch.as_strided(g0, (len(gs), rows, D), (step, D, 1))
 
 
+def _gather_segments(gs, rows, D, dtype, device):
+    """The gradients `gs` (None: zero) copied into one new [P, rows, D] tensor -- the segment layout: ONE launch."""
+    g = torch.empty((len(gs), rows, D), dtype=dtype, device=device)
+    dsts, srcs = [], []
+    for p_, gp in enumerate(gs):
+        if gp is None:
+            g[p_].zero_()
+        else:
+            dsts.append(g[p_])
+            srcs.append(gp.reshape(rows, D))
+    if all(t.dtype == dtype and t.is_contiguous() for t in srcs):
+        torch._foreach_copy_(dsts, srcs)     # (17 separate copies of 64 KB were 17 graph nodes of ~5 us each)
+    else:
+        for d_, s_ in zip(dsts, srcs):
+            d_.copy_(s_)
+    return g
+
+
 # "0": the self-attention's position adds as their own element-wise launches (not in the grouped projection's epilogue)
 GROUP_RESIDUAL = os.environ.get("FOD_GROUP_RESIDUAL", "1") != "0"
 
@@ -1826,25 +1116,6 @@ def group_linear(x, linears, residual=None, res_row_mod=0):
     return out
 
 
-class _StackCache:
-    """P same-length f32 vectors (the LayerNorm weights / biases of P layers) as one [P, D] table, refreshed with the
-    other prepared operands."""
-
-    def get(self, vecs):
-        def build():
-            D = vecs[0].numel()
-            table = torch.empty((len(vecs), D), dtype=torch.float32, device=vecs[0].device)
-            jobs = []
-            for i, v in enumerate(vecs):
-                vd = v.detach()
-                jobs.append(_Job(vd, table[i], (1, 1, D), (0, 0, vd.stride(0))))
-            return (table,), jobs
-
-        key = (tuple(v.data_ptr() for v in vecs), torch.float32, "stack")
-        return PREP.get(key, list(vecs), build)[0]
-
-
-STACK = _StackCache()
 
 # "0": every encoder layer computes its IMU-token block itself (4 GEMMs + 2 norms on [frames, D] rows per layer)
 IMU_BATCHED = os.environ.get("FOD_IMU_BATCHED", "1") != "0"
@@ -1905,19 +1176,7 @@ class ImuBranchFn(Function):
             ctx.queue.flush()                                # the slots handed out as gradients become real
         de = _as_segments(gs, M, D)
         if de is None or de.dtype != dtype:
-            de = torch.empty((P, M, D), dtype=dtype, device=dev)
-            dsts, srcs = [], []
-            for p_, gp in enumerate(gs):
-                if gp is None:
-                    de[p_].zero_()
-                else:
-                    dsts.append(de[p_])
-                    srcs.append(gp.reshape(M, D))
-            if all(s_.dtype == dtype and s_.is_contiguous() for s_ in srcs):
-                torch._foreach_copy_(dsts, srcs)
-            else:
-                for d_, s_ in zip(dsts, srcs):
-                    d_.copy_(s_)
+            de = _gather_segments(gs, M, D, dtype, dev)
 
         def wgrads(ws, bs, g, x):
             """queued weight / bias gradients of P layers with their own inputs: g [P, M, N], x [P, M, K]"""
@@ -1927,6 +1186,7 @@ class ImuBranchFn(Function):
                 WGRADS.tn(WGRADS.site((ws[p_], bs[p_])), g[p_], x[p_], dw[p_ * N:(p_ + 1) * N], db[p_ * N:(p_ + 1) * N])
             return [dw[p_ * N:(p_ + 1) * N] for p_ in range(P)], [db[p_ * N:(p_ + 1) * N] for p_ in range(P)]
 
+        sl = lambda v: [v[p_ * D:(p_ + 1) * D] for p_ in range(P)]
         extra = []
         if use_mlp:
             g1, b1, w0, b0, w3, b3, g2, b2 = groups[4:]
@@ -1943,7 +1203,6 @@ class ImuBranchFn(Function):
             dg1, db1 = zeros_f32((P * D,), dev), zeros_f32((P * D,), dev)
             ds1 = ops.layernorm_bwd(dn1.view(P * M, D), s1, mean1, rstd1, STACK.get(g1), dg1, db1, group_rows=M)
             do = ops.eltwise(L.EW_SCALE, ds1, alpha=2.0).view(P, M, D)       # norm1(o + o): o enters twice
-            sl = lambda v: [v[p_ * D:(p_ + 1) * D] for p_ in range(P)]
             extra = sl(dg1) + sl(db1) + dw0 + db0 + dw3 + db3 + sl(dg2) + sl(db2)
         else:
             do = de
@@ -1952,7 +1211,6 @@ class ImuBranchFn(Function):
         dego = ops.group_linear_dgrad(dt_, CAT.get(wv, bv, dtype)[2], P) if ctx.needs_input_grad[0] else None
         dwv, dbv = zeros_f32((P * D, D), dev), zeros_f32((P * D,), dev)
         WGRADS.grouped(WGRADS.site(tuple(wv) + tuple(bv)), dt_, ego, dwv, dbv)
-        sl = lambda v: [v[p_ * D:(p_ + 1) * D] for p_ in range(P)]
         return (dego, None, None, None) + tuple(sl(dwv) + sl(dbv) + dwo + dbo + extra)
 
 
@@ -2117,8 +1375,6 @@ class HoistedCrossAttnFn(Function):
 
 
 def hoisted_cross_attention(q1, q2, side, layer, image, scale, drop_p=0.0, training=False):
-    if training and drop_p > 0.0:
-        return HoistedCrossAttnFn.apply(q1.contiguous(), q2.contiguous(), side.big[image], side.ks_all, side, layer,
-                                        image, scale, float(drop_p), DROP_SEEDS.next())
+    drop = (float(drop_p), DROP_SEEDS.next()) if training and drop_p > 0.0 else ()
     return HoistedCrossAttnFn.apply(q1.contiguous(), q2.contiguous(), side.big[image], side.ks_all, side, layer,
-                                    image, scale)
+                                    image, scale, *drop)

@@ -39,10 +39,10 @@ class FusedAdamW(torch.optim.Optimizer):
             for p in grp["params"]:
                 if p.grad is not None:
                     p.grad = None
-        from future_od.native import functional as Fn
+        from future_od.native import arena
         for grp in self.param_groups:
             if grp["params"]:
-                Fn.ARENA.recycle(grp["params"][0].device)
+                arena.ARENA.recycle(grp["params"][0].device)
                 break
 
     def _state_for(self, p):
@@ -217,8 +217,8 @@ class FusedAdamW(torch.optim.Optimizer):
                                                 self._dev_step, self._dev_betas))
         # the kernel wrote the parameters through raw pointers (their `_version` did not move): every prepared
         # operand derived from a parameter (compute-dtype / transposed / BN-folded copies) is now out of date
-        from future_od.native import functional as Fn
-        Fn.PREP.mark_stale()
+        from future_od.native import prepared
+        prepared.PREP.mark_stale()
 
     @torch.no_grad()
     def step(self, closure=None):

@@ -11,7 +11,7 @@ NOT used:
     before any byte moves (measured with a one-rank RCCL group: 36.6 -> 41.1 ms/step); its runtime-statistics
     logger additionally blocks the host on CUDA events in the first 10 iterations and every 100th;
   * here every parameter gradient is already a slice of ONE flat fp32 buffer, the zero arena the `_acc`
-    kernels accumulate into (`native/functional.py`), filled in backward execution order: transformer
+    kernels accumulate into (`native/arena.py`), filled in backward execution order: transformer
     (decoder -> encoder), then the backbone sweep layer4 -> layer2.  `GradientReducer` averages that buffer
     in place with a handful of large all-reduces (`ReduceOp.AVG`) on a side stream:
         flush A  when the backbone's backward starts: every transformer gradient is final (~120 MB);
@@ -107,8 +107,8 @@ class GradientReducer:
             # pace -- an in-place flush would average slices that are not final yet and race with those adds.  Then
             # nothing is averaged in place: every gradient goes through the packed path at the end of backward.
             self.accumulating = any(p.grad is not None for p in self.params)
-            from future_od.native import functional as Fn
-            self.start = self.flushed = Fn.ARENA.off if Fn.ARENA.active else 0
+            from future_od.native import arena
+            self.start = self.flushed = arena.ARENA.off if arena.ARENA.active else 0
             torch.autograd.Variable._execution_engine.queue_callback(self.finish)
 
     def _all_reduce(self, t):
@@ -138,8 +138,8 @@ class GradientReducer:
 
     def flush(self, arena, min_elems=1):
         """Average the arena region filled since the last flush, if it holds at least `min_elems` elements."""
-        from future_od.native import functional as Fn
-        Fn.WGRADS.flush()                # weight gradients still waiting for their launch are part of the region
+        from future_od.native import wgrad
+        wgrad.WGRADS.flush()                # weight gradients still waiting for their launch are part of the region
         if not self.enabled or not arena.active or arena.buf is None:
             return
         self.arm()
@@ -183,8 +183,8 @@ class GradientReducer:
         try:
             if not self.enabled:
                 return
-            from future_od.native import functional as Fn
-            self.flush(Fn.ARENA)
+            from future_od.native import arena
+            self.flush(arena.ARENA)
             self._reduce_stragglers()
             if self.comm is not None:
                 torch.cuda.current_stream(self.comm.device).wait_stream(self.comm)
@@ -259,8 +259,8 @@ class FodDataParallel(DistributedDataParallel):
         else:
             super().__init__(module, broadcast_buffers=False, bucket_cap_mb=bucket_cap_mb, find_unused_parameters=False,
                              process_group=process_group)
-            from future_od.native import functional as Fn
-            Fn.WGRADS.enabled = False    # torch's reducer hooks see gradients on arrival: none may be filled in later
+            from future_od.native import wgrad
+            wgrad.WGRADS.enabled = False    # torch's reducer hooks see gradients on arrival: none may be filled in later
         self.require_backward_grad_sync = False          # torch's reducer stays idle (as under no_sync())
         self.grad_reducer = GradientReducer(self.module.parameters(), self.process_group, bucket_cap_mb)
         self._sync_enabled = True

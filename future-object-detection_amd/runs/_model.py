@@ -19,6 +19,7 @@ from future_od.models.paper import (JointEncoder, JointEncoderF2F, JointEncoderS
                                     PositionalEncoder, SeparateEncoder)
 from future_od.models.st_detr import SpatioTemporalDETR, SpatioTemporalDETRArgs
 from future_od.native import functional as Fn
+from future_od.native import prepared
 from future_od.parallel import FodDataParallel
 
 _DTYPES = {"bf16": torch.bfloat16, "bfloat16": torch.bfloat16, "fp32": torch.float32, "float32": torch.float32,
@@ -48,7 +49,7 @@ def _joint_encoder(args, detr_args):
 
 
 def build_model(args, detr_args: SpatioTemporalDETRArgs):
-    Fn.PREP.clear()
+    prepared.PREP.clear()
     num_images = getattr(args, "num_images", 2)
     single = getattr(args, "core", "future_pred") == "single_frame"       # paper.py:488 SingleFrameCore (baseline)
     make_core = (lambda separate_encoder, joint_encoder, **kw: SingleFrameCore(encoder=separate_encoder, **kw)) \

@@ -188,7 +188,7 @@ def test_average_meter_semantics_and_checkpoint_state():
 
 
 def test_weight_gradient_job_tables():
-    """Host side of the queued weight gradients (native/functional.py: WGRADS): the job array built with numpy has the
+    """Host side of the queued weight gradients (native/wgrad.py): the job array built with numpy has the
     layout of the C struct fod_tn_job, every (job, tile) / (job, split, tile) gets exactly one block, chained segments
     follow their head, the blocks of one M-split of a long job sit in ONE XCD column (block index mod 8), idle blocks
     are marked -1, and fod_tn_plan_long cuts M into pieces that are multiples of the kernel's step and cover it."""
@@ -196,17 +196,19 @@ def test_weight_gradient_job_tables():
 
     import numpy as np
 
-    from future_od.native import functional as Fn
     from future_od.native import lib as L
-    q = Fn._WgradQueue()
+    from future_od.native import wgrad as W
+    assert W.Job._fields == tuple(name for name, _ in L.TnJob._fields_)
+    long_rows = W._WgradQueue().long_rows
     size = C.sizeof(L.TnJob)
 
     def job(n, M, N1, K2, seg_cols=0, seg_stride=0):
-        return (1000 * n + 16, 2000 * n + 32, 3000 * n + 48, 4000 * n + 64, N1, K2, K2, M, N1, K2, 0, seg_cols, seg_stride)
+        return W.Job(G=1000 * n + 16, X=2000 * n + 32, dW=3000 * n + 48, colsum=4000 * n + 64, ldg=N1, ldx=K2, ldw=K2,
+                     M=M, N1=N1, K2=K2, accumulate=0, g_seg_cols=seg_cols, g_seg_stride=seg_stride)
 
     jobs = [job(1, 300, 256, 256), job(2, 512, 264, 72), job(3, 7, 8, 2048), job(4, 300, 192, 256, 64, 300 * 64)]
     members = {0: [job(5, 64, 256, 256), job(6, 300, 256, 256)]}
-    raw, off, nblocks = q._pack(jobs, members)
+    raw, off, nblocks, _ = W.short_table(jobs, members)
     njobs = len(jobs) + 2
     assert off == (njobs * size + 15) // 16 * 16 and raw.size == off + 8 * nblocks
     table = (L.TnJob * njobs).from_buffer_copy(raw[:njobs * size].tobytes())
@@ -220,16 +222,16 @@ def test_weight_gradient_job_tables():
         assert sorted(bt[bj == slot].tolist()) == list(range(tiles))
         seen.add(t.G)
         for k in range(t.chain):                            # the segments that add into this job follow it in the table
-            assert table[slot + 1 + k].G in (members[0][0][0], members[0][1][0]) and table[slot + 1 + k].chain == 0
-    assert seen == {j[0] for j in jobs}
+            assert table[slot + 1 + k].G in (members[0][0].G, members[0][1].G) and table[slot + 1 + k].chain == 0
+    assert seen == {j.G for j in jobs}
     first = table[heads[0]]                                  # longest reduction first: 300 + 64 + 300 rows
-    assert (first.G, first.chain, first.M) == (jobs[0][0], 2, 300)
-    seg = next(table[s] for s in heads if table[s].G == jobs[3][0])
+    assert (first.G, first.chain, first.M) == (jobs[0].G, 2, 300)
+    seg = next(table[s] for s in heads if table[s].G == jobs[3].G)
     assert (seg.g_seg_cols, seg.g_seg_stride, seg.ldg) == (64, 300 * 64, 192)
 
     long_jobs = [job(10 + i, 14500, n1, k2) for i, (n1, k2) in enumerate([(512, 256), (256, 256), (2048, 256), (256, 2048)])]
     long_jobs.append(job(20, 513, 8, 8))
-    raw, off, nblocks = q._pack_long(long_jobs)
+    raw, off, nblocks, _ = W.long_table(long_jobs, long_rows)
     assert nblocks % 8 == 0 and raw.size == off + 8 * nblocks
     table = (L.TnJob * len(long_jobs)).from_buffer_copy(raw[:len(long_jobs) * size].tobytes())
     bj = raw[off:off + 4 * nblocks].view(np.int32).reshape(-1, 8)

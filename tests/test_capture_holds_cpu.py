@@ -12,13 +12,13 @@ import torch
 def native(monkeypatch):
     """The native layer with its launches stubbed out and a prepared-operand store of the test's own."""
     from future_od.native import capture
-    from future_od.native import functional as Fn
     from future_od.native import ops
-    monkeypatch.setattr(Fn.L, "call", lambda *a, **k: None)
+    from future_od.native import prepared
+    monkeypatch.setattr(prepared.L, "call", lambda *a, **k: None)
     monkeypatch.setattr(ops, "stream", lambda: 0)
-    monkeypatch.setattr(Fn, "PREP", Fn._Prepared())
+    monkeypatch.setattr(prepared, "PREP", prepared._Prepared())
     assert capture._open is None
-    return capture, Fn
+    return capture, prepared
 
 
 def _weight(seed=0):
@@ -26,23 +26,23 @@ def _weight(seed=0):
     return torch.nn.Parameter(torch.randn(24, 16))
 
 
-def _prepare(Fn, w):
+def _prepare(prep, w):
     """Request the operand of `w`: builds its entry and launches (stub) a refresh from a table of its own.
     -> weak references to the entry's value tensor and to the table's device job array."""
-    value = Fn.prep_linear(w, torch.float32, False)
-    table = list(Fn.PREP._tables.values())[-1]
+    value = prep.prep_linear(w, torch.float32, False)
+    table = list(prep.PREP._tables.values())[-1]
     assert table[4][0][1] is value                    # the table built last is the one that fills this entry
     return weakref.ref(value), weakref.ref(table[0])
 
 
 def test_a_record_keeps_what_was_used_while_it_was_open(native):
-    capture, Fn = native
+    capture, prep = native
     w = _weight()
     with capture.Record() as record:
-        value, table = _prepare(Fn, w)
+        value, table = _prepare(prep, w)
     del w                 # (a live parameter's memo keeps its own entry, and the store it was made in, for the fast path)
     assert record.of("prepared operands") and record.of("refresh table")
-    Fn.PREP.clear()
+    prep.PREP.clear()
     gc.collect()
     assert value() is not None and table() is not None
     del record
@@ -51,25 +51,25 @@ def test_a_record_keeps_what_was_used_while_it_was_open(native):
 
 
 def test_without_a_record_clear_frees(native):
-    capture, Fn = native
+    capture, prep = native
     w = _weight()
-    value, table = _prepare(Fn, w)
+    value, table = _prepare(prep, w)
     del w
-    Fn.PREP.clear()
+    prep.PREP.clear()
     gc.collect()
     assert value() is None and table() is None
     assert not capture.FOREIGN
 
 
 def test_an_evicted_refresh_table_survives_only_in_a_record(native):
-    capture, Fn = native
+    capture, prep = native
     weights = [_weight(i) for i in range(24)]
     with capture.Record() as record:
-        _, held = _prepare(Fn, weights[0])
-    _, loose = _prepare(Fn, weights[1])
+        _, held = _prepare(prep, weights[0])
+    _, loose = _prepare(prep, weights[1])
     for w in weights[2:]:                             # 22 further stale sets, one table each: the cap of 16 is passed
-        _prepare(Fn, w)
-    assert len(Fn.PREP._tables) < 16
+        _prepare(prep, w)
+    assert len(prep.PREP._tables) < 16
     gc.collect()
     assert held() is not None and loose() is None
     assert record.of("refresh table")[0][0] is held()
@@ -79,7 +79,7 @@ def test_an_evicted_refresh_table_survives_only_in_a_record(native):
 
 
 def test_an_outgrown_arena_buffer_survives_only_in_a_record(native):
-    capture, Fn = native
+    capture, prep = native
 
     def outgrow(arena):
         old = weakref.ref(arena.buf)
@@ -89,7 +89,8 @@ def test_an_outgrown_arena_buffer_survives_only_in_a_record(native):
         gc.collect()
         return old
 
-    arena = Fn._ZeroArena()
+    from future_od.native.arena import _ZeroArena
+    arena = _ZeroArena()
     arena.recycle("cpu")
     assert outgrow(arena)() is None
     with capture.Record() as record:
@@ -101,21 +102,21 @@ def test_an_outgrown_arena_buffer_survives_only_in_a_record(native):
 
 
 def test_a_record_asks_the_providers_when_it_closes(native):
-    capture, Fn = native
+    capture, prep = native
     w = _weight()
-    value, _ = _prepare(Fn, w)                        # built BEFORE the record opens, as a capture's warm-up does
+    value, _ = _prepare(prep, w)                        # built BEFORE the record opens, as a capture's warm-up does
     with capture.Record() as record:
-        assert Fn.prep_linear(w, torch.float32, False) is value()        # the memo fast path: holds nothing itself
+        assert prep.prep_linear(w, torch.float32, False) is value()        # the memo fast path: holds nothing itself
         assert not record.held
-    assert [id(o) for o in record.of("prepared operands")] == [id(Fn.PREP._store)]
+    assert [id(o) for o in record.of("prepared operands")] == [id(prep.PREP._store)]
     del w
-    Fn.PREP.clear()
+    prep.PREP.clear()
     gc.collect()
     assert value() is not None
 
 
 def test_hold_outside_a_record_keeps_nothing(native):
-    capture, Fn = native
+    capture, prep = native
     t = torch.zeros(4)
     ref = weakref.ref(t)
     assert capture.hold("anything", t) is None and capture.hold_or_ask("anything", t) is False

@@ -113,26 +113,26 @@ def test_deterministic_long_job_plan_keeps_the_scratch_bounded_at_the_headline_e
     default plan has ~7 M-splits of 2048 rows per job and no scratch; the deterministic plan at most
     FOD_TN_DET_MAX_SPLITS longer ones, and cuts the jobs into launches that each fit fod_workspace_bytes(WS_TN_MULTI_DET)."""
     import numpy as np
-    from future_od.native import functional as Fn
     from future_od.native import lib as L
-    q = Fn._WgradQueue()
+    from future_od.native import wgrad as W
+    long_rows = W._WgradQueue().long_rows
     n = [0]
 
     def job(M, N1, K2, bias=True):
         n[0] += 1
-        return (1000 * n[0] + 16, 2000 * n[0] + 32, 3000 * n[0] + 48, 4000 * n[0] + 64 if bias else 0, N1, K2, K2, M, N1, K2,
-                0, 0, 0)
+        return W.Job(G=1000 * n[0] + 16, X=2000 * n[0] + 32, dW=3000 * n[0] + 48, colsum=4000 * n[0] + 64 if bias else 0,
+                     ldg=N1, ldx=K2, ldw=K2, M=M, N1=N1, K2=K2)
     enc = [(512, 256), (256, 256), (256, 256), (2048, 256), (256, 2048)]        # q|k, v, out, the two feed-forward layers
     jobs = [job(14500, n1, k2) for _ in range(6) for n1, k2 in enc]
     jobs += [job(7250, 256, 256) for _ in range(6) for _ in range(3)]           # the decoder's memory-side projections
     jobs.append(job(14500, 256, 256, bias=False))
     cap = L.LIB.fod_workspace_bytes(L.WS_TN_MULTI_DET)
-    groups = q.det_groups(jobs)
+    groups = W.det_groups(jobs, long_rows)
     assert sum(len(g) for g in groups) == len(jobs) and [j for g in groups for j in g] == jobs      # queue order kept
     assert len(groups) >= 2                                  # (this extent does not fit one launch: the cut is exercised)
     size = ctypes.sizeof(L.TnJob)
     for group in groups:
-        raw, off, nblocks, part_floats = q._pack_long(group, det=True)
+        raw, off, nblocks, part_floats = W.long_table(group, long_rows, det=True)
         assert 0 < 4 * part_floats <= cap
         assert raw.size == off + 8 * nblocks + 8 * len(group)
         table = (L.TnJob * len(group)).from_buffer_copy(raw[:len(group) * size].tobytes())
@@ -144,9 +144,9 @@ def test_deterministic_long_job_plan_keeps_the_scratch_bounded_at_the_headline_e
             at += t.nsplit * (t.N1 * t.K2 + (t.N1 if t.colsum else 0))
         assert at == part_floats
     # the default plan is what it was
-    raw, off, nblocks = q._pack_long(jobs[:5])
+    raw, off, nblocks, _ = W.long_table(jobs[:5], long_rows)
     table = (L.TnJob * 5).from_buffer_copy(raw[:5 * size].tobytes())
     assert all(t.nsplit == 7 for t in table)
     # a job that cannot fit is refused, not run with atomics
     with pytest.raises(L.FodError, match="scratch"):
-        q.det_groups([job(14500, 8192, 2048)])
+        W.det_groups([job(14500, 8192, 2048)], long_rows)

@@ -24,6 +24,7 @@ if torch.cuda.is_available():
     from future_od.native import functional as Fn
     from future_od.native import lib as L
     from future_od.native import ops
+    from future_od.native import wgrad
     from test_kernels_gpu import check, rnd
 
 
@@ -126,8 +127,8 @@ def test_gemm_tn_multi_long_det():
             outs += [dw, db]
         assert len(q.long_jobs) == len(cases)
         if det:
-            assert all(q._long_plan(m, True)[1] > 1 for m, _, _ in cases)                    # several splits per element
-            assert all(q._long_plan(m, True)[1] <= L.TN_DET_MAX_SPLITS for m, _, _ in cases)
+            assert all(wgrad.long_plan(m, q.long_rows, True)[1] > 1 for m, _, _ in cases)                    # several splits per element
+            assert all(wgrad.long_plan(m, q.long_rows, True)[1] <= L.TN_DET_MAX_SPLITS for m, _, _ in cases)
         q.flush()
         assert q.launches == 1 and q.carried == len(cases)
         ops.set_deterministic(True)

@@ -76,7 +76,7 @@ def test_graphed_steps_track_eager_steps(dtype):
 
 
 def test_capture_without_spare_job_tables_launches_the_queued_gradients_one_by_one(monkeypatch):
-    """The queued short weight gradients (native/functional.py: WGRADS) need a pinned job table set aside BEFORE a
+    """The queued short weight gradients (native/wgrad.py: WGRADS) need a pinned job table set aside BEFORE a
     capture; a capture that finds none (more flushes than spares, a foreign capture) must launch them one by one --
     never allocate inside the capture, never drop a gradient."""
     from future_od.datasets.synthetic import make_batch

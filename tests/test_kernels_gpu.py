@@ -1277,6 +1277,7 @@ def test_gemm_tn_multi_long_matches_single_launches():
     """fod_gemm_tn_multi_long (the long weight gradients of a backward pass in one launch, M split per job, splits dealt
     to XCDs, idle padding blocks) against one fod_gemm_tn_acc launch per job and against fp32 matmuls."""
     from future_od.native import functional as Fn
+    from future_od.native import wgrad
     dtype = torch.bfloat16
     cases = [(14500, 256, 256), (2900, 2048, 256), (4350, 256, 2048), (3000, 264, 72), (513, 8, 8), (7250, 512, 256)]
     q = Fn._WgradQueue()
@@ -1306,7 +1307,7 @@ def test_gemm_tn_multi_long_matches_single_launches():
         q.tn(True, g, x, dw, db)
     q.flush()
     for (M, N1, K2), (g, x, dw, db, dw_ref, db_ref) in zip(cases, outs):
-        single = q._plans[M][1] == 1
+        single = wgrad.long_plan(M, q.long_rows, False)[1] == 1
         check(dw, dw_ref if single else 2 * dw_ref, torch.float32, 2 * math.sqrt(M), f"second launch {(M, N1, K2)}")
 
 

@@ -57,8 +57,8 @@ def restore(model, opt, snap):
     opt._step_no = step_no
     if getattr(opt, "_dev_step", None) is not None:
         opt._dev_step.fill_(float(step_no))
-    from future_od.native import functional as Fn
-    Fn.PREP.mark_stale()
+    from future_od.native import prepared
+    prepared.PREP.mark_stale()
 
 
 def run_until_takeoff(model, opt, batches, steps, every=5):

@@ -26,6 +26,7 @@ from future_od.datasets.synthetic import make_batch  # noqa: E402
 from future_od.graph import GraphedStep  # noqa: E402
 from future_od.native import functional as Fn  # noqa: E402
 from future_od.native import lib as L  # noqa: E402
+from future_od.native import wgrad  # noqa: E402
 from future_od.optim import FusedAdamW  # noqa: E402
 
 
@@ -59,7 +60,7 @@ def main():
     ms_graph = (time.perf_counter() - t0) * 100
     print(f"graph replay: {ms_graph:.3f} ms/step", flush=True)
 
-    Fn.WGRADS.eager = True
+    wgrad.WGRADS.eager = True
     eager_step()
     torch.cuda.synchronize()
 
@@ -122,7 +123,7 @@ def main():
         gc.enable()
         print(f"parked leg {rep}: enqueue took {t_enq * 1e3:.1f} ms (a value near 5000 = the queue filled and the timer released it)")
         summarize("b) stream parked during enqueue", L.PROFILER.records)
-    Fn.WGRADS.eager = False
+    wgrad.WGRADS.eager = False
 
     # c) torch.profiler over replays
     try:
