@@ -30,6 +30,12 @@ FOD_DEVINL float giou_xyxy(const Box4& a, const Box4& t) {
 
 FOD_DEVINL float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 FOD_DEVINL float softplusf(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+// cxcywh in (0,1) -> xyxy pixels (st_detr.py:198-210); shared by post_proc_kernel and detect_select_kernel, whose boxes
+// are compared bit for bit
+FOD_DEVINL Box4 cxcywh_to_px(const float* b, float H, float W) {
+  const float cx = b[0] * W, cy = b[1] * H, w = b[2] * W, h = b[3] * H;
+  return {cx - 0.5f * w, cy - 0.5f * h, cx + 0.5f * w, cy + 0.5f * h};
+}
 
 // ------------------------------------------------------------------------------------------------
 __global__ void match_cost_kernel(const float* __restrict__ logits, const float* __restrict__ boxes,
@@ -233,11 +239,103 @@ __global__ void post_proc_kernel(const float* __restrict__ logits, const float* 
     mx = fmaxf(mx, s);
   }
   scores[(long)r * (C + 1) + C] = mx;
-  const float cx = boxes[r * 4 + 0] * W, cy = boxes[r * 4 + 1] * H, w = boxes[r * 4 + 2] * W, h = boxes[r * 4 + 3] * H;
-  boxes_px[r * 4 + 0] = cx - 0.5f * w;
-  boxes_px[r * 4 + 1] = cy - 0.5f * h;
-  boxes_px[r * 4 + 2] = cx + 0.5f * w;
-  boxes_px[r * 4 + 3] = cy + 0.5f * h;
+  const Box4 px = cxcywh_to_px(boxes + r * 4, H, W);
+  boxes_px[r * 4 + 0] = px.x0;
+  boxes_px[r * 4 + 1] = px.y0;
+  boxes_px[r * 4 + 2] = px.x1;
+  boxes_px[r * 4 + 3] = px.y1;
+}
+
+// Label-free detection output (reference st_detr.py:190-234 followed by ConditionalDETR's PostProcess / demo.ipynb:171-172,
+// 245: sigmoid, top-k, index -> (query, class), gather, box conversion, scaling, masking) as ONE launch: one workgroup
+// per sample ranks that sample's candidates in LDS and writes the K best rows.
+//   key = (score bits << 32) | (0xffffffff - flat index): scores are sigmoids, i.e. non-negative floats, whose bit patterns
+//   order like their values, so ONE descending sort of the 64-bit words is "score descending, flat index ascending";
+//   0 marks "not eligible" (below the threshold, NaN, or padding up to the power of two P) and sorts last -- no eligible
+//   key is 0, because its low word is at least 0xffffffff - 8191.
+// Scores and boxes come from the very inline functions post_proc_kernel uses (sigmoidf, cxcywh_to_px): a selected row
+// is bit-equal to the row fod_post_proc writes.  No scratch, no atomics, nothing between workgroups: deterministic.
+constexpr int DET_MAX_K = 1024, DET_MAX_N = 8192;
+__global__ __launch_bounds__(1024) void detect_select_kernel(const float* __restrict__ logits,
+                                                             const float* __restrict__ boxes,
+                                                             const float* __restrict__ box_map, int M, int C, int K,
+                                                             int P, float thr, int per_query, float H, float W,
+                                                             float* __restrict__ out_scores,
+                                                             int32_t* __restrict__ out_labels,
+                                                             int32_t* __restrict__ out_query,
+                                                             float* __restrict__ out_boxes,
+                                                             int32_t* __restrict__ out_count) {
+  extern __shared__ unsigned long long det_keys[];     // [P]
+  const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+  const int n = per_query ? M : M * C;
+  const float* lg = logits + (long)b * M * C;
+  for (int f = tid; f < P; f += nthr) {
+    unsigned long long key = 0ull;
+    if (f < n) {
+      float s;
+      if (per_query) {
+        s = -INFINITY;                                  // the appended "max" column of post_proc_kernel
+        for (int c = 0; c < C; ++c) s = fmaxf(s, sigmoidf(lg[(long)f * C + c]));
+      } else {
+        s = sigmoidf(lg[f]);
+      }
+      // (a NaN fails both tests; so does the -inf "maximum" of a query whose logits are all NaN)
+      if (s >= thr && s >= 0.f) key = ((unsigned long long)__float_as_uint(s) << 32) | (0xffffffffu - (unsigned)f);
+    }
+    det_keys[f] = key;
+  }
+  // bitonic network, descending: pair t of a step with distance j is (i, i + j), i = t with a zero inserted at bit j.
+  // (Measured at 1024 candidates: 17.4 us either way with the workgroup barrier of the 45 steps that stay inside one
+  // wave's keys replaced by a wave-local fence -- the LDS round trip of each step is the time, not the barrier.)
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int t = tid; t < (P >> 1); t += nthr) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const unsigned long long a = det_keys[i], c = det_keys[i + j];
+        if ((i & k) == 0 ? a < c : a > c) {
+          det_keys[i] = c;
+          det_keys[i + j] = a;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  // the eligible keys are the non-zero prefix: exactly one position sees its end
+  for (int j = tid; j < P; j += nthr) {
+    const bool here = det_keys[j] != 0ull, next = j + 1 < P && det_keys[j + 1] != 0ull;
+    if (here && !next) out_count[b] = min(K, j + 1);
+    if (j == 0 && !here) out_count[b] = 0;
+  }
+  for (int j = tid; j < K; j += nthr) {
+    const unsigned long long key = j < P ? det_keys[j] : 0ull;
+    const long o = (long)b * K + j;
+    float score = 0.f, x0 = 0.f, y0 = 0.f, x1 = 0.f, y1 = 0.f;
+    int label = -1, query = -1;
+    if (key != 0ull) {
+      const int f = (int)(0xffffffffu - (unsigned)key);
+      score = __uint_as_float((unsigned)(key >> 32));
+      query = per_query ? f : f / C;
+      label = per_query ? 0 : f - query * C;
+      if (per_query)                                    // lowest class that attains the maximum
+        for (int c = C - 1; c >= 0; --c)
+          if (sigmoidf(lg[(long)f * C + c]) == score) label = c;
+      const Box4 px = cxcywh_to_px(boxes + ((long)b * M + query) * 4, H, W);
+      x0 = px.x0, y0 = px.y0, x1 = px.x1, y1 = px.y1;
+      if (box_map) {                                    // output pixels -> source-frame pixels; a flip has sx < 0
+        const float sx = box_map[b * 4 + 0], sy = box_map[b * 4 + 1], ox = box_map[b * 4 + 2], oy = box_map[b * 4 + 3];
+        const float u0 = x0 * sx + ox, u1 = x1 * sx + ox, v0 = y0 * sy + oy, v1 = y1 * sy + oy;
+        x0 = fminf(u0, u1), x1 = fmaxf(u0, u1), y0 = fminf(v0, v1), y1 = fmaxf(v0, v1);
+      }
+    }
+    out_scores[o] = score;
+    out_labels[o] = label;
+    out_query[o] = query;
+    out_boxes[o * 4 + 0] = x0;
+    out_boxes[o * 4 + 1] = y0;
+    out_boxes[o * 4 + 2] = x1;
+    out_boxes[o * 4 + 3] = y1;
+  }
 }
 
 // The annotation counts start from zero in a kernel of their own, not through hipMemsetAsync: captured into a
@@ -507,6 +605,28 @@ extern "C" int fod_post_proc(const float* logits, const float* boxes, float* cla
   FOD_REQUIRE(logits && boxes && class_scores && boxes_px && R > 0 && C > 0, "post_proc: bad args");
   hipLaunchKernelGGL(post_proc_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, stream, logits, boxes, class_scores,
                      boxes_px, R, C, img_h, img_w);
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}
+
+extern "C" int fod_detect_select(const float* logits, const float* boxes, const float* box_map, int B, int M, int C,
+                                 int K, float score_threshold, int per_query, float img_h, float img_w,
+                                 float* out_scores, int32_t* out_labels, int32_t* out_query, float* out_boxes,
+                                 int32_t* out_count, hipStream_t stream) {
+  FOD_REQUIRE(B > 0 && M > 0 && C > 0, "detect_select: bad extents B=%d M=%d C=%d", B, M, C);
+  FOD_REQUIRE(K >= 1 && K <= DET_MAX_K, "detect_select: K=%d is outside 1..%d", K, DET_MAX_K);
+  FOD_REQUIRE(logits && boxes && out_scores && out_labels && out_query && out_boxes && out_count,
+              "detect_select: null operand");
+  const long n = per_query ? (long)M : (long)M * C;
+  FOD_REQUIRE(n <= DET_MAX_N, "detect_select: %ld candidates per sample (%s) exceed the limit of %d", n,
+              per_query ? "M" : "M*C", DET_MAX_N);
+  FOD_REQUIRE((long)M * C <= 0x7fffffffL / B, "detect_select: B*M*C overflows the index range");
+  int P = 1;                                            // sorted length: the power of two that holds the candidates
+  while (P < n) P <<= 1;
+  const int threads = std::min(1024, std::max(64, P / 2));
+  hipLaunchKernelGGL(detect_select_kernel, dim3(B), dim3(threads), (size_t)P * sizeof(unsigned long long), stream, logits,
+                     boxes, box_map, M, C, K, P, score_threshold, per_query != 0, img_h, img_w, out_scores, out_labels,
+                     out_query, out_boxes, out_count);
   FOD_LAUNCH_CHECK();
   return FOD_OK;
 }

@@ -89,6 +89,16 @@ class Plan:
             boxes, classes = annotate(step, boxes, classes)
         return boxes, classes
 
+    def box_map(self):
+        """(sx, sy, ox, oy): output-pixel coordinates back to source-frame pixels, x_src = x * sx + ox and y_src =
+        y * sy + oy -- the inverse of `annotate` for boxes inside the rectangle.  A flip gives sx < 0: the caller
+        re-orders the corners (ops.detect_select does)."""
+        top, left, h, w = self.rect
+        H, W = self.size
+        if self.flip:
+            return (-w / W, h / H, float(left + w), float(top))
+        return (w / W, h / H, float(left), float(top))
+
     def __repr__(self):
         return f"Plan(rect={self.rect}, size={self.size}, flip={self.flip}, steps={self.steps})"
 

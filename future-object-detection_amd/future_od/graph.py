@@ -466,13 +466,12 @@ def _warmup_stream(dev):
     return _WARMUP_STREAMS[key]
 
 
-class GraphedForward:
-    """out = GraphedForward(model)(data): the evaluation pass (`with torch.no_grad(): model(data)`; forward, set loss,
-    post-processing, AP bookkeeping) as one hipGraph per batch signature.  The reference's evaluation loop
-    (trainer.py:171-178 without the backward) is ~450 launches behind ~16 us of Python each: bound by the launching
-    thread on all but the largest configuration.  Parameters are read when the graph RUNS, so a graph captured once stays
-    valid while training updates them in place; the compute-dtype weight copies the kernels read are refreshed (one eager
-    launch) before a replay whenever a parameter has changed since.  Returns (post, loss, stats, od): the graph's static outputs, valid until the next call."""
+class _GraphedInference:
+    """What the captured evaluation passes share: one hipGraph per batch signature -- eager warm-up on the shared
+    warm-up stream, prepared weight copies refreshed before the capture and before each replay, a capture.Record that
+    holds what the graph bakes in, CaptureError on a failed capture, inputs staged into the captured buffers.
+    A subclass says what one pass is (`_run`), which entries of a batch it reads (`_inputs`, `_signature`) and what is
+    checked before a replay (`_before_replay`)."""
 
     def __init__(self, model, warmup=1):
         self.model, self.warmup = model, max(int(warmup), 1)
@@ -480,14 +479,20 @@ class GraphedForward:
         self.replays = 0
 
     def _run(self, data):
-        with torch.no_grad():
-            post, _state, loss, stats, od = self.model(data=data, distributed=False)
-        return post, loss, stats, od
+        raise NotImplementedError
+
+    def _inputs(self, data):
+        return {k: v for k, v in data.items() if k != "_host_annotations"}
+
+    def _signature(self, data):
+        return GraphedStep._signature(data)
+
+    def _before_replay(self, g):
+        pass
 
     def _capture(self, data):
         dev = next(v for v in data.values() if isinstance(v, torch.Tensor)).device
-        static = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in data.items()
-                  if k != "_host_annotations"}
+        static = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in self._inputs(data).items()}
         side = _warmup_stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -507,22 +512,61 @@ class GraphedForward:
         return {"graph": graph, "static": static, "outs": outs, "record": record}
 
     def __call__(self, data):
+        name = type(self).__name__
         if self.model.training:
-            raise RuntimeError("GraphedForward: evaluation only (model.eval()); training steps go through GraphedStep")
-        sig = GraphedStep._signature(data)
+            raise RuntimeError(f"{name}: evaluation only (model.eval()); training steps go through GraphedStep")
+        sig = self._signature(data)
         g = self._graphs.get(sig)
         if g is None:
-            for k, v in data.items():
+            for k, v in self._inputs(data).items():
                 if isinstance(v, torch.Tensor) and not v.is_cuda:
-                    raise RuntimeError(f"GraphedForward: batch entry {k!r} is not on the device")
+                    raise RuntimeError(f"{name}: batch entry {k!r} is not on the device")
             try:
                 g = self._capture(data)
             except Exception as e:                    # noqa: BLE001
                 raise CaptureError(f"{type(e).__name__}: {e}") from e
             self._graphs[sig] = g
-        _check_matcher(g)
+        self._before_replay(g)
         _stage_inputs(g, data)
         prepared.PREP.refresh()                             # one launch if an optimizer step happened since, nothing otherwise
         g["graph"].replay()
         self.replays += 1
         return g["outs"]
+
+
+class GraphedForward(_GraphedInference):
+    """out = GraphedForward(model)(data): the evaluation pass (`with torch.no_grad(): model(data)`; forward, set loss,
+    post-processing, AP bookkeeping) as one hipGraph per batch signature.  The reference's evaluation loop
+    (trainer.py:171-178 without the backward) is ~450 launches behind ~16 us of Python each: bound by the launching
+    thread on all but the largest configuration.  Parameters are read when the graph RUNS, so a graph captured once stays
+    valid while training updates them in place; the compute-dtype weight copies the kernels read are refreshed (one eager
+    launch) before a replay whenever a parameter has changed since.  Returns (post, loss, stats, od): the graph's static outputs, valid until the next call."""
+
+    def _run(self, data):
+        with torch.no_grad():
+            post, _state, loss, stats, od = self.model(data=data, distributed=False)
+        return post, loss, stats, od
+
+    def _before_replay(self, g):
+        _check_matcher(g)
+
+
+class GraphedPredict(_GraphedInference):
+    """det = GraphedPredict(model, top_k=100)(data): `model.predict(data, ...)` -- the core and ONE detection-selection
+    launch, no targets, matcher, loss or AP bookkeeping -- as one hipGraph per signature.  The signature covers the
+    entries `predict` reads (`video`, the IMU keys, `temporal_offsets`, and whether a `box_map` is there); whatever else
+    the batch carries (labels, say) is ignored and never staged.  Returns the dict of `predict` as the graph's static
+    outputs, valid until the next call; nothing is read back.  Parameters are read when the graph runs (GraphedForward)."""
+
+    def __init__(self, model, top_k=100, score_threshold=0.0, per_query=False, warmup=1):
+        super().__init__(model, warmup)
+        self.top_k, self.score_threshold, self.per_query = int(top_k), float(score_threshold), bool(per_query)
+
+    def _run(self, data):
+        return self.model.predict(data, self.top_k, self.score_threshold, self.per_query)
+
+    def _inputs(self, data):
+        return self.model.predict_inputs(data)
+
+    def _signature(self, data):
+        return GraphedStep._signature(self._inputs(data))

@@ -104,11 +104,7 @@ class SpatioTemporalDETR(nn.Module):
                                       anno_classes=anno["classes"])
             packed = pack_targets(targets, images.device)
             num_boxes = self._criterion.global_num_boxes(targets, images.device, distributed, lazy=True)
-        kwargs = {}
-        if data.get("translation") is not None:
-            kwargs["imu"] = torch.cat([data[k] for k in self._imu_keys], dim=2)
-        if self._encode_offset:
-            kwargs["temporal_offsets"] = data["temporal_offsets"]
+        kwargs = self._core_kwargs(data)
         # --- device work
         outputs, model_moods = self._model(images, **kwargs)
         if not (isinstance(outputs, dict) and outputs["pred_logits"].dim() == 3):
@@ -128,6 +124,50 @@ class SpatioTemporalDETR(nn.Module):
         od_map_stuffs, post = done[0]
         post["moods"] = model_moods
         return post, None, loss, stats, od_map_stuffs
+
+    def _core_kwargs(self, data):
+        kwargs = {}
+        if data.get("translation") is not None:
+            kwargs["imu"] = torch.cat([data[k] for k in self._imu_keys], dim=2)
+        if self._encode_offset:
+            kwargs["temporal_offsets"] = data["temporal_offsets"]
+        return kwargs
+
+    def predict_inputs(self, data):
+        """The entries of `data` that `predict` reads (what GraphedPredict stages): `video`, the IMU keys when
+        `translation` is there, `temporal_offsets` when the offsets are encoded, `box_map` when present."""
+        keys = ["video"]
+        if data.get("translation") is not None:
+            keys += self._imu_keys
+        if self._encode_offset:
+            keys.append("temporal_offsets")
+        if data.get("box_map") is not None:
+            keys.append("box_map")
+        return {k: data[k] for k in keys}
+
+    @torch.no_grad()
+    def predict(self, data, top_k=100, score_threshold=0.0, per_query=False, box_map=None):
+        """Detections for frames WITHOUT annotations: the core exactly as `forward` calls it, then one launch
+        (ops.detect_select) in place of the reference's post-processing chain (st_detr.py:190-234, ConditionalDETR's
+        PostProcess, demo.ipynb:171-172,245) -- no targets, no matcher, no loss, no AP bookkeeping, no host sync.
+        -> {"scores" f32 [B,K], "labels" i32 [B,K], "boxes" f32 [B,K,4] xyxy pixels, "query" i32 [B,K], "count" i32 [B]}
+        on the device: per sample the `top_k` best of all (query, class) pairs -- `per_query`: of the queries, each
+        with its best class -- whose score reaches `score_threshold`, best first; rows from `count[b]` on are padding
+        (score 0, label / query -1, box 0).  `box_map` f32 [B,4] = (sx, sy, ox, oy) (default: `data["box_map"]`, which
+        the label-free raw-frame path provides) takes the boxes from the network's input frame to the camera's."""
+        if self.training:
+            raise RuntimeError("predict: evaluation only (model.eval()); dropout would make the detections random")
+        images = data["video"]
+        H, W = images.shape[-2:]
+        if box_map is None:
+            box_map = data.get("box_map")
+        outputs, _moods = self._model(images, **self._core_kwargs(data))
+        if not (isinstance(outputs, dict) and outputs["pred_logits"].dim() == 3):
+            raise ValueError("cannot interpret output on the format: %s" % type(outputs))
+        scores, labels, boxes, query, count = ops.detect_select(
+            outputs["pred_logits"].detach().float().contiguous(), outputs["pred_boxes"].detach().float().contiguous(),
+            H, W, top_k, score_threshold, per_query, box_map)
+        return {"scores": scores, "labels": labels, "boxes": boxes, "query": query, "count": count}
 
     def loss(self, data, outputs, distributed, targets=None, packed=None, num_boxes=None):
         if targets is None and packed is None:

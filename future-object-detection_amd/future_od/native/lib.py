@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "lib", "libfod_hip.so"))
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 F32, BF16 = 0, 1
 EW_ADD, EW_MUL, EW_RELU_MASK, EW_SCALE, EW_ADD3, EW_RELU, EW_COPY_B = range(7)
@@ -151,6 +151,7 @@ SIGNATURES = {
     "fod_set_loss_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p, _f, _p],
     "fod_od_map": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p],
     "fod_post_proc": [_p, _p, _p, _p, _i, _i, _f, _f, _p],
+    "fod_detect_select": [_p, _p, _p, _i, _i, _i, _i, _f, _i, _f, _f, _p, _p, _p, _p, _p, _p],
     "fod_tracker_cost": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "fod_tracker_extrapolate": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "fod_multi_sqnorm_acc": [_p, _p, _p, _p, _i, _p, _p],

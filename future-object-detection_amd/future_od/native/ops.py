@@ -1113,6 +1113,41 @@ def post_proc(logits, boxes, img_h, img_w):
     return scores, boxes_px
 
 
+def detect_select(logits, boxes, img_h, img_w, top_k=100, score_threshold=0.0, per_query=False, box_map=None, out=None):
+    """logits f32 [B,M,C], boxes f32 [B,M,4] cxcywh in (0,1) -> (scores f32 [B,K], labels i32 [B,K], boxes f32 [B,K,4]
+    xyxy pixels, query i32 [B,K], count i32 [B]): the K best candidates of each sample, one launch (fod_detect_select in
+    include/fod.h has the exact semantics).  `box_map` f32 [B,4] = (sx, sy, ox, oy) moves the boxes into another frame.
+    `out`: five tensors of those shapes to write into instead of new ones."""
+    _chk(logits, "logits", torch.float32); _chk(boxes, "boxes", torch.float32)
+    if logits.dim() != 3 or boxes.shape != logits.shape[:2] + (4,):
+        raise L.FodError(f"detect_select: logits [B,M,C] and boxes [B,M,4] expected, got {tuple(logits.shape)} and "
+                         f"{tuple(boxes.shape)}")
+    B, M, Cc = logits.shape
+    K, dev = int(top_k), logits.device
+    if box_map is not None:
+        _chk(box_map, "box_map", torch.float32)
+        if box_map.shape != (B, 4) or box_map.device != dev:
+            raise L.FodError(f"detect_select: box_map f32 [{B},4] on {dev} expected, got {tuple(box_map.shape)} on "
+                             f"{box_map.device}")
+    if out is None:
+        out = (torch.empty((B, max(K, 0)), dtype=torch.float32, device=dev),
+               torch.empty((B, max(K, 0)), dtype=torch.int32, device=dev),
+               torch.empty((B, max(K, 0), 4), dtype=torch.float32, device=dev),
+               torch.empty((B, max(K, 0)), dtype=torch.int32, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    scores, labels, boxes_px, query, count = out
+    for t, name, dtype, shape in ((scores, "scores", torch.float32, (B, K)), (labels, "labels", torch.int32, (B, K)),
+                                  (boxes_px, "boxes", torch.float32, (B, K, 4)), (query, "query", torch.int32, (B, K)),
+                                  (count, "count", torch.int32, (B,))):
+        _chk(t, "out " + name, dtype)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise L.FodError(f"detect_select: out {name} {shape} on {dev} expected, got {tuple(t.shape)} on {t.device}")
+    call("fod_detect_select", ptr(logits), ptr(boxes), ptr(box_map), B, M, Cc, K, float(score_threshold),
+         int(bool(per_query)), float(img_h), float(img_w), ptr(scores), ptr(labels), ptr(query), ptr(boxes_px),
+         ptr(count), stream())
+    return scores, labels, boxes_px, query, count
+
+
 def od_map(scores, boxes_px, anno_boxes, anno_classes, anno_active, imsize, T=10):
     _chk(scores, "scores", torch.float32); _chk(boxes_px, "boxes", torch.float32)
     _chk(anno_boxes, "anno_boxes", torch.float32)

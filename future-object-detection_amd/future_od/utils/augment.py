@@ -38,7 +38,7 @@ class DeviceJointTransform:
         """-> a new batch dict: `boxes`, `classes`, `active` (and the non-zero rows of `ignore_boxes`) transformed --
         kept rows first, in their old order, freed rows zero / inactive, the dense padding of the reference's datasets
         (datasets/utils.py:19-38) -- plus `plans` int32 [B, 5] for the device half.  `_host_annotations` holds the
-        transformed tensors."""
+        transformed tensors.  A batch with none of `boxes`, `classes`, `active` is label-free: see _host_label_free."""
         video = batch["video"]
         if video.dtype != torch.uint8 or video.dim() != 5:
             raise ValueError(f"the device transform takes raw uint8 clips [B, L, 3, H0, W0], got {video.dtype} {tuple(video.shape)}")
@@ -46,14 +46,17 @@ class DeviceJointTransform:
             index = self._index
             self._index += 1
         B, h0, w0 = video.shape[0], video.shape[-2], video.shape[-1]
+        present = [k for k in ("boxes", "classes", "active") if k in batch]
+        if not present:
+            return self._host_label_free(batch, index, B, h0, w0)
+        if len(present) != 3:
+            raise ValueError(f"a batch carries all of boxes / classes / active or none of them (label-free frames), "
+                             f"this one only {present}")
         boxes, classes, active = (torch.zeros_like(batch[k]) for k in ("boxes", "classes", "active"))
         ignore = torch.zeros_like(batch["ignore_boxes"]) if "ignore_boxes" in batch else None
         plans, size = torch.zeros(B, 5, dtype=torch.int32), None
         for b in range(B):
-            plan = self.joint_transform.plan(h0, w0, self.sample_rng(index, b))
-            if size is not None and plan.size != size:
-                raise ValueError(f"samples of one batch must share the output size: {plan.size} after {size} "
-                                 "(end the transform with a JointResize or a fixed-size crop)")
+            plan = self._plan(index, b, h0, w0, size)
             size = plan.size
             plans[b] = torch.tensor(plan.row(), dtype=torch.int32)
             rows = batch["active"][b].bool()
@@ -71,6 +74,35 @@ class DeviceJointTransform:
             out["ignore_boxes"] = ignore
         out[PLANS], out[PLAN_SIZE] = plans, size
         out[HOST_ANNOTATIONS] = {"active": active, "boxes": boxes, "classes": classes}
+        return out
+
+    def _plan(self, index, b, h0, w0, size):
+        plan = self.joint_transform.plan(h0, w0, self.sample_rng(index, b))
+        if size is not None and plan.size != size:
+            raise ValueError(f"samples of one batch must share the output size: {plan.size} after {size} "
+                             "(end the transform with a JointResize or a fixed-size crop)")
+        return plan
+
+    def _host_label_free(self, batch, index, B, h0, w0):
+        """Frames without annotations (inference): the same plans, no annotation work, and `box_map` f32 [B, 4] =
+        Plan.box_map() per sample, which takes detections in the transformed frame back to the camera's pixels
+        (SpatioTemporalDETR.predict reads it).  `ignore_boxes`, if there, is transformed as for a labelled batch."""
+        plans, box_map, size = torch.zeros(B, 5, dtype=torch.int32), torch.zeros(B, 4, dtype=torch.float32), None
+        ignore = torch.zeros_like(batch["ignore_boxes"]) if "ignore_boxes" in batch else None
+        for b in range(B):
+            plan = self._plan(index, b, h0, w0, size)
+            size = plan.size
+            plans[b] = torch.tensor(plan.row(), dtype=torch.int32)
+            box_map[b] = torch.tensor(plan.box_map(), dtype=torch.float32)
+            if ignore is not None:
+                old = batch["ignore_boxes"][b]
+                old = old[(old != 0).any(dim=1)]
+                ig, _ = plan.annotate(old, torch.zeros(old.shape[0], dtype=torch.int64))
+                ignore[b, :ig.shape[0]] = ig
+        out = {k: v for k, v in batch.items() if k != HOST_ANNOTATIONS}
+        if ignore is not None:
+            out["ignore_boxes"] = ignore
+        out[PLANS], out[PLAN_SIZE], out["box_map"] = plans, size, box_map
         return out
 
     def device(self, batch):

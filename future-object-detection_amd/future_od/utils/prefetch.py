@@ -43,7 +43,8 @@ class DevicePrefetcher:
         host = {}
         if self.transform is not None:
             batch = self.transform.host(batch)
-            batch.pop(HOST_ANNOTATIONS)          # the transformed host tensors; kept below, not uploaded twice
+            batch.pop(HOST_ANNOTATIONS, None)    # the transformed host tensors; kept below, not uploaded twice
+                                                 # (a label-free batch has none)
         if isinstance(batch, dict) and all(k in batch for k in _ANNOTATION_KEYS):
             host = {k: batch[k] for k in _ANNOTATION_KEYS
                     if isinstance(batch[k], torch.Tensor) and batch[k].device.type == "cpu"}

@@ -45,7 +45,7 @@ enum { FOD_OK = 0, FOD_ERR_ARG = 1, FOD_ERR_LAUNCH = 2, FOD_ERR_RUNTIME = 3 };
 size_t fod_last_error(char* buf, size_t cap);
 /* ABI version of this header; the loader refuses a library that disagrees. */
 int fod_abi_version(void);
-#define FOD_ABI_VERSION 8
+#define FOD_ABI_VERSION 9
 
 /* Kernel-selection knobs: the FOD_* variables the library looks at (listed with their values and defaults in
  * csrc/knobs.h) live in one process-wide host table that is filled from the environment ONCE, at its first use; a
@@ -640,6 +640,23 @@ int fod_tracker_extrapolate(const float* boxes2, const float* logits2, const flo
 /* class_scores = sigmoid(logits) with appended max; boxes cxcywh(0..1) -> xyxy pixels (st_detr.py:198-210) */
 int fod_post_proc(const float* logits, const float* boxes, float* class_scores, float* boxes_px, int R,
                   int C, float img_h, float img_w, fod_stream_t stream);
+/* Label-free detection output in ONE launch (replaces the reference's st_detr.py:190-234 followed by the top-k
+ * selection of ConditionalDETR's PostProcess and the thresholding / ranking of demo.ipynb:171-172,245: sigmoid, topk,
+ * div, remainder, gather, box conversion, scaling, masking).  logits f32 [B,M,C] (last decoder level), boxes f32
+ * [B,M,4] cxcywh in (0,1).  Candidates of a sample: per_query == 0: every (m, c), flat index f = m*C + c, n = M*C of
+ * them; per_query != 0: one per query, f = m, n = M, its class the arg-max over c (lowest c on ties) and its score that
+ * maximum (the appended column of fod_post_proc).  score = sigmoid(logit), bit-equal to fod_post_proc's class_scores;
+ * eligible iff score >= score_threshold (a NaN never is); order: score descending, ties by f ascending.
+ * count i32 [B] = min(K, #eligible); rows j < count[b] of out_scores f32 [B,K], out_labels / out_query i32 [B,K] (c, m)
+ * and out_boxes f32 [B,K,4] (xyxy pixels of an img_h x img_w frame, bit-equal to fod_post_proc's boxes_px) hold the
+ * j-th best candidate, rows j >= count[b] are written as score 0, label -1, query -1, box 0.  box_map f32 [B,4] =
+ * (sx, sy, ox, oy) or NULL: x' = x*sx + ox, y' = y*sy + oy, corners re-ordered so that x0 <= x1, y0 <= y1 (a flip has
+ * sx < 0).  Limits: 1 <= K <= 1024 (K may exceed n), n <= 8192; anything else is FOD_ERR_ARG before any launch.
+ * One workgroup per sample sorts packed (score bits, index) keys in LDS: no scratch, no atomics, deterministic. */
+int fod_detect_select(const float* logits, const float* boxes, const float* box_map, int B, int M, int C, int K,
+                      float score_threshold, int per_query, float img_h, float img_w, float* out_scores,
+                      int32_t* out_labels, int32_t* out_query, float* out_boxes, int32_t* out_count,
+                      fod_stream_t stream);
 
 /* Gradient clipping + AdamW over many tensors in two launches (torch.optim.AdamW + clip_grad_norm_
  * semantics; reference future_od/trainer.py:186-188, runs/_helper.py:84-107).  Device tables:
