@@ -18,8 +18,8 @@ hipcc $FLAGS -c csrc/api.cpp -o build/api.o &
 pids+=($!)
 for p in "${pids[@]}"; do wait $p; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o lib/libfod_hip.so build/*.o -lpthread
-# fast-call CPython wrappers of the same entry points (generated from the binding's signature table)
+# fast-call CPython wrappers of the same entry points (generated from include/fod.h, which the generated file includes)
 python3 ../tools/gen_fastcall.py > /dev/null
-gcc -O2 -shared -fPIC -I"$(python3 -c 'import sysconfig; print(sysconfig.get_paths()["include"])')" \
+gcc -O2 -Wall -Werror=int-conversion -shared -fPIC -I../include -I"$(python3 -c 'import sysconfig; print(sysconfig.get_paths()["include"])')" \
     build/fastcall.c -o lib/_fodfast.so -Llib -lfod_hip -Wl,-rpath,'$ORIGIN'
 echo "built $(pwd)/lib/libfod_hip.so"

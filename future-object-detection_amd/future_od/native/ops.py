@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from . import capture
+from . import abi, capture
 from . import lib as L
 from .lib import F32, BF16, AttnShape, ConvGeom, Epilogue
 
@@ -122,6 +122,19 @@ def det_workspace(device, kind=L.WS_DET):
     """(address, bytes) of the scratch a deterministic entry point is handed, for the current stream."""
     ws = _workspace(kind, device)
     return ws.data_ptr(), ws.numel() * 4
+
+
+# entry point -> its `_det` twin takes (scratch, bytes) in front of the stream (False: the same arguments); a twin the
+# header declares any other way fails this import
+_DET_TWINS = abi.det_twins(abi.PROTOTYPES)
+
+
+def call_twin(name, device, *args, **kw):
+    """call(name, *args, stream) -- in deterministic mode its `_det` twin, handed the scratch of `device`."""
+    if not _DETERMINISTIC:
+        return call(name, *args, stream(), **kw)
+    scratch = det_workspace(device) if _DET_TWINS[name] else ()
+    return call(name + "_det", *args, *scratch, stream(), **kw)
 
 
 # The two places where this module must know what the library will decide, because the scratch is the caller's to hand
@@ -267,9 +280,8 @@ def gemm_tn_acc(g, x, dw, row_scale=None, colsum=None, zeroed=False):
     if colsum is not None:
         _chk(colsum, "colsum", torch.float32); assert colsum.numel() == N1
     ws, ws_bytes = tn_workspace(g.device) if _tn_ws_bytes(M) else (None, 0)
-    call("fod_gemm_tn_acc_det" if _DETERMINISTIC else "fod_gemm_tn_acc", dt(g), ptr(g), N1, ptr(x), K2, ptr(dw), K2, M, N1, K2, ptr(row_scale), ptr(colsum),
-         0 if zeroed else 1, ws, ws_bytes, stream(),
-         work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
+    call_twin("fod_gemm_tn_acc", g.device, dt(g), ptr(g), N1, ptr(x), K2, ptr(dw), K2, M, N1, K2, ptr(row_scale),
+              ptr(colsum), 0 if zeroed else 1, ws, ws_bytes, work=2.0 * M * N1 * K2, tag="fod_gemm_tn_acc")
     return dw
 
 
@@ -330,10 +342,7 @@ def colsum_acc(g, out, group_rows=0):
     M = g.numel() // N
     groups = 1 if group_rows <= 0 else (M + group_rows - 1) // group_rows
     assert out.numel() == groups * N, (g.shape, out.shape, group_rows)
-    if _DETERMINISTIC:
-        call("fod_colsum_acc_det", dt(g), ptr(g), N, M, N, group_rows, ptr(out), *det_workspace(g.device), stream())
-    else:
-        call("fod_colsum_acc", dt(g), ptr(g), N, M, N, group_rows, ptr(out), stream())
+    call_twin("fod_colsum_acc", g.device, dt(g), ptr(g), N, M, N, group_rows, ptr(out))
     return out
 
 
@@ -481,9 +490,8 @@ def conv2d_wgrad_acc(dy, x, dw, geom, row_scale=None, zeroed=False):
     if row_scale is not None:
         _chk(row_scale, "row_scale", torch.float32); assert row_scale.numel() == geom.Cout
     ws, ws_bytes = tn_workspace(dy.device) if _tn_ws_bytes(dy.numel() // geom.Cout) else (None, 0)
-    call("fod_conv2d_wgrad_acc_det" if _DETERMINISTIC else "fod_conv2d_wgrad_acc", dt(dy), ptr(dy), ptr(x), ptr(dw), _Addr(geom), ptr(row_scale),
-         0 if zeroed else 1, ws, ws_bytes, stream(),
-         work=_conv_flops(geom), tag="fod_conv2d_wgrad_acc")
+    call_twin("fod_conv2d_wgrad_acc", dy.device, dt(dy), ptr(dy), ptr(x), ptr(dw), _Addr(geom), ptr(row_scale),
+              0 if zeroed else 1, ws, ws_bytes, work=_conv_flops(geom), tag="fod_conv2d_wgrad_acc")
     return dw
 
 
@@ -624,7 +632,6 @@ def _attn_shape(q1, k1, v, o, scale, k2=None, dk2=None, drop_p=0.0, drop_seed=0,
 
 
 _ATTN_SPLIT = {}
-_ATTN_SPLIT_FLOATS_PER_TILE = 8 * 2176          # FOD_ATTN_SPLIT_WS_FLOATS_PER_TILE (include/fod.h)
 
 
 def _attn_split_workspace(device, tiles, captured=None):
@@ -638,7 +645,7 @@ def _attn_split_workspace(device, tiles, captured=None):
     hit = _ATTN_SPLIT.get(key)
     if hit is None or hit[2] < tiles:
         cap = max(tiles, 256)
-        hit = (torch.empty(cap * _ATTN_SPLIT_FLOATS_PER_TILE, dtype=torch.float32, device=device),
+        hit = (torch.empty(cap * L.ATTN_SPLIT_WS_FLOATS_PER_TILE, dtype=torch.float32, device=device),
                torch.zeros(cap, dtype=torch.int32, device=device), cap)
         _ATTN_SPLIT[key] = hit
     if captured:
@@ -843,11 +850,9 @@ def linear_add_norm_bwd(dy, xsum, mean, rstd, gamma, w_t, dgamma, dbeta, want_da
     _chk(dgamma, "dgamma", torch.float32); _chk(dbeta, "dbeta", torch.float32)
     dsum = torch.empty_like(xsum)
     da = torch.empty((M, K), dtype=xsum.dtype, device=xsum.device) if want_da else None
-    det = det_workspace(xsum.device) if _DETERMINISTIC else ()
-    call("fod_linear_add_norm_bwd_det" if det else "fod_linear_add_norm_bwd", dt(xsum), ptr(dy), ptr(xsum), ptr(mean),
-         ptr(rstd), ptr(gamma), ptr(w_t), ptr(dsum),
-         ptr(da), ptr(dgamma), ptr(dbeta), M, N, K, ptr(pre_g), ptr(pre_w_t), *det, stream(),
-         work=2.0 * M * N * K * ((1 if want_da else 0) + (1 if pre_g is not None else 0)), tag="fod_gemm_nt")
+    call_twin("fod_linear_add_norm_bwd", xsum.device, dt(xsum), ptr(dy), ptr(xsum), ptr(mean), ptr(rstd), ptr(gamma),
+              ptr(w_t), ptr(dsum), ptr(da), ptr(dgamma), ptr(dbeta), M, N, K, ptr(pre_g), ptr(pre_w_t),
+              work=2.0 * M * N * K * ((1 if want_da else 0) + (1 if pre_g is not None else 0)), tag="fod_gemm_nt")
     return dsum, da
 
 
@@ -903,10 +908,8 @@ def mlp2_mul_bwd(dout, table, q, h, w2_t, w1_t, dtable):
         ds = torch.empty((M, D), dtype=dout.dtype, device=dout.device)
     dh = torch.empty((M, D), dtype=dout.dtype, device=dout.device)
     dx = torch.empty((M, D), dtype=dout.dtype, device=dout.device)
-    det = det_workspace(dout.device) if _DETERMINISTIC else ()
-    call("fod_mlp2_mul_bwd_det" if det else "fod_mlp2_mul_bwd", dt(dout), ptr(dout), ptr(table), rows_t, ptr(q), ptr(h),
-         ptr(w2_t), ptr(w1_t), ptr(ds), ptr(dh),
-         ptr(dx), ptr(dtable), M, D, *det, stream(), work=4.0 * M * D * D, tag="fod_gemm_nt")
+    call_twin("fod_mlp2_mul_bwd", dout.device, dt(dout), ptr(dout), ptr(table), rows_t, ptr(q), ptr(h), ptr(w2_t),
+              ptr(w1_t), ptr(ds), ptr(dh), ptr(dx), ptr(dtable), M, D, work=4.0 * M * D * D, tag="fod_gemm_nt")
     return (ds if table is not None else dout), dh, dx
 
 
@@ -920,9 +923,8 @@ def layernorm_bwd(dy, xsum, mean, rstd, gamma, dgamma, dbeta, group_rows=0):
     for t in (gamma, dgamma, dbeta):
         _chk(t, "gamma/dgamma/dbeta", torch.float32); assert t.numel() == groups * D
     dx = torch.empty_like(dy)
-    det = det_workspace(dy.device) if _DETERMINISTIC else ()
-    call("fod_layernorm_bwd_det" if det else "fod_layernorm_bwd", dt(dy), ptr(dy), ptr(xsum), ptr(mean), ptr(rstd),
-         ptr(gamma), ptr(dx), ptr(dgamma), ptr(dbeta), rows, D, group_rows, *det, stream())
+    call_twin("fod_layernorm_bwd", dy.device, dt(dy), ptr(dy), ptr(xsum), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx),
+              ptr(dgamma), ptr(dbeta), rows, D, group_rows)
     return dx
 
 

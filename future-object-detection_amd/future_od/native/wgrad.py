@@ -391,12 +391,11 @@ class _WgradQueue:
     def _one_by_one(self, jobs, members, long=False):
         if long:
             for j in jobs:
-                det = ops.is_deterministic()
-                ws, ws_bytes = ops.tn_workspace(torch.device("cuda", torch.cuda.current_device())) \
-                    if ops.tn_may_use_partials_ws(j.M) or det else (None, 0)
-                L.call("fod_gemm_tn_acc_det" if det else "fod_gemm_tn_acc", L.BF16, j.G, j.ldg, j.X, j.ldx, j.dW, j.ldw,
-                       j.M, j.N1, j.K2, 0, j.colsum, 1, ws, ws_bytes, ops.stream(),
-                       work=2.0 * j.M * j.N1 * j.K2, tag="fod_gemm_tn_acc")
+                dev = torch.device("cuda", torch.cuda.current_device())
+                ws, ws_bytes = ops.tn_workspace(dev) \
+                    if ops.tn_may_use_partials_ws(j.M) or ops.is_deterministic() else (None, 0)
+                ops.call_twin("fod_gemm_tn_acc", dev, L.BF16, j.G, j.ldg, j.X, j.ldx, j.dW, j.ldw, j.M, j.N1, j.K2, 0,
+                              j.colsum, 1, ws, ws_bytes, work=2.0 * j.M * j.N1 * j.K2, tag="fod_gemm_tn_acc")
             return
         for i, j in enumerate(jobs):
             L.call("fod_gemm_tn_grouped", L.BF16, j.G, j.ldg, j.g_seg_cols, j.g_seg_stride, j.X, j.ldx, j.dW, j.ldw,

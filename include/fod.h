@@ -2,7 +2,7 @@
  * forward/backward hot path.
  *
  * The reference (atonderski/future-object-detection) has no native layer and no FFI: its hot path
- * is PyTorch ops called from future_od/models/*.py.  This library sits below that Python surface;
+ * is PyTorch ops called from the modules of future_od/models/.  This library sits below that Python surface;
  * every entry point names the reference computation it replaces (paths relative to the reference
  * root).  The host-side binding is ctypes (future-object-detection_amd/future_od/native/lib.py);
  * INTEGRATION.md shows the stub a reference maintainer would add.
