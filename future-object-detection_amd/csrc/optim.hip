@@ -3,7 +3,10 @@
 // future_od/trainer.py:186-188 and runs/_helper.py:84-107.  HBM-bound: reads p, g, m, v once, writes
 // p, m, v once.  Every tensor is processed as its dense storage order, so parameter, gradient and both
 // moments must share one memory layout (the host wrapper checks).
+// Behind them: the exponential moving average of the weights and its in-place swap (include/fod_ext.h), same geometry.
 #include "common.h"
+
+#include "../../include/fod_ext.h"
 
 namespace {
 
@@ -158,6 +161,79 @@ __global__ __launch_bounds__(256) void multi_adamw_kernel(const long* __restrict
   for (long i = tail + threadIdx.x; i < end; i += 256) update(p[i], g[i], m[i], v[i]);
 }
 
+// Exponential moving average of the weights over MANY tensors in one launch (include/fod_ext.h): the geometry of
+// multi_adamw_kernel -- the same CHUNK, the same block tables -- over (average, parameter) pairs.  HBM-bound at
+// 12 B / element: reads e and p, writes e.  The number of the update is read from device memory and every block forms
+// the weight itself, so a captured launch bakes in no host scalar that changes from step to step.
+FOD_DEVINL float ema_weight(long long u, float decay, int warmup) {
+  double d = (double)decay;
+  if (warmup) d = fmin(d, (1.0 + (double)u) / (10.0 + (double)u));
+  return (float)(1.0 - d);
+}
+
+// e + w * (p - e), each of the three operations rounded on its own: the float32 restatement in numpy gives the same
+// bits.  The pragma is what keeps the product and the sum apart -- __fmul_rn / __fadd_rn are plain operators in
+// inline functions here, and hipcc's default contraction fused them into v_pk_fma_f32 / v_fmac_f32 all the same.
+FOD_DEVINL float ema_step(float e, float p, float w) {
+#pragma clang fp contract(off)
+  const float diff = p - e;
+  const float move = w * diff;
+  return e + move;
+}
+
+__global__ __launch_bounds__(256) void multi_ema_kernel(const long* __restrict__ pairs, const long* __restrict__ numel,
+                                                        const int* __restrict__ blk_tensor,
+                                                        const int* __restrict__ blk_chunk,
+                                                        const long long* __restrict__ updates, float decay, int warmup) {
+  const float w = ema_weight(*updates, decay, warmup);
+  const int t = blk_tensor[blockIdx.x];
+  const long base = (long)blk_chunk[blockIdx.x] * CHUNK;
+  const long end = min(numel[t], base + CHUNK);
+  float* e = reinterpret_cast<float*>(pairs[t * 2 + 0]);
+  const float* p = reinterpret_cast<const float*>(pairs[t * 2 + 1]);
+  long tail = base;
+  if (((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(p)) & 15) == 0) {      // 16 bytes per lane and stream
+    const long end4 = base + ((end - base) & ~3L);
+    for (long i = base + 4 * threadIdx.x; i < end4; i += 1024) {
+      float4 eq = *reinterpret_cast<float4*>(e + i);
+      const float4 pq = *reinterpret_cast<const float4*>(p + i);
+      eq.x = ema_step(eq.x, pq.x, w);
+      eq.y = ema_step(eq.y, pq.y, w);
+      eq.z = ema_step(eq.z, pq.z, w);
+      eq.w = ema_step(eq.w, pq.w, w);
+      *reinterpret_cast<float4*>(e + i) = eq;
+    }
+    tail = end4;
+  }
+  for (long i = tail + threadIdx.x; i < end; i += 256) e[i] = ema_step(e[i], p[i], w);
+}
+
+// The two tensors of every pair change contents, bit for bit (words are moved, never interpreted).
+__global__ __launch_bounds__(256) void multi_swap_kernel(const long* __restrict__ pairs, const long* __restrict__ numel,
+                                                         const int* __restrict__ blk_tensor,
+                                                         const int* __restrict__ blk_chunk) {
+  const int t = blk_tensor[blockIdx.x];
+  const long base = (long)blk_chunk[blockIdx.x] * CHUNK;
+  const long end = min(numel[t], base + CHUNK);
+  unsigned* a = reinterpret_cast<unsigned*>(pairs[t * 2 + 0]);
+  unsigned* b = reinterpret_cast<unsigned*>(pairs[t * 2 + 1]);
+  long tail = base;
+  if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) {
+    const long end4 = base + ((end - base) & ~3L);
+    for (long i = base + 4 * threadIdx.x; i < end4; i += 1024) {
+      const uint4 aq = *reinterpret_cast<const uint4*>(a + i), bq = *reinterpret_cast<const uint4*>(b + i);
+      *reinterpret_cast<uint4*>(a + i) = bq;
+      *reinterpret_cast<uint4*>(b + i) = aq;
+    }
+    tail = end4;
+  }
+  for (long i = tail + threadIdx.x; i < end; i += 256) {
+    const unsigned av = a[i], bv = b[i];
+    a[i] = bv;
+    b[i] = av;
+  }
+}
+
 }  // namespace
 
 extern "C" int fod_multi_sqnorm_acc(const long* ptrs, const long* numel, const int* blk_tensor, const int* blk_chunk,
@@ -189,3 +265,21 @@ extern "C" int fod_multi_adamw(const long* ptrs, const long* numel, const float*
 }
 
 extern "C" int fod_multi_chunk(void) { return CHUNK; }
+
+extern "C" int fod_multi_ema(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk,
+                             int nblocks, const long long* updates_dev, float decay, int warmup, hipStream_t stream) {
+  FOD_REQUIRE(pairs && numel && blk_tensor && blk_chunk && updates_dev && nblocks > 0, "multi_ema: bad args");
+  FOD_REQUIRE(decay >= 0.f && decay <= 1.f, "multi_ema: decay %g is not in [0, 1]", (double)decay);
+  hipLaunchKernelGGL(multi_ema_kernel, dim3(nblocks), dim3(256), 0, stream, pairs, numel, blk_tensor, blk_chunk,
+                     updates_dev, decay, warmup);
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}
+
+extern "C" int fod_multi_swap(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk,
+                              int nblocks, hipStream_t stream) {
+  FOD_REQUIRE(pairs && numel && blk_tensor && blk_chunk && nblocks > 0, "multi_swap: bad args");
+  hipLaunchKernelGGL(multi_swap_kernel, dim3(nblocks), dim3(256), 0, stream, pairs, numel, blk_tensor, blk_chunk);
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}

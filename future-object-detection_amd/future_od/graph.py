@@ -260,10 +260,12 @@ class GraphedStep:
     def _snapshot(self):
         opt = self.opt
         params = [p for grp in opt.param_groups for p in grp["params"]]
+        ema = getattr(opt, "_ema", None)             # an attached weight average is advanced by every warm-up step too
         return {"params": [(p, p.detach().clone()) for p in params],
                 "moments": {p: (st["exp_avg"].clone(), st["exp_avg_sq"].clone())
                             for p, st in opt.state.items() if "exp_avg" in st},
-                "step_no": getattr(opt, "_step_no", 0)}
+                "step_no": getattr(opt, "_step_no", 0),
+                "ema": (ema, ema.snapshot()) if ema is not None else None}
 
     def _restore(self, snap):
         opt = self.opt
@@ -282,6 +284,9 @@ class GraphedStep:
         opt._step_no = snap["step_no"]
         if getattr(opt, "_dev_step", None) is not None:
             opt._dev_step.fill_(float(snap["step_no"]))
+        if snap["ema"] is not None:
+            ema, saved = snap["ema"]
+            ema.restore(saved)                       # tensors and the device-side count of updates, in place
         prepared.PREP.mark_stale()
 
     def _capture(self, data):
@@ -387,6 +392,9 @@ class GraphedStep:
     def __call__(self, data, sync=True):
         """One optimizer step on `data`.  `sync=False` (data parallel only) skips the gradient average -- the ranks'
         parameters then DIVERGE; it exists to time the step without communication."""
+        ema = getattr(self.opt, "_ema", None)
+        if ema is not None and ema.is_applied:
+            raise RuntimeError("GraphedStep inside WeightEMA.applied(): the model holds the averaged weights")
         token = getattr(self.opt, "_state_token", 0)
         if token != getattr(self, "_opt_token", token):
             # optimizer.load_state_dict() replaced the moment tensors: capture anew.  Once per checkpoint load: no replay

@@ -14,6 +14,8 @@ class FodError(RuntimeError):
 
 
 HEADER_PATH = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "..", "include", "fod.h"))
+# entry points added without touching fod.h (the header says why); read into tables of their own, see _read_ext()
+EXT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "fod_ext.h")
 
 # kind -> ctypes type.  Every pointer (pointer typedefs and pointers to structs included) travels as a plain address.
 CTYPE = {"pointer": C.c_void_p, "int": C.c_int, "long": C.c_long, "float": C.c_float, "size_t": C.c_size_t,
@@ -42,12 +44,21 @@ def _value(expr, where):
         raise FodError(f"fod.h: '{where}' is not an integer expression") from None
 
 
-def parse(text):
-    """(prototypes, structs, constants) of a header text:
+_POINTER_TYPEDEF = r"\btypedef\s+struct\s+\w+\s*\*\s*(\w+)\s*;"
+
+
+def pointer_typedefs(text):
+    """The names a header text declares as `typedef struct x* name;` -- what a second header that uses them is read with."""
+    return set(re.findall(_POINTER_TYPEDEF, re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)))
+
+
+def parse(text, pointer_types=()):
+    """(prototypes, structs, constants) of a header text (`pointer_types`: pointer typedefs it may use without declaring
+    them, i.e. those of a header it includes):
     prototypes: name -> (return kind, [argument kinds]) of every `int|size_t fod_*(...)` declaration, in header order
     structs:    name -> [(field, kind)] of every `typedef struct fod_* {...} fod_*`, in declaration order
     constants:  name -> int for every enumerator of the anonymous enums and every `#define` with an integer body"""
-    prototypes, structs, constants, pointer_types = {}, {}, {}, set()
+    prototypes, structs, constants, pointer_types = {}, {}, {}, set(pointer_types)
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#\s*ifdef __cplusplus.*?#\s*endif[^\n]*$", "", text, flags=re.S | re.M)    # extern "C" { / }
 
@@ -73,7 +84,7 @@ def parse(text):
     def pointer_typedef(m):
         pointer_types.add(m.group(1))
         return ""
-    text = re.sub(r"\btypedef\s+struct\s+\w+\s*\*\s*(\w+)\s*;", pointer_typedef, text)
+    text = re.sub(_POINTER_TYPEDEF, pointer_typedef, text)
 
     def struct(m):
         name, fields = m.group(1), []
@@ -143,4 +154,21 @@ def _read():
         return parse(f.read())
 
 
+def _read_ext():
+    """The prototypes of include/fod_ext.h, read with fod.h's pointer typedefs.  It adds entry points and nothing else:
+    a struct, a constant or a name fod.h has is refused."""
+    for path in (HEADER_PATH, EXT_HEADER_PATH):
+        if not os.path.isfile(path):
+            raise FodError(f"{path} not found: the binding is built from the header, there is no second copy")
+    with open(HEADER_PATH) as f:
+        known = pointer_typedefs(f.read())
+    with open(EXT_HEADER_PATH) as f:
+        prototypes, structs, constants = parse(f.read(), known)
+    extra = sorted(structs) + sorted(constants) + sorted(set(prototypes) & set(PROTOTYPES))
+    if extra:
+        raise FodError(f"fod_ext.h declares {', '.join(extra)}: it holds new prototypes only")
+    return prototypes
+
+
 PROTOTYPES, STRUCTS, CONSTANTS = _read()
+EXT_PROTOTYPES = _read_ext()

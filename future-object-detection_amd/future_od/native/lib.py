@@ -1,4 +1,4 @@
-"""ctypes binding of libfod_hip.so (include/fod.h).
+"""ctypes binding of libfod_hip.so (include/fod.h, and the later entry points of include/fod_ext.h).
 
 The HIP library IS the compute path: if it is missing or its ABI disagrees, importing this
 module raises -- there is no CPU or eager-PyTorch fallback behind these calls.
@@ -37,10 +37,13 @@ EXPORTS = sorted(abi.PROTOTYPES)
 # name -> argtypes of the entry points call() and the fast-call wrappers serve.  Struct arguments travel as addresses
 # (C.addressof / None): plain ints are what the fast-call wrappers take.
 SIGNATURES = {name: [abi.CTYPE[kind] for kind in args] for name, args in abi.served(abi.PROTOTYPES).items()}
+# the same two tables for include/fod_ext.h; call() serves these through ctypes (there are no fast-call wrappers of them)
+EXT_EXPORTS = sorted(abi.EXT_PROTOTYPES)
+EXT_SIGNATURES = {name: [abi.CTYPE[kind] for kind in args] for name, args in abi.served(abi.EXT_PROTOTYPES).items()}
 
 
 def _typed(lib, name):
-    ret, args = abi.PROTOTYPES[name]
+    ret, args = abi.PROTOTYPES[name] if name in abi.PROTOTYPES else abi.EXT_PROTOTYPES[name]
     fn = getattr(lib, name)
     fn.restype, fn.argtypes = abi.CTYPE[ret], [abi.CTYPE[kind] for kind in args]
     return fn
@@ -59,7 +62,9 @@ def _load():
     built = _typed(lib, "fod_abi_version")()
     if built != abi.CONSTANTS["FOD_ABI_VERSION"]:
         raise FodError(f"libfod_hip.so ABI {built} != header ABI {abi.CONSTANTS['FOD_ABI_VERSION']}: rebuild")
-    for name in EXPORTS:
+    for name in EXPORTS + EXT_EXPORTS:
+        if not hasattr(lib, name):
+            raise FodError(f"libfod_hip.so does not export {name}: rebuild")
         _typed(lib, name)
     return lib
 
@@ -117,6 +122,7 @@ def _load_fast():
 
 FAST = _load_fast()
 _ENTRY = {name: FAST.get(name, getattr(LIB, name)) for name in SIGNATURES}
+_ENTRY.update({name: getattr(LIB, name) for name in EXT_SIGNATURES})
 
 
 def _plain_call(name, *args):

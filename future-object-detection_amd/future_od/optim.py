@@ -3,7 +3,12 @@
 Same update rule and state layout as torch.optim.AdamW (the reference's optimizer, reference
 runs/_helper.py:105) and torch.nn.utils.clip_grad_norm_ (reference future_od/trainer.py:186-187);
 `state_dict()` / `load_state_dict()` interchange with torch's, so reference checkpoints resume.
+
+`WeightEMA` is an exponential moving average of the weights kept by one more launch per step behind the AdamW launch
+(`FusedAdamW.attach_ema`), so a captured step carries it along; `ema.applied()` puts the averaged weights under the
+model for evaluation.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -32,6 +37,13 @@ class FusedAdamW(torch.optim.Optimizer):
         self._bias_dev = None        # device-resident bias corrections (captured steps, see future_od/graph.py)
         self._dev_step = self._dev_betas = None
         self.last_grad_norm = None
+        self._ema = None             # a WeightEMA updated behind every AdamW launch (attach_ema)
+
+    def attach_ema(self, ema):
+        """Every step() from now on ends with one update of `ema` (a WeightEMA of the model this optimizer trains),
+        launched behind the AdamW launch on the same stream -- inside a captured step too, since it sits in step().
+        None detaches it.  A step that was captured before keeps what it recorded."""
+        self._ema = ema
 
     def zero_grad(self, set_to_none=True):
         """Drops the gradients (set_to_none) and recycles the zero arena they were accumulated in."""
@@ -219,10 +231,14 @@ class FusedAdamW(torch.optim.Optimizer):
         # operand derived from a parameter (compute-dtype / transposed / BN-folded copies) is now out of date
         from future_od.native import prepared
         prepared.PREP.mark_stale()
+        if self._ema is not None:
+            self._ema.update()
 
     @torch.no_grad()
     def step(self, closure=None):
         assert closure is None
+        if self._ema is not None and self._ema.is_applied:
+            raise RuntimeError("FusedAdamW.step() inside WeightEMA.applied(): the model holds the averaged weights")
         betas, eps = self.param_groups[0]["betas"], self.param_groups[0]["eps"]
         for grp in self.param_groups:
             assert grp["betas"] == betas and grp["eps"] == eps    # lr / weight decay are per tensor, these are shared
@@ -283,3 +299,165 @@ class FusedAdamW(torch.optim.Optimizer):
         if getattr(self, "_dev_step", None) is not None:              # that baked the old ones in must be re-captured
             self._dev_step.fill_(float(self._step_no))
         self._plan = None
+
+
+def _dense(t):
+    """Non-overlapping and without holes: its storage order is one run of numel() elements."""
+    n = 1
+    for stride, size in sorted((s, d) for s, d in zip(t.stride(), t.shape) if d > 1):
+        if stride != n:
+            return False
+        n *= size
+    return True
+
+
+class WeightEMA:
+    """ema = WeightEMA(model, decay=0.9998, warmup=True);  optimizer.attach_ema(ema)
+
+    An f32 copy of every parameter of `model` that requires a gradient, initialised to its current value and moved
+    towards it after every optimizer step: e += w * (p - e), w = 1 - d, d = min(decay, (1 + u) / (10 + u)) with warm-up
+    (u = number of the update, so the first updates are not dominated by the initial weights) and d = decay without.
+    One `fod_multi_ema` launch over all tensors.  The count of updates lives on the device only, advanced on the stream:
+    a captured step advances it by replaying, and python-side code that runs while nothing executes (a capture) cannot
+    miscount.  Buffers (BatchNorm statistics) and frozen parameters are not averaged: evaluation under `applied()` reads
+    the model's own.
+
+    `decay` and `warmup` are launch arguments: a step captured with them keeps them."""
+
+    def __init__(self, model, decay=0.9998, warmup=True):
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"WeightEMA: decay {decay} is not in [0, 1]")
+        self.decay, self.warmup = float(decay), bool(warmup)
+        self._model = model
+        named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        if not named:
+            raise L.FodError("WeightEMA: the model has no parameter that requires a gradient")
+        dev = named[0][1].device
+        for n, p in named:
+            if p.dtype != torch.float32 or not p.is_cuda or p.device != dev:
+                raise L.FodError(f"WeightEMA handles float32 parameters on one device only ({n}: {p.dtype}, {p.device})")
+            if not _dense(p):
+                raise L.FodError(f"WeightEMA: parameter {n} is not dense (shape {tuple(p.shape)}, strides {p.stride()})")
+        self._names = [n for n, _ in named]
+        self._params = [p for _, p in named]
+        with torch.no_grad():
+            self._ema = [torch.empty_like(p, memory_format=torch.preserve_format).copy_(p) for p in self._params]
+        self._updates = torch.zeros(1, dtype=torch.int64, device=dev)
+        chunk = L.LIB.fod_multi_chunk()
+        bt, bc = [], []
+        for t, p in enumerate(self._params):
+            for c in range((p.numel() + chunk - 1) // chunk):
+                bt.append(t)
+                bc.append(c)
+        host = (torch.tensor([[e.data_ptr(), p.data_ptr()] for e, p in zip(self._ema, self._params)], dtype=torch.int64),
+                torch.tensor([p.numel() for p in self._params], dtype=torch.int64),
+                torch.tensor(bt, dtype=torch.int32), torch.tensor(bc, dtype=torch.int32))
+        up = [FusedAdamW._upload(x, dev) for x in host]
+        self._tab = tuple(u[0] for u in up)
+        self._keep = [u[1] for u in up]              # the uploads read the pinned copies when they run
+        self._nblocks = len(bt)
+        self._applied = False
+
+    # ---- the average ---------------------------------------------------------------------------------------------
+    @property
+    def num_updates(self):
+        """Read from the device (synchronises): for logs, checkpoints and tests, not for the step."""
+        return int(self._updates.item())
+
+    @property
+    def is_applied(self):
+        return self._applied
+
+    def named_tensors(self):
+        """(parameter name, averaged tensor) pairs; the tensors are the live ones."""
+        return list(zip(self._names, self._ema))
+
+    @torch.no_grad()
+    def update(self):
+        """One update towards the parameters' current values, on the current stream (what FusedAdamW.step() ends with)."""
+        if self._applied:
+            raise RuntimeError("WeightEMA.update() inside applied(): the model holds the averaged weights")
+        pairs, numel, bt, bc = self._tab
+        self._updates.add_(1)                        # on the stream: the kernel reads the number of this update
+        L.call("fod_multi_ema", ptr(pairs), ptr(numel), ptr(bt), ptr(bc), self._nblocks, ptr(self._updates), self.decay,
+               int(self.warmup), stream())
+        # a capture that recorded the launch keeps what it reads (the parameters are the model's own)
+        capture.hold_or_ask("weight ema", (self._tab, self._ema, self._updates))
+
+    def _swap(self):
+        from future_od.native import prepared
+        pairs, numel, bt, bc = self._tab
+        L.call("fod_multi_swap", ptr(pairs), ptr(numel), ptr(bt), ptr(bc), self._nblocks, stream())
+        # the parameters were rewritten through raw pointers: the kernels' prepared copies are out of date
+        prepared.PREP.mark_stale()
+
+    @contextlib.contextmanager
+    def applied(self):
+        """with ema.applied(): ...  -- the model's own tensors hold the averaged weights (and the EMA's tensors the raw
+        ones) from entry to exit: one swap launch each way, no copy, no address changes.  Eager passes, inference graphs
+        captured before or after, and model.state_dict() all read the averaged weights inside.  Optimizer steps, the
+        EMA's own state and nesting are refused inside."""
+        if self._applied:
+            raise RuntimeError("WeightEMA.applied() does not nest")
+        self._swap()
+        self._applied = True
+        try:
+            yield self
+        finally:
+            self._swap()
+            self._applied = False
+
+    # ---- what GraphedStep rolls back with its warm-up steps --------------------------------------------------------
+    def snapshot(self):
+        return [e.clone() for e in self._ema], self._updates.clone()
+
+    @torch.no_grad()
+    def restore(self, snap):
+        for e, old in zip(self._ema, snap[0]):
+            e.copy_(old)
+        self._updates.copy_(snap[1])
+
+    # ---- state -----------------------------------------------------------------------------------------------------
+    def _not_applied(self, what):
+        if self._applied:
+            raise RuntimeError(f"WeightEMA.{what} inside applied(): the EMA's tensors hold the raw weights")
+
+    @torch.no_grad()
+    def reset(self):
+        """Back to the parameters' current values, no update counted (in place)."""
+        self._not_applied("reset()")
+        for e, p in zip(self._ema, self._params):
+            e.copy_(p)
+        self._updates.zero_()
+
+    def state_dict(self):
+        self._not_applied("state_dict()")
+        return {"decay": self.decay, "warmup": self.warmup, "num_updates": self.num_updates,
+                "params": {n: e.detach().clone() for n, e in zip(self._names, self._ema)}}
+
+    @torch.no_grad()
+    def load_state_dict(self, state):
+        """Copies IN PLACE (captured graphs stay valid).  Names and shapes must be exactly this EMA's; `decay` and
+        `warmup` stay the constructor's (they are launch arguments of steps that may already be captured)."""
+        self._not_applied("load_state_dict()")
+        params = state["params"]
+        missing, extra = sorted(set(self._names) - set(params)), sorted(set(params) - set(self._names))
+        if missing or extra:
+            raise L.FodError(f"WeightEMA.load_state_dict: missing {missing}, unexpected {extra}")
+        for n, e in zip(self._names, self._ema):
+            if tuple(params[n].shape) != tuple(e.shape):
+                raise L.FodError(f"WeightEMA.load_state_dict: {n} has shape {tuple(params[n].shape)}, "
+                                 f"expected {tuple(e.shape)}")
+        for n, e in zip(self._names, self._ema):
+            e.copy_(params[n])
+        self._updates.fill_(int(state["num_updates"]))
+
+    def model_state_dict(self):
+        """The model's full state_dict() with the averaged values in place of the averaged parameters: loads straight
+        into a fresh model."""
+        self._not_applied("model_state_dict()")
+        sd = self._model.state_dict()
+        for n, e in zip(self._names, self._ema):
+            assert n in sd, n
+            sd[n] = e.detach().clone()
+        return sd

@@ -1,6 +1,7 @@
 """Training / evaluation loop with the reference Trainer's constructor, checkpoint format and printed
 metrics (reference future_od/trainer.py), driving the HIP-backed model.  wandb and the PNG
 visualisation are optional imports: absent packages disable those features instead of failing."""
+import contextlib
 import os
 
 import torch
@@ -29,7 +30,7 @@ class Trainer:
     def __init__(self, model, optimizer, lr_sched, train_loader, val_loaders, checkpoint_path, visualization_path,
                  save_name, device, print_interval, visualization_epochs, visualization_iterations, category_dict,
                  checkpoint_epochs=None, gradient_clip_value=None, distributed=False, is_master=False,
-                 wandb_config=WandBConfig(), max_norm=0.0):
+                 wandb_config=WandBConfig(), max_norm=0.0, ema=None):
         self._model = model
         self._model_no_ddp = _unwrap(model)
         self._optimizer, self._lr_sched = optimizer, lr_sched
@@ -56,6 +57,11 @@ class Trainer:
         # an optimizer that clips inside its fused update (future_od.optim.FusedAdamW) makes the separate
         # clip_grad_norm_ pass unnecessary
         self._optimizer_clips = getattr(optimizer, "max_norm", 0.0) > 0
+        # an exponential moving average of the weights (future_od.optim.WeightEMA): updated inside the optimizer's step,
+        # evaluated under and saved with the checkpoints.  None: nothing changes
+        self._ema = ema
+        if ema is not None:
+            optimizer.attach_ema(ema)
 
     # ------------------------------------------------------------------ public API
     def train(self, max_epochs):
@@ -99,7 +105,9 @@ class Trainer:
 
     def _run_eval(self):
         self._model.train(False)
-        with torch.no_grad():
+        if self._ema is not None:
+            print(f"Evaluating under the weight EMA (decay {self._ema.decay}, {self._ema.num_updates} updates).")
+        with self._ema.applied() if self._ema is not None else contextlib.nullcontext(), torch.no_grad():
             for name, loader in self._val_loaders.items():
                 if hasattr(self._model_no_ddp._model, "drop_mode"):
                     self._model_no_ddp._model.drop_mode = name
@@ -273,9 +281,14 @@ class Trainer:
         state = {"epoch": self._epoch, "net_type": type(self._model_no_ddp).__name__,
                  "net": self._model_no_ddp.state_dict(), "optimizer": self._optimizer.state_dict(),
                  "lr_schedule": self._lr_sched.state_dict(), "stats": self._stats, "device": self._device}
+        if self._ema is not None:
+            state["ema"] = self._ema.state_dict()
         torch.save(state, f"{self._checkpoint_path}/{self._save_name}.pth.tar")
         if is_final:
-            torch.save({"net": state["net"]}, f"{self._checkpoint_path}/{self._save_name}_final.pth.tar")
+            final = {"net": state["net"]}
+            if self._ema is not None:
+                final["net_ema"] = self._ema.model_state_dict()      # loads into a model like "net" does
+            torch.save(final, f"{self._checkpoint_path}/{self._save_name}_final.pth.tar")
 
     def load_checkpoint(self, checkpoint: str = None, load_only_net=False):
         print(f"Loading checkpoint: {checkpoint}")
@@ -297,4 +310,10 @@ class Trainer:
             self._optimizer.load_state_dict(ck["optimizer"])
             self._stats = ck["stats"]
             self._lr_sched.load_state_dict(ck["lr_schedule"])
+        if self._ema is not None:
+            # (a file's "ema" is simply not read by a trainer without one)
+            if not load_only_net and "ema" in ck:
+                self._ema.load_state_dict(ck["ema"])
+            else:
+                self._ema.reset()          # no average in the file, or only the weights were asked for: start from them
         print(f"Loaded: {path}")

@@ -58,6 +58,13 @@ def get_trainer(args, config, detr_args, lr_sched, model, optimizer, train_loade
     from future_od.trainer import Trainer
     from future_od.utils.wandb import WandBConfig
     from runs._loader import CATEGORY_DICT
+    ema = None
+    if getattr(args, "ema_decay", None):
+        # the averaged weights are evaluated and saved beside the raw ones (future_od/optim.py: WeightEMA); the names
+        # are those of the checkpoint's "net"
+        from future_od.optim import WeightEMA
+        bare = model.module if isinstance(model, torch.nn.parallel.DistributedDataParallel) else model
+        ema = WeightEMA(bare, decay=args.ema_decay)
     return Trainer(
         model=model, optimizer=optimizer, lr_sched=lr_sched, train_loader=train_loader, val_loaders=val_loaders,
         checkpoint_path=config["checkpoint_path"],
@@ -66,4 +73,4 @@ def get_trainer(args, config, detr_args, lr_sched, model, optimizer, train_loade
         print_interval=25, visualization_epochs=set(int(i) for i in np.linspace(1, args.epochs, 10)),
         visualization_iterations=[0], category_dict=CATEGORY_DICT, distributed=args.distributed,
         is_master=(args.world_rank == 0),
-        wandb_config=WandBConfig(enabled=False), max_norm=detr_args.max_norm)
+        wandb_config=WandBConfig(enabled=False), max_norm=detr_args.max_norm, ema=ema)

@@ -52,6 +52,9 @@ def main(argv=None):
     parser.add_argument("--out", default="/tmp/fod_runs", help="checkpoint / visualisation directory")
     parser.add_argument("--stage_sizes", default=None,
                         help="override the two stages, 'H1xW1:B1,H2xW2:B2' (global batches), e.g. for a smoke run")
+    parser.add_argument("--ema-decay", dest="ema_decay", default=None, type=float,
+                        help="keep an exponential moving average of the weights with this decay (e.g. 0.9998): "
+                             "evaluation runs under it, checkpoints carry it; default: none")
     args = parser.parse_args(argv)
     if args.stage_sizes:
         args.stages = tuple((tuple(int(v) for v in sz.split("x")), int(b))

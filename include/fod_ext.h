@@ -1,0 +1,43 @@
+/* fod_ext.h -- entry points of libfod_hip.so that came after include/fod.h was closed.
+ *
+ * Why a second header: fod.h is pinned as a whole -- its prototypes, structs and served entry points are counted by
+ * the tests that keep the binding (future_od/native/abi.py, lib.py) and the fast-call wrappers equal to it, and those
+ * counts are a yardstick that later work does not move.  An entry point that is added without changing anything fod.h
+ * declares goes here instead.  Same dialect, same conventions (fod.h's opening comment: device pointers, asynchronous on
+ * `stream`, nothing allocated, no state kept, 0 on success and the text via fod_last_error()), read by the same reader:
+ * abi.py hands it fod.h's pointer typedefs and keeps its prototypes in tables of their own (EXT_PROTOTYPES), lib.py
+ * types and binds them so that lib.call(name, ...) serves them.  This header declares prototypes only: no struct, no
+ * constant, no name fod.h has.  FOD_ABI_VERSION (fod.h) counts for both.
+ */
+#ifndef FOD_EXT_H_
+#define FOD_EXT_H_
+
+#include "fod.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Exponential moving average of the weights over many tensors in ONE launch (the reference has none; what a
+ * DETR-family trainer keeps beside its optimizer, torch: `ema.lerp_(p, 1 - d)` per tensor).  Device tables with the
+ * geometry of fod_multi_adamw:
+ *   pairs i64 [T,2] = {average, parameter} f32 pointers (same dense layout each), numel i64 [T]; block b works on
+ *   elements [blk_chunk[b]*C, +C) of pair blk_tensor[b], C = fod_multi_chunk().
+ * updates_dev: i64 device scalar, the number u >= 1 of THIS update -- advanced on the stream by the caller before the
+ * launch, so a captured launch bakes in no count.  Every block forms the weight itself, in double:
+ *   d = warmup ? min((double)decay, (1 + u) / (10 + u)) : (double)decay,   w = (float)(1 - d)
+ * and every element becomes  e = e + w * (p - e)  with the subtraction, the product and the sum each rounded to f32
+ * (no fused multiply-add): a float32 restatement gives the same bits.  Reads p and e, writes e (12 B / element).
+ * 16-byte accesses where both tensors of a pair are 16-byte aligned, a scalar tail; 4-byte accesses otherwise.
+ * decay outside [0, 1] is FOD_ERR_ARG. */
+int fod_multi_ema(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk, int nblocks,
+                  const long long* updates_dev, float decay, int warmup, fod_stream_t stream);
+/* The two tensors of every pair exchange their contents, bit for bit (words are moved, not interpreted); twice is the
+ * identity.  Same tables as fod_multi_ema.  The tensors of a pair must not overlap. */
+int fod_multi_swap(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk, int nblocks,
+                   fod_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* FOD_EXT_H_ */
