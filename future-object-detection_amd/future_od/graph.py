@@ -38,6 +38,7 @@ from future_od.native import functional as Fn
 from future_od.native import ops
 from future_od.native import prepared
 from future_od.native import wgrad
+from future_od.switches import SW
 
 
 def _stage_inputs(g, data):
@@ -115,13 +116,12 @@ class GraphedStep:
         # backbone's kernels for every CU, where a ring step of a real group runs on a few channels.  So: on for
         # world > 1 with RCCL (FOD_GRAPH_OVERLAP=0 turns it off), off at one rank and for gloo (a two-rank gloo
         # rehearsal with full-size gradients stalled in the asynchronous collective, 6.7 s per step, round 2).
-        import os
-        env = os.environ.get("FOD_GRAPH_OVERLAP")
+        env = SW.FOD_GRAPH_OVERLAP                        # None (not set) / True ("1") / False (any other text)
         # default (round 3): ON for a real multi-rank RCCL group, off for one rank and for gloo -- see the comment above
         # and profiles/r03e_ddp_overlap_probe_1rank.txt
-        self.overlap = (env == "1") if env is not None else (self.ddp and self.world > 1 and self._native_avg())
-        self.overlap_mode = os.environ.get("FOD_GRAPH_OVERLAP_MODE", "async")     # "after": experiment, see __call__
-        self.grad_bf16 = os.environ.get("FOD_GRAD_BF16", "0") == "1"
+        self.overlap = env if env is not None else (self.ddp and self.world > 1 and self._native_avg())
+        self.overlap_mode = SW.FOD_GRAPH_OVERLAP_MODE     # "after": experiment, see __call__
+        self.grad_bf16 = SW.FOD_GRAD_BF16
         self._bf16_bufs = {}
 
     def broadcast_parameters(self, src=0):
@@ -411,8 +411,8 @@ class GraphedStep:
         self.opt.sync_hyperparams()                       # the current plan (eager steps) ...
         if g.get("plan") is not None:
             self.opt.sync_hyperparams(g["plan"])          # ... and the one baked into this graph, if it is another
-        import os, time
-        dbg = os.environ.get("FOD_GRAPH_TIMING") == "1"
+        import time
+        dbg = SW.FOD_GRAPH_TIMING
         def tick(label, _t=[time.perf_counter()]):
             if dbg:
                 torch.cuda.synchronize()

@@ -16,6 +16,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from future_od.native import ops
+from future_od.switches import SW
 
 
 class HungarianMatcher(nn.Module):
@@ -151,8 +152,7 @@ class _AsyncLap:
         match = torch.empty((Lv, B, M), dtype=torch.int32, device=cost.device)
         stream = torch.cuda.current_stream(cost.device).cuda_stream
         inline = False
-        import os
-        for _ in range(0 if os.environ.get("FOD_ASYNC_MATCH") == "2" else 8):      # "2": always park (tests)
+        for _ in range(0 if SW.FOD_ASYNC_MATCH == "2" else 8):      # "2": always park (tests)
             if event.query():
                 # the GPU has already delivered the cost matrices: the step is host-bound here, nothing to overlap --
                 # solve inline (measured: parking + worker cost a host-bound step ~8 %, and gain a GPU-bound one 15 %)
@@ -225,8 +225,7 @@ def check_device_matcher(device):
 
 def device_matching_enabled(device):
     """The matcher runs entirely on the GPU by default (FOD_DEVICE_MATCH=0: host solver, asynchronous or blocking)."""
-    import os
-    return torch.device(device).type == "cuda" and os.environ.get("FOD_DEVICE_MATCH", "1") != "0"
+    return torch.device(device).type == "cuda" and SW.FOD_DEVICE_MATCH
 
 
 # Work that does not depend on the matches (post-processing, AP bookkeeping) can be queued between the cost matrices'
@@ -283,8 +282,7 @@ def _stream_wait_supported(device):
 def async_matching_enabled(device):
     """The asynchronous matcher needs a GPU stream to park; FOD_ASYNC_MATCH=0 restores the host sync, =2 parks even
     when the cost matrices have already arrived (so that tests reach the worker path on tiny inputs)."""
-    import os
-    return (torch.device(device).type == "cuda" and os.environ.get("FOD_ASYNC_MATCH", "1") != "0"
+    return (torch.device(device).type == "cuda" and SW.FOD_ASYNC_MATCH != "0"
             and _stream_wait_supported(device))
 
 

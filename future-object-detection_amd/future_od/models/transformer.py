@@ -17,13 +17,13 @@ Dropout: the reference applies dropout(0.1) in training mode.  These modules imp
 eval-mode graph (dropout = identity) in both modes for now -- see DESIGN.md "Gaps".
 """
 import math
-import os
 from typing import List, Optional
 
 import torch
 from torch import Tensor, nn
 
 from future_od.native import functional as Fn
+from future_od.switches import SW
 
 
 def _reset_parameters(parameters):
@@ -152,8 +152,6 @@ class SlotToSlotAttention(Attention):
 # would be per frame; by default train mode therefore runs the general form (keys = the one token) and is mask-for-mask
 # the reference's computation.  FOD_IMU_COLLAPSED_TRAIN=1 keeps the collapsed form in train mode too (faster, per-frame
 # masks).  Eval mode (the benchmark, and every parity fixture) is unaffected: without dropout the two forms are equal.
-IMU_COLLAPSED_TRAIN = os.environ.get("FOD_IMU_COLLAPSED_TRAIN", "0") == "1"
-
 
 class EgodeepAttention(nn.Module):
     """Attention to the per-frame IMU token(s) (reference transformer.py:85-119).
@@ -165,7 +163,7 @@ class EgodeepAttention(nn.Module):
 
     def per_token_masks(self):
         """True when the one-key case must run the general form: dropout is active and its masks are per token."""
-        return self.training and self.droprate > 0.0 and not IMU_COLLAPSED_TRAIN
+        return self.training and self.droprate > 0.0 and not SW.FOD_IMU_COLLAPSED_TRAIN
 
     def __init__(self, D, Nhead, droprate, Dff=None):
         super().__init__()
@@ -233,7 +231,7 @@ class SlotToImageAttention(Attention):
         `keep`: also return x for the residual step (one autograd consumer of x instead of two, Fn.LinearKeepFn)."""
         _no_masks(attn_mask, key_padding_mask)
         B, M, D = x.shape
-        if keep and qc_pre is not None and Fn.FUSED_LINEAR_PRE:
+        if keep and qc_pre is not None and SW.FOD_FUSED_LINEAR_PRE:
             # query_content(x) is an output of the node that produced x (_add_norm(then=...)); so is its backward
             x_keep, qc = x, qc_pre.view(B, M, D)
         elif keep:
@@ -516,7 +514,7 @@ class TransformerEncoder(nn.Module):
         blocks = [getattr(layer, "egodeep_attend", None) for layer in self.layers]
         if (egodeep is not None and egodeep.dim() == 2 and all(b is not None for b in blocks)
                 and not any(b.training and b.droprate > 0.0 for b in blocks) and Fn.imu_branch_fits(egodeep, blocks)):
-            queue = Fn.ResGradQueue(len(blocks)) if (Fn.RES_GRAD_QUEUE and torch.is_grad_enabled()) else None
+            queue = Fn.ResGradQueue(len(blocks)) if (SW.FOD_RES_GRAD_QUEUE and torch.is_grad_enabled()) else None
             pre = Fn.imu_branch(egodeep, blocks, queue=queue)
         for i, layer in enumerate(self.layers):
             if pre is not None:

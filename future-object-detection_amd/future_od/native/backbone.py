@@ -9,7 +9,6 @@ because stem and layer1 are frozen (reference future_od/models/paper.py:102-109)
 Module/parameter names follow torchvision's ResNet so checkpoints load unchanged
 (SURVEY.md 8b): body.conv1, body.bn1, body.layer{1..4}.{i}.{conv,bn}{1,2,3}, downsample.{0,1}.
 """
-import os
 
 import torch
 import torch.nn as nn
@@ -18,6 +17,7 @@ from torch.autograd import Function
 from . import arena
 from . import functional as Fn
 from . import ops
+from ..switches import SW
 
 RESNET_SPECS = {"resnet18": ("basic", (2, 2, 2, 2), 1),
                 "resnet34": ("basic", (3, 4, 6, 3), 1),
@@ -135,13 +135,6 @@ class ResNetBody(nn.Module):
         return c
 
 
-# the frozen stem and its max-pool as one launch (csrc/stem_pool.hip); "0": two launches
-FUSED_STEM_POOL = os.environ.get("FOD_FUSED_STEM_POOL", "1") != "0"
-
-# frames per pass of the frozen front (stem .. last frozen block); 0 (default) = all frames at once
-FRONT_FRAMES = int(os.environ.get("FOD_FRONT_FRAMES", "0")) or (1 << 30)
-
-
 def _conv_fwd(x, cw, bn, dtype, relu, residual=None, cin_pad=None, out=None):
     scale, shift = bn.scale_shift()
     w = Fn.prep_conv(cw.weight, dtype, scale, False, cin_pad=cin_pad)
@@ -150,19 +143,18 @@ def _conv_fwd(x, cw, bn, dtype, relu, residual=None, cin_pad=None, out=None):
                           out=out), geom
 
 
-# "2" (default): every frozen 64-channel bottleneck as one launch of the persistent weight-stationary kernel -- measured at
+# FOD_FUSED_BOTTLENECK "2" (default): every frozen 64-channel bottleneck as one launch of the persistent weight-stationary kernel -- measured at
 # 10 x 225 x 400: projection block 196 us against 517 us for its four separate launches, identity blocks 316 against 430
 # (profiles/r03v_fused_bottleneck_v4.txt).  "1": only the stage's first block (the policy of the earlier kernel, which
 # tied on the identity blocks); "0": none.
-FUSED_BOTTLENECK = os.environ.get("FOD_FUSED_BOTTLENECK", "2")
 
 
 def _fusable(blk, x, dtype, force=False):
     """fod_bottleneck_fused_fwd's domain: bf16, stride-1 bottleneck of width 64 with an identity (Cin 256) or 1x1
     projection (Cin 64) shortcut -- torchvision ResNet-50's layer1.  `force`: the domain only, not the policy."""
-    if (FUSED_BOTTLENECK == "0" and not force) or dtype != torch.bfloat16 or blk.kind == "basic":
+    if (SW.FOD_FUSED_BOTTLENECK == "0" and not force) or dtype != torch.bfloat16 or blk.kind == "basic":
         return False
-    if FUSED_BOTTLENECK == "1" and not force and blk.downsample is None:
+    if SW.FOD_FUSED_BOTTLENECK == "1" and not force and blk.downsample is None:
         return False
     main, ds = blk.convs()
     c1, c2, c3 = main[0][0], main[1][0], main[2][0]
@@ -274,12 +266,12 @@ class BackboneFn(Function):
                and not blocks[n_front][1].convs()[0][0][0].weight.requires_grad):
             n_front += 1
         b_sz, l_sz = video.shape[0], video.shape[1]
-        steps = max(1, min(l_sz, FRONT_FRAMES // max(b_sz, 1)))
+        steps = max(1, min(l_sz, (SW.FOD_FRONT_FRAMES or (1 << 30)) // max(b_sz, 1)))
         x = None
         for l0 in range(0, l_sz, steps):
             part = video[:, l0:l0 + steps]
             xp = ops.clip_to_stem_layout(part, dtype, *norm)
-            if FUSED_STEM_POOL and dtype == torch.bfloat16 and w_stem.shape[0] == 64:
+            if SW.FOD_FUSED_STEM_POOL and dtype == torch.bfloat16 and w_stem.shape[0] == 64:
                 # the stem is frozen (reference paper.py:102-109): conv + BN + ReLU + max-pool in one launch, the
                 # full-resolution map stays in LDS
                 h = ops.stem_pool_fwd(xp, w_stem, video.shape[-2], video.shape[-1], shift=shift1)

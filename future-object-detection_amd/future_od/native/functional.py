@@ -4,8 +4,6 @@ Parameters are fp32; kernels consume prepared copies of them (native/prepared.py
 in the compute dtype (torch.float32 = parity mode, torch.bfloat16 = performance mode); parameter gradients are fp32
 slices of the zero arena (native/arena.py), the short and the long ones filled by the queue of native/wgrad.py.
 """
-import os
-
 import torch
 from torch.autograd import Function
 
@@ -16,6 +14,7 @@ from .arena import ARENA, _ZeroArena, zeros_f32
 from .prepared import (CAT, PREP, STACK, _Job, _Prepared, _VEC, _pad_to, _wkey, prep_conv, prep_linear,
                        prep_stem)
 from .wgrad import WGRADS, _WgradQueue
+from ..switches import SW
 
 # Data-parallel runs: the object that averages finished arena regions across ranks (parallel.GradientReducer),
 # installed by FodDataParallel.forward for the coming backward pass; None otherwise.
@@ -174,13 +173,10 @@ class LinearKeepFn(Function):
         return dx, dw, db, None, None, None
 
 
-_LINEAR_KEEP = os.environ.get("FOD_LINEAR_KEEP", "1") != "0"       # "0": two autograd consumers (experiments)
-
-
 def linear_keep(x, weight, bias=None, relu=False, grad_masked=False, precomputed=None):
     """-> (x for the residual path, act(x W^T + b)); see LinearKeepFn.  Falls back to two consumers when the output
     width does not fit the vector epilogue (that path masks its own gradient: a second mask upstream is harmless)."""
-    if weight.shape[0] % _VEC[x.dtype] != 0 or not _LINEAR_KEEP:
+    if weight.shape[0] % _VEC[x.dtype] != 0 or not SW.FOD_LINEAR_KEEP:
         assert precomputed is None
         return x, linear(x, weight, bias, relu=relu)
     return LinearKeepFn.apply(x.contiguous(), weight, bias, relu, grad_masked, precomputed)
@@ -257,10 +253,6 @@ class TableGradAcc:
         return buf
 
 
-# "0": the decoder's query_scale MLP and the product with the sine embedding as separate launches (2 GEMMs + multiply)
-FUSED_MLP2 = os.environ.get("FOD_FUSED_MLP2", "1") != "0"
-
-
 class Mlp2MulFn(Function):
     """((relu(x W1^T + b1)) W2^T + b2) * table[m % rows(table)] as ONE launch forward and ONE backward
     (fod_mlp2_mul_fwd / _bwd, csrc/linear_norm.hip): reference transformer.py:384-386, once per decoder layer.  As separate
@@ -294,7 +286,7 @@ class Mlp2MulFn(Function):
 
 def mlp2_mul_fits(x, mlp, table):
     """Whether Mlp2MulFn applies: bf16, a two-layer 256 -> 256 -> 256 MLP with biases, a [rows, 256] table dividing x's rows."""
-    if not FUSED_MLP2 or x.dtype != torch.bfloat16 or getattr(mlp, "num_layers", 0) != 2:
+    if not SW.FOD_FUSED_MLP2 or x.dtype != torch.bfloat16 or getattr(mlp, "num_layers", 0) != 2:
         return False
     l0, l1 = mlp.layers
     D = x.shape[-1]
@@ -337,10 +329,6 @@ class ExpandRowsFn(Function):
 
 def expand_rows(x, reps):
     return ExpandRowsFn.apply(x.contiguous(), reps)
-
-
-# "0": every encoder layer sums the gradient of its per-frame IMU rows itself (fod_colsum_acc + a cast per layer)
-RES_GRAD_QUEUE = os.environ.get("FOD_RES_GRAD_QUEUE", "1") != "0"
 
 
 class ResGradQueue:
@@ -410,19 +398,11 @@ def layer_norm(x, gamma, beta, residual=None, res_row_div=0, res_queue=None, res
                              res_row_div, res_queue, res_slot)
 
 
-# "0": the output projection and the post-norm of the decoder's attention blocks as two launches (fod_gemm_nt +
-# fod_layernorm_fwd) instead of fod_linear_add_norm_fwd
-FUSED_LINEAR_NORM = os.environ.get("FOD_FUSED_LINEAR_NORM", "1") != "0"
-# the next cross-attention block's query-content projection from the same launch (fod_linear_add_norm_fwd then_*); "0": its own GEMM
-FUSED_LINEAR_THEN = os.environ.get("FOD_FUSED_LINEAR_THEN", "1") != "0"
-# ... and its backward: the input gradient of that projection (dq . then_w) is formed inside the fused backward launch
-# (fod_linear_add_norm_bwd pre_*) instead of by a GEMM of LinearKeepFn; "0": LinearKeepFn(precomputed=...) as before
-FUSED_LINEAR_PRE = os.environ.get("FOD_FUSED_LINEAR_PRE", "1") != "0"
-# rows up to which the fused launches are used.  The kernels walk 16-row tiles with the weights stationary, so they take any
+# FOD_FUSED_LINEAR_NORM_ROWS: rows up to which the fused projection + norm launches (fod_linear_add_norm_fwd / _bwd, with
+# their then_* and pre_* parts) are used.  The kernels walk 16-row tiles with the weights stationary, so they take any
 # row count, but at the encoder's 14 500 rows they do not pay (one wave per SIMD, every tile's loads queue behind the
 # previous tile's stores): forward 19.5 us against 21.3 for GEMM + norm, backward 26.3 against 20.9, whole step +0.1 ms
 # (profiles/r03l_fused_linear_norm.txt)
-FUSED_LINEAR_NORM_ROWS = int(os.environ.get("FOD_FUSED_LINEAR_NORM_ROWS", "1024"))
 
 
 class LinearAddNormFn(Function):
@@ -440,8 +420,8 @@ class LinearAddNormFn(Function):
         w = prep_linear(weight, a.dtype, False)
         assert w.shape[0] == N, "linear_add_norm: out_features must be a multiple of the vector width"
         rows = a.numel() // a.shape[-1]
-        if (FUSED_LINEAR_NORM and a.dtype == torch.bfloat16 and N == 256 and weight.shape[1] == 256 and w.shape[1] == 256
-                and rows <= FUSED_LINEAR_NORM_ROWS):
+        if (SW.FOD_FUSED_LINEAR_NORM and a.dtype == torch.bfloat16 and N == 256 and weight.shape[1] == 256 and w.shape[1] == 256
+                and rows <= SW.FOD_FUSED_LINEAR_NORM_ROWS):
             # the decoder's query side: projection + residual add + norm as ONE launch (csrc/linear_norm.hip)
             if then_weight is not None:
                 # ... and the next block's 256 -> 256 projection of y from the same launch: a CONSTANT second output
@@ -457,7 +437,7 @@ class LinearAddNormFn(Function):
             y, s, mean, rstd = ops.layernorm_fwd(x, gamma, beta, residual=o)
         ctx.then = None
         ctx.weight, ctx.bias, ctx.has_bias, ctx.a_relu = weight, bias, bias is not None, bool(a_relu)
-        if then_weight is not None and FUSED_LINEAR_PRE:
+        if then_weight is not None and SW.FOD_FUSED_LINEAR_PRE:
             # the second result is differentiable: its gradient comes back to THIS node (backward's pre form)
             ctx.then = (then_weight, then_bias)
             ctx.save_for_backward(a, s, mean, rstd, gamma, y)
@@ -489,7 +469,7 @@ class LinearAddNormFn(Function):
                                     False)
         if dy is not None:
             dy = dy.contiguous()
-        if (FUSED_LINEAR_NORM and s.dtype == torch.bfloat16 and N == 256 and K == 256 and rows <= FUSED_LINEAR_NORM_ROWS
+        if (SW.FOD_FUSED_LINEAR_NORM and s.dtype == torch.bfloat16 and N == 256 and K == 256 and rows <= SW.FOD_FUSED_LINEAR_NORM_ROWS
                 and ctx.needs_input_grad[0] and not ctx.a_relu):
             # the decoder's query side: layer-norm gradient and the projection's input gradient as ONE launch
             wt = prep_linear(weight, a.dtype, True)
@@ -516,12 +496,12 @@ def linear_add_norm(a, x, weight, bias, gamma, beta, a_relu=False):
 def linear_add_norm_then_fits(a, weight, then_weight):
     """Whether linear_add_norm_then may be used: the fused launch's domain (bf16, 256-wide projections, few rows)."""
     rows = a.numel() // a.shape[-1]
-    return (FUSED_LINEAR_NORM and FUSED_LINEAR_THEN and a.dtype == torch.bfloat16 and tuple(weight.shape) == (256, 256)
-            and tuple(then_weight.shape) == (256, 256) and rows <= FUSED_LINEAR_NORM_ROWS and _LINEAR_KEEP)
+    return (SW.FOD_FUSED_LINEAR_NORM and SW.FOD_FUSED_LINEAR_THEN and a.dtype == torch.bfloat16 and tuple(weight.shape) == (256, 256)
+            and tuple(then_weight.shape) == (256, 256) and rows <= SW.FOD_FUSED_LINEAR_NORM_ROWS and SW.FOD_LINEAR_KEEP)
 
 
 def linear_add_norm_then(a, x, weight, bias, gamma, beta, then_weight, then_bias):
-    """(y, y then_weight^T + then_bias) with y = LayerNorm(x + a W^T + b): ONE launch.  With FUSED_LINEAR_PRE the second
+    """(y, y then_weight^T + then_bias) with y = LayerNorm(x + a W^T + b): ONE launch.  With FOD_FUSED_LINEAR_PRE the second
     result is a differentiable output of this node (use it as it is: its gradient returns here and the backward launch
     forms dq . then_weight itself); without, it is a constant for autograd -- hand it to
     linear_keep(y, then_weight, then_bias, precomputed=...), whose backward needs nothing else."""
@@ -667,16 +647,14 @@ def dropout(x, p, training):
     return DropoutFn.apply(x.contiguous(), float(p), DROP_SEEDS.next())
 
 
-# fp8 attention (BASELINE.json configs[4], csrc/attention_fp8.hip).  "off": bf16 / f32 kernels everywhere (default);
+# FOD_ATTN_FP8: fp8 attention (BASELINE.json configs[4], csrc/attention_fp8.hip).  "off": bf16 / f32 kernels everywhere;
 # "long": the launches the block-shared LDS kernels take in bf16 (long query sequences: the encoder's self-attention,
 # the joint encoders) run the MX-fp8 forward; "all": every bf16 attention without active dropout does (the decoder's
 # few-query launches then lose their key split across blocks: slower, kept for tests and the record).
-# Set by runs/_model.build_model(args.attn_dtype) / bench.py --attn-dtype; FOD_ATTN_FP8 overrides.
-ATTN_FP8 = {"mode": os.environ.get("FOD_ATTN_FP8", "off")}
-
-
+# The environment gives the start value; an explicit runs/_model.build_model(attn_dtype=...) / bench.py --attn-dtype
+# overwrites it.
 def _fp8_takes(q1, k1, drop_p):
-    mode = ATTN_FP8["mode"]
+    mode = SW.FOD_ATTN_FP8
     if mode == "off" or q1.dtype != torch.bfloat16 or drop_p > 0.0:
         return False
     few_queries = q1.shape[1] <= 512 and k1.shape[1] >= 128       # launch_all()'s split predicate (attention.hip)
@@ -836,7 +814,7 @@ class InProjSelfFn(Function):
 def in_proj_self(src, pos, weight, bias):
     """-> (src for the residual step, q, k, v) with q = k-input = src + pos (see InProjSelfFn); None if `pos` carries a
     gradient or the fused form is switched off (the caller then takes the separate add + in_proj)."""
-    if pos.requires_grad or not _LINEAR_KEEP:
+    if pos.requires_grad or not SW.FOD_LINEAR_KEEP:
         return None
     row_mod = pos.shape[-2] if pos.dim() == 2 else 0
     return InProjSelfFn.apply(src.contiguous(), pos.contiguous(), weight, bias, row_mod)
@@ -1090,10 +1068,6 @@ def _gather_segments(gs, rows, D, dtype, device):
     return g
 
 
-# "0": the self-attention's position adds as their own element-wise launches (not in the grouped projection's epilogue)
-GROUP_RESIDUAL = os.environ.get("FOD_GROUP_RESIDUAL", "1") != "0"
-
-
 def group_linear(x, linears, residual=None, res_row_mod=0):
     """[m(x) for m in linears] for nn.Linear-like holders of equal shape; grouped launches in bf16, plain
     per-layer launches otherwise (fp32 parity mode, odd widths).  `residual`: a list of [R, D] tables added to the first
@@ -1106,7 +1080,7 @@ def group_linear(x, linears, residual=None, res_row_mod=0):
         out = [linear(x, m.weight, m.bias) for m in linears]
         fused = False
     else:
-        fused = bool(res) and GROUP_RESIDUAL and all(r.dim() == 2 and r.shape[1] == D and r.dtype == x.dtype for r in res) \
+        fused = bool(res) and SW.FOD_GROUP_RESIDUAL and all(r.dim() == 2 and r.shape[1] == D and r.dtype == x.dtype for r in res) \
             and _as_segments(res, res[0].shape[0], D) is not None and 0 < res_row_mod <= res[0].shape[0]
         out = list(GroupLinearFn.apply(x.contiguous(), len(res) if fused else 0, res_row_mod if fused else 0,
                                        *(res if fused else []), *[m.weight for m in linears], *[m.bias for m in linears]))
@@ -1115,10 +1089,6 @@ def group_linear(x, linears, residual=None, res_row_mod=0):
             out[i] = add(out[i], r, b_row_mod=res_row_mod)
     return out
 
-
-
-# "0": every encoder layer computes its IMU-token block itself (4 GEMMs + 2 norms on [frames, D] rows per layer)
-IMU_BATCHED = os.environ.get("FOD_IMU_BATCHED", "1") != "0"
 
 
 class ImuBranchFn(Function):
@@ -1217,7 +1187,7 @@ class ImuBranchFn(Function):
 def imu_branch_fits(ego, blocks):
     """Whether the one-key IMU blocks `blocks` (EgodeepAttention-like holders) can run as ImuBranchFn: bf16, >= 2 same-shaped
     blocks with biases, widths inside the short-launch kernel's vector epilogue."""
-    if not IMU_BATCHED or len(blocks) < 2 or ego.dim() != 2 or ego.dtype != torch.bfloat16:
+    if not SW.FOD_IMU_BATCHED or len(blocks) < 2 or ego.dim() != 2 or ego.dtype != torch.bfloat16:
         return False
     D = ego.shape[1]
     b0 = blocks[0]
@@ -1284,10 +1254,6 @@ class MemorySide:
         return kc, ks, v
 
 
-# "0": every cross-attention block launches its own dk / dv pass (fod_attn_bwd) instead of queueing it
-DKV_QUEUE = os.environ.get("FOD_DKV_QUEUE", "1") != "0"
-
-
 class _DkvQueue:
     """The dk / dv passes of the decoder's cross-attention blocks (one per layer and image: 30 per step) wait here during the
     backward sweep and run as ONE launch (fod_attn_bwd_dkv_multi; 32 jobs at most per launch) when the first consumer of
@@ -1346,7 +1312,7 @@ class HoistedCrossAttnFn(Function):
         if key not in side.dq2:
             side.dq2[key] = torch.empty((side.K,) + tuple(q2.shape), dtype=q2.dtype, device=q2.device)
         B_, Tq_, S_ = q1.shape[0], q1.shape[1], kc.shape[1]
-        if (DKV_QUEUE and q1.dtype == torch.bfloat16 and ctx.drop[0] == 0.0 and Tq_ <= 512 and S_ >= 256
+        if (SW.FOD_DKV_QUEUE and q1.dtype == torch.bfloat16 and ctx.drop[0] == 0.0 and Tq_ <= 512 and S_ >= 256
                 and dks.dim() == 3):
             # (the few-query shapes: what fod_attn_bwd would run as dq + attn_bwd_dkv_pf_kernel; the same kernel body runs
             # the queued jobs, so the results are bit-equal)

@@ -9,6 +9,7 @@ import os
 
 from . import abi
 from .abi import FodError
+from ..switches import SW
 
 LIB_PATH = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "lib", "libfod_hip.so"))
 
@@ -79,7 +80,7 @@ def last_error():
 
 
 # ---- kernel-selection knobs (csrc/knobs.h): the library reads the FOD_* variables it looks at ONCE, at its first use;
-# afterwards os.environ does not reach it -- these do.  A captured graph keeps the kernels of its capture.
+# afterwards the environment does not reach it -- these do.  A captured graph keeps the kernels of its capture.
 def knob(name):
     """The value in effect of a C-side knob, as text ("auto" where a rule decides)."""
     buf = C.create_string_buffer(32)
@@ -112,7 +113,7 @@ def _load_fast():
     host time per call than ctypes.  Optional: without them every call goes through ctypes (same library)."""
     import importlib.util
     path = os.path.join(os.path.dirname(LIB_PATH), "_fodfast.so")
-    if not os.path.isfile(path) or os.environ.get("FOD_FASTCALL", "1") == "0":
+    if not os.path.isfile(path) or not SW.FOD_FASTCALL:
         return {}
     spec = importlib.util.spec_from_file_location("_fodfast", path)
     mod = importlib.util.module_from_spec(spec)

@@ -3,13 +3,14 @@ an out-of-bounds access on the GPU), output allocation through torch (which owns
 memory), launch on torch's current HIP stream.  No arithmetic happens in this file."""
 import ctypes as C
 import math
-import os
 
 import torch
 
 from . import abi, capture
 from . import lib as L
 from .lib import F32, BF16, AttnShape, ConvGeom, Epilogue
+from .. import switches
+from ..switches import SW
 
 
 def call(name, *args, **kw):
@@ -89,7 +90,7 @@ def preallocate_graph_workspaces(device):
     allocation and zero-fill do not become nodes of the graph (a 64 MiB memset per replay otherwise)."""
     device = torch.device(device)
     kinds = (L.WS_NT_SPLIT, L.WS_NT_SPLIT_TICKETS, L.WS_TN_PARTIALS)
-    if _DETERMINISTIC:
+    if SW.FOD_DETERMINISTIC:
         kinds += (L.WS_DET, L.WS_TN_MULTI_DET)
     for kind in kinds:
         _workspace(kind, device, captured=True)
@@ -106,16 +107,12 @@ def preallocate_graph_workspaces(device):
 # summed in index order -- gradients, and with them parameters and Adam moments, are bit-identical from run to run
 # on one GPU (more than one rank: the all-reduce's summation order is RCCL's and not covered).  The library keeps no
 # state: the mode is this module's, and an argument (the entry point called) for the library.
-_DETERMINISTIC = os.environ.get("FOD_DETERMINISTIC", "0") == "1"
-
-
 def set_deterministic(flag):
-    global _DETERMINISTIC
-    _DETERMINISTIC = bool(flag)
+    switches.set("FOD_DETERMINISTIC", bool(flag))
 
 
 def is_deterministic():
-    return _DETERMINISTIC
+    return SW.FOD_DETERMINISTIC
 
 
 def det_workspace(device, kind=L.WS_DET):
@@ -131,7 +128,7 @@ _DET_TWINS = abi.det_twins(abi.PROTOTYPES)
 
 def call_twin(name, device, *args, **kw):
     """call(name, *args, stream) -- in deterministic mode its `_det` twin, handed the scratch of `device`."""
-    if not _DETERMINISTIC:
+    if not SW.FOD_DETERMINISTIC:
         return call(name, *args, stream(), **kw)
     scratch = det_workspace(device) if _DET_TWINS[name] else ()
     return call(name + "_det", *args, *scratch, stream(), **kw)
@@ -187,13 +184,13 @@ def gemm_nt_route(M, N, K, dtype=torch.bfloat16):
 
 
 def _tn_ws_bytes(M):
-    return L.LIB.fod_workspace_bytes(L.WS_TN_PARTIALS) if tn_may_use_partials_ws(M) or _DETERMINISTIC else 0
+    return L.LIB.fod_workspace_bytes(L.WS_TN_PARTIALS) if tn_may_use_partials_ws(M) or SW.FOD_DETERMINISTIC else 0
 
 
 def gemm_tn_route(M, N1, K2, dtype=torch.bfloat16, row_scale=False, colsum=False):
     """L.TnRoute of gemm_tn_acc(g [M, N1], x [M, K2], dw, row_scale, colsum) under the knobs and the mode in effect."""
     r = L.TnRoute()
-    call("fod_gemm_tn_route", _DT[dtype], M, N1, K2, N1, K2, K2, int(row_scale), int(colsum), int(_DETERMINISTIC),
+    call("fod_gemm_tn_route", _DT[dtype], M, N1, K2, N1, K2, K2, int(row_scale), int(colsum), int(SW.FOD_DETERMINISTIC),
          _tn_ws_bytes(M), C.addressof(r))
     return r
 
@@ -202,7 +199,7 @@ def conv2d_route(which, geom, dtype=torch.bfloat16):
     """Route of conv2d_fwd / conv2d_dgrad (L.CONV_FWD / L.CONV_DGRAD: an L.NtRoute; stride 2: of the first parity class)
     or conv2d_wgrad_acc (L.CONV_WGRAD: an L.TnRoute) for `geom`."""
     r = L.TnRoute() if which == L.CONV_WGRAD else L.NtRoute()
-    call("fod_conv2d_route", which, _DT[dtype], C.addressof(geom), None, int(_DETERMINISTIC),
+    call("fod_conv2d_route", which, _DT[dtype], C.addressof(geom), None, int(SW.FOD_DETERMINISTIC),
          _tn_ws_bytes(geom.Nimg * geom.Ho * geom.Wo), C.addressof(r))
     return r
 

@@ -6,7 +6,6 @@ by their shapes, whose only library call is the host-only fod_tn_plan_long.  The
 which gradients of a pass may wait, keeps their operands alive and launches the tables when the pass ends.
 """
 import ctypes as C
-import os
 from collections import namedtuple
 
 import numpy as np
@@ -15,6 +14,7 @@ import torch
 from . import capture
 from . import lib as L
 from . import ops
+from ..switches import SW
 
 
 # One fod_tn_job (include/fod.h) on the host: the fields of lib.TnJob, in its order.  dW [N1, K2] += G [M, N1]^T X [M, K2],
@@ -192,7 +192,7 @@ class _WgradQueue:
     SPARE_BYTES = 1 << 18
 
     def __init__(self):
-        self.enabled = os.environ.get("FOD_WGRAD_QUEUE", "1") != "0" and L.knob("FOD_TN_SMALL") != "0"
+        self.enabled = SW.FOD_WGRAD_QUEUE and L.knob("FOD_TN_SMALL") != "0"
         if not hasattr(torch._C, "_current_graph_task_id"):      # (private API: how the end of a backward pass is found)
             self.enabled = False
         # the LONG weight gradients (nn.Linear layers applied to more than 512 rows: the encoder, the memory side of
@@ -201,9 +201,9 @@ class _WgradQueue:
         # launched step is bound by the launching thread, not by the GPU, and the queue's bookkeeping (~30 us per site)
         # made it 5 ms slower (28.7 -> 34.0 ms).  `eager` = True (FOD_WGRAD_QUEUE_EAGER=1; tests, bench.py's profiling
         # leg) queues there too.
-        self.eager = os.environ.get("FOD_WGRAD_QUEUE_EAGER", "0") == "1"
-        self.long_enabled = os.environ.get("FOD_WGRAD_QUEUE_LONG", "1") != "0"
-        self.long_rows = int(os.environ.get("FOD_WGRAD_LONG_ROWS", "2048"))
+        self.eager = SW.FOD_WGRAD_QUEUE_EAGER
+        self.long_enabled = SW.FOD_WGRAD_QUEUE_LONG
+        self.long_rows = SW.FOD_WGRAD_LONG_ROWS
         self.long_jobs = []
         self.jobs = []
         self.members = {}            # index into jobs -> further jobs that add into that job's outputs

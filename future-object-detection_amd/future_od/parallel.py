@@ -39,6 +39,8 @@ import torch
 import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel
 
+from future_od.switches import SW
+
 
 class GradientReducer:
     def __init__(self, params, process_group=None, bucket_mb=48):
@@ -244,8 +246,7 @@ class FodDataParallel(DistributedDataParallel):
         keeps a backward pass from being captured into a hipGraph on another stream (future_od/graph.py).  What the
         constructor is needed for is done directly: rank 0's parameters and buffers are broadcast, shapes verified.
         FOD_DDP_TORCH_INIT=1 runs torch's constructor instead (then captured steps need the bare model)."""
-        import os
-        self.light = os.environ.get("FOD_DDP_TORCH_INIT", "0") != "1"
+        self.light = not SW.FOD_DDP_TORCH_INIT
         if self.light:
             torch.nn.Module.__init__(self)
             self.module = module

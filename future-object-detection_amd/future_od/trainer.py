@@ -9,6 +9,7 @@ import torch.distributed as distrib
 
 from future_od.graph import CaptureError
 from future_od.models.set_criterion import join_matchers
+from future_od.switches import SW
 from future_od.utils.distributed import EXIT, gather_distrib_od_map_stuffs, reduce_distrib_loss
 from future_od.utils.od_map import aggregate_mean_average_precision
 from future_od.utils.prefetch import DevicePrefetcher
@@ -123,13 +124,12 @@ class Trainer:
         if g is False:
             return None
         if g is None:
-            import os
             from future_od.models.set_criterion import device_matching_enabled
             dev = torch.device(self._device)
             # data parallel: with the FodDataParallel wrapper built without torch's reducer (its default) the step is two
             # graphs around an eagerly launched gradient all-reduce (graph.py); any other wrapper keeps the eager loop
             dp_ok = not self._distributed or getattr(self._model, "light", False)
-            ok = (os.environ.get("FOD_GRAPH_TRAIN", "1") != "0" and dp_ok and dev.type == "cuda"
+            ok = (SW.FOD_GRAPH_TRAIN and dp_ok and dev.type == "cuda"
                   and hasattr(self._optimizer, "enable_device_step")
                   and (self._optimizer_clips or not self._max_norm) and device_matching_enabled(dev))
             if not ok:
@@ -146,10 +146,9 @@ class Trainer:
         if g is False:
             return None
         if g is None:
-            import os
             from future_od.models.set_criterion import device_matching_enabled
             dev = torch.device(self._device)
-            ok = (os.environ.get("FOD_GRAPH_EVAL", "1") != "0" and not self._distributed and dev.type == "cuda"
+            ok = (SW.FOD_GRAPH_EVAL and not self._distributed and dev.type == "cuda"
                   and device_matching_enabled(dev) and not torch.is_grad_enabled())
             if not ok:
                 self._graphed_eval = False

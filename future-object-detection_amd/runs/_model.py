@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 import future_od.models.transformer as transformer
+from future_od import switches
 from future_od.models.paper import (JointEncoder, JointEncoderF2F, JointEncoderSequential, SingleFrameCore, CDetrBackbone, CDetrDetectorSpatioTemporal, FuturePredCore,
                                     PositionalEncoder, SeparateEncoder)
 from future_od.models.st_detr import SpatioTemporalDETR, SpatioTemporalDETRArgs
@@ -85,7 +86,7 @@ def build_model(args, detr_args: SpatioTemporalDETRArgs):
     if attn_dtype is not None:
         # BASELINE.json configs[4]: "fp8" = MX-fp8 QK^T / PV in the long-sequence attention launches (the encoder's
         # self-attention), "fp8-all" = in every attention launch; a process-wide switch of the kernel layer
-        Fn.ATTN_FP8["mode"] = {"bf16": "off", "fp8": "long", "fp8-all": "all"}[attn_dtype]
+        switches.set("FOD_ATTN_FP8", {"bf16": "off", "fp8": "long", "fp8-all": "all"}[attn_dtype])
     deterministic = getattr(args, "deterministic", None)
     if deterministic is not None:
         # fixed-order sums instead of f32 atomics in the backward pass; like attn_dtype a process-wide switch of the

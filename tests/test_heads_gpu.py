@@ -1,9 +1,12 @@
 """Positional tables, reference-point / box-head kernels, matcher cost, LAP, set losses and the AP
 bookkeeping kernel against the CPU oracle (oracle/) and the committed golden fixtures."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
 
+from future_od import switches
 from oracle import criterion as ocrit
 from oracle import stdetr as O
 from oracle import thirdparty as tp
@@ -14,6 +17,14 @@ if torch.cuda.is_available():
     from future_od.native import ops
 
 DEV = "cuda:0"
+
+
+@pytest.fixture
+def switch():
+    """switch(FOD_X=v, ...): sets Python-side switches (future_od/switches.py) for the rest of the test; the values they
+    had come back at teardown."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(switches.override(**values))
 
 
 def close(a, b, atol=1e-5, rtol=1e-5):
@@ -235,7 +246,7 @@ def _criterion_inputs(seed=0, B=3, M=32, Lv=3, C=8):
     return logits, boxes, targets
 
 
-def test_async_matcher_equals_host_synchronous_matcher(monkeypatch):
+def test_async_matcher_equals_host_synchronous_matcher(switch):
     """The stream-parking matcher (fod_stream_wait_flag + fod_match_after_event on a worker thread) must produce
     exactly the matches, losses and gradients of the path that blocks the host on the cost matrix."""
     from future_od.models.set_criterion import SetCriterion, build_matcher, _async_lap
@@ -244,7 +255,7 @@ def test_async_matcher_equals_host_synchronous_matcher(monkeypatch):
                         ["labels", "boxes", "cardinality"], "per level")
     res = {}
     for mode in ("0", "1", "2"):                              # host sync / adaptive / always through the worker
-        monkeypatch.setenv("FOD_ASYNC_MATCH", mode)
+        switch(FOD_ASYNC_MATCH=mode)
         tables = []
         for it in range(3):                                   # several tickets in flight one after the other
             logits, boxes, targets = _criterion_inputs(seed=it)
@@ -258,13 +269,13 @@ def test_async_matcher_equals_host_synchronous_matcher(monkeypatch):
             assert torch.equal(t0, t1) and torch.equal(gl0, gl1) and torch.equal(gb0, gb1), mode
 
 
-def test_async_matcher_failure_releases_the_stream_and_raises_late(monkeypatch):
+def test_async_matcher_failure_releases_the_stream_and_raises_late(switch):
     """A cost matrix the assignment solver rejects (non-finite) must not leave the stream parked: the worker writes
     'no match' and sets the flag; the error surfaces at the next join."""
     from future_od.models.set_criterion import SetCriterion, build_matcher, _async_lap
     from future_od.models.st_detr import SpatioTemporalDETRArgs
     from future_od.native.lib import FodError
-    monkeypatch.setenv("FOD_ASYNC_MATCH", "2")                 # through the worker thread
+    switch(FOD_ASYNC_MATCH="2")                              # through the worker thread
     crit = SetCriterion(8, build_matcher(SpatioTemporalDETRArgs(num_classes=8)), {}, 0.25,
                         ["labels", "boxes", "cardinality"], "per level")
     logits, boxes, targets = _criterion_inputs(seed=5)
@@ -322,13 +333,13 @@ def test_device_lap_flags_non_finite_costs():
     assert int(status.item()) != 0 and bool((got == -1).all())
 
 
-def test_device_target_path_equals_host_matcher(monkeypatch):
+def test_device_target_path_equals_host_matcher(switch):
     """Targets packed on the device (fod_pack_targets), matched by the device solver and normalised by a device-side
     `num_boxes` must give exactly the loss table and gradients of the host path (to_detr_targets + pack_targets +
     host solver + host num_boxes)."""
     from future_od.models.set_criterion import SetCriterion, build_matcher
     from future_od.models.st_detr import SpatioTemporalDETRArgs, to_detr_targets
-    monkeypatch.setenv("FOD_ASYNC_MATCH", "0")
+    switch(FOD_ASYNC_MATCH="0")
     crit = SetCriterion(8, build_matcher(SpatioTemporalDETRArgs(num_classes=8)), {}, 0.25,
                         ["labels", "boxes", "cardinality"], "per level")
     H, W, N = 96, 160, 32

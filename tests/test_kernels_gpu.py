@@ -19,6 +19,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from future_od import switches
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -319,13 +321,11 @@ def test_fused_linear_add_norm_then_next_projection(M):
     lin, lin2, ln = torch.nn.Linear(256, 256).to(DEV), torch.nn.Linear(256, 256).to(DEV), torch.nn.LayerNorm(256).to(DEV)
     gy, gq = rnd((M, 256), dtype, 65).to(DEV), rnd((M, 256), dtype, 66).to(DEV)
     grads = []
-    pre_was = Fn.FUSED_LINEAR_PRE
-    try:
-        for fused in ("pre", "then", None):
-            for prm in list(lin.parameters()) + list(lin2.parameters()) + list(ln.parameters()):
-                prm.grad = None
-            Fn.PREP.clear()
-            Fn.FUSED_LINEAR_PRE = fused == "pre"
+    for fused in ("pre", "then", None):
+        for prm in list(lin.parameters()) + list(lin2.parameters()) + list(ln.parameters()):
+            prm.grad = None
+        Fn.PREP.clear()
+        with switches.override(FOD_FUSED_LINEAR_PRE=fused == "pre"):
             aa, xx = a.clone().requires_grad_(True), x.clone().requires_grad_(True)
             if fused == "pre":
                 # the projection's result is a differentiable output of the fused node; its input gradient is formed
@@ -339,9 +339,7 @@ def test_fused_linear_add_norm_then_next_projection(M):
                 yy = Fn.linear_add_norm(aa, xx, lin.weight, lin.bias, ln.weight, ln.bias)
                 keep, qq = Fn.linear_keep(yy, lin2.weight, lin2.bias)
             ((keep.float() * gy.float()).sum() + (qq.float() * gq.float()).sum()).backward()
-            grads.append([aa.grad, xx.grad] + [prm.grad.clone() for prm in list(lin.parameters()) + list(lin2.parameters()) + list(ln.parameters())])
-    finally:
-        Fn.FUSED_LINEAR_PRE = pre_was
+        grads.append([aa.grad, xx.grad] + [prm.grad.clone() for prm in list(lin.parameters()) + list(lin2.parameters()) + list(ln.parameters())])
     for other in grads[:2]:
         for g1, g2 in zip(other, grads[2]):
             err = float((g1.double() - g2.double()).norm() / g2.double().norm().clamp_min(1e-9))
@@ -422,23 +420,20 @@ def test_fused_linear_add_norm_backward(M):
         assert err <= 2e-2, (name, err)
 
 
-def test_frozen_front_in_frame_chunks_equals_the_whole_clip(monkeypatch):
+def test_frozen_front_in_frame_chunks_equals_the_whole_clip():
     """FOD_FRONT_FRAMES (the frozen front -- fused stem + max-pool, fused layer1 blocks -- a few frames at a time, the last
     block writing into its slice of the full tensor): the same features as all frames at once, bit for bit, and the same
     with the fused launches switched off (bf16 tolerance: the separate launches round the projection shortcut once more)."""
-    from future_od.native import backbone as BB
     from future_od.models.paper import CDetrBackbone
     torch.manual_seed(8)
     bb = CDetrBackbone("resnet50", True, False, 64, pretrained=False).to(DEV)
     clip = torch.randn(2, 3, 3, 70, 100, device=DEV)
     with torch.no_grad():
         ref = bb.forward_clip(clip, torch.bfloat16)
-        monkeypatch.setattr(BB, "FRONT_FRAMES", 2)
-        chunked = bb.forward_clip(clip, torch.bfloat16)
-        monkeypatch.setattr(BB, "FRONT_FRAMES", 1 << 30)
-        monkeypatch.setattr(BB, "FUSED_BOTTLENECK", "0")
-        monkeypatch.setattr(BB, "FUSED_STEM_POOL", False)
-        plain = bb.forward_clip(clip, torch.bfloat16)
+        with switches.override(FOD_FRONT_FRAMES=2):
+            chunked = bb.forward_clip(clip, torch.bfloat16)
+        with switches.override(FOD_FRONT_FRAMES=0, FOD_FUSED_BOTTLENECK="0", FOD_FUSED_STEM_POOL=False):
+            plain = bb.forward_clip(clip, torch.bfloat16)
     assert torch.equal(ref, chunked)
     span = float(plain.float().abs().max())
     assert float((ref.float() - plain.float()).abs().max()) <= 3e-2 * span
@@ -725,14 +720,12 @@ def attention_fp8_forward_and_backward(shape, peaked):
 
 
 def test_attention_fp8_through_autograd_switch():
-    """The model-level switch (Fn.ATTN_FP8, runs/_model.py attn_dtype): 'long' sends only the long-query launches through
+    """The model-level switch (FOD_ATTN_FP8, runs/_model.py attn_dtype): 'long' sends only the long-query launches through
     the fp8 forward, 'all' every one; gradients flow to the original (unquantised) leaves."""
     from future_od.native import functional as Fn
     dtype = torch.bfloat16
-    was = Fn.ATTN_FP8["mode"]
-    try:
-        for mode, Tq, expect in (("long", 700, True), ("long", 128, False), ("all", 128, True), ("off", 700, False)):
-            Fn.ATTN_FP8["mode"] = mode
+    for mode, Tq, expect in (("long", 700, True), ("long", 128, False), ("all", 128, True), ("off", 700, False)):
+        with switches.override(FOD_ATTN_FP8=mode):
             q = rnd((1, Tq, 64), dtype, 1).to(DEV).requires_grad_(True)
             k = rnd((1, 300, 64), dtype, 2).to(DEV).requires_grad_(True)
             v = rnd((1, 300, 64), dtype, 3).to(DEV).requires_grad_(True)
@@ -743,8 +736,6 @@ def test_attention_fp8_through_autograd_switch():
             assert float((o.detach().float().cpu() - ref).abs().max()) <= 0.15 * float(ref.abs().max())
             for t in (q, k, v):
                 assert t.grad is not None and torch.isfinite(t.grad.float()).all() and float(t.grad.float().abs().max()) > 0
-    finally:
-        Fn.ATTN_FP8["mode"] = was
 
 
 def _drop_keep_mask(B, H, Tq, S, seed, p):

@@ -4,6 +4,7 @@ weights and (b) the golden fixtures captured from the reference's own files.
 fp32 mode (exact-f32 MFMA): pred_logits / pred_boxes / loss within 1e-3 relative of the fp32 CPU path
 (BASELINE.json north_star), Hungarian assignment indices bit-exact, gradients within 2e-3 of their norm.
 bf16 mode: same graph on bf16 MFMA; tolerance stated in the test (it is a precision trade, not parity)."""
+import contextlib
 import math
 
 import numpy as np
@@ -11,6 +12,7 @@ import pytest
 import torch
 import torch.nn as nn
 
+from future_od import switches
 from future_od.datasets.synthetic import make_batch
 from oracle import criterion as ocrit
 from oracle import stdetr as O
@@ -25,6 +27,14 @@ if torch.cuda.is_available():
                                         PositionalEncoder, SeparateEncoder)
     from future_od.models.st_detr import SpatioTemporalDETR, SpatioTemporalDETRArgs
     from future_od.native import functional as Fn
+
+
+@pytest.fixture
+def switch():
+    """switch(FOD_X=v, ...): sets Python-side switches (future_od/switches.py) for the rest of the test; the values they
+    had come back at teardown."""
+    with contextlib.ExitStack() as stack:
+        yield lambda **values: stack.enter_context(switches.override(**values))
 
 
 def build_joint(cfg: Config):
@@ -231,7 +241,7 @@ def test_train_mode_dropout():
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_imu_branch_dropout_is_per_token_in_train_mode(dtype, monkeypatch):
+def test_imu_branch_dropout_is_per_token_in_train_mode(dtype, switch):
     """with ONE IMU token per frame the reference drops per TOKEN -- the attention probability (a
     dropped weight removes that token's whole IMU contribution), the block's output, its MLP (transformer.py:108-119,444,
     485).  Train mode runs the general attention form for that: the IMU update differs between the tokens of a frame and
@@ -264,7 +274,7 @@ def test_imu_branch_dropout_is_per_token_in_train_mode(dtype, monkeypatch):
     assert 0.45 < float(zero.float().mean()) < 0.55, float(zero.float().mean())
     want = 2.0 * v.float().view(F_, 1, 8, 32).expand(F_, N, 8, 32)
     assert float((a - want)[~zero].abs().max()) <= 2e-2 * float(want.abs().max())
-    monkeypatch.setattr(T, "IMU_COLLAPSED_TRAIN", True)
+    switch(FOD_IMU_COLLAPSED_TRAIN=True)
     assert not att.per_token_masks()
 
 
@@ -404,7 +414,7 @@ def test_library_imported_before_torch_still_launches():
 
 
 @pytest.mark.parametrize("use_mlp", [True, False])
-def test_imu_blocks_of_all_layers_at_once(use_mlp, monkeypatch):
+def test_imu_blocks_of_all_layers_at_once(use_mlp, switch):
     """Fn.imu_branch (ImuBranchFn: the one-key IMU blocks of all layers in a handful of batched launches) against the
     layer-by-layer EgodeepAttention.forward_single_key: outputs bit-equal (the same kernels on the same rows) or within one
     bf16 ulp where the batched launch cannot split K, every parameter gradient and the input gradient within bf16
@@ -447,7 +457,7 @@ def test_imu_blocks_of_all_layers_at_once(use_mlp, monkeypatch):
     pos = torch.randn(96, D, device=DEV).to(torch.bfloat16)
     ys = []
     for batched in (True, False):
-        monkeypatch.setattr(Fn, "IMU_BATCHED", batched)
+        switch(FOD_IMU_BATCHED=batched)
         for prm in enc.parameters():
             prm.grad = None
         Fn.PREP.clear()
@@ -460,7 +470,7 @@ def test_imu_blocks_of_all_layers_at_once(use_mlp, monkeypatch):
         assert rel(ys[0][1][n], ys[1][1][n]) <= 3e-2, (n, rel(ys[0][1][n], ys[1][1][n]))
 
 
-def test_queued_cross_attention_key_value_gradients(monkeypatch):
+def test_queued_cross_attention_key_value_gradients(switch):
     """Fn._DkvQueue: the dk / dv passes of the decoder's cross-attention blocks wait during the backward sweep and run as one
     fod_attn_bwd_dkv_multi launch when layer 0 hands the memory-side gradient buffers on.  The queued jobs run the SAME
     kernel body as fod_attn_bwd's own dk / dv pass, so every gradient of the model agrees with the unqueued run to the
@@ -469,7 +479,7 @@ def test_queued_cross_attention_key_value_gradients(monkeypatch):
     data = make_batch(2, 4, 320, 400, seed=11, device=DEV, max_boxes=6)
     grads = []
     for queued in (True, False):
-        monkeypatch.setattr(Fn, "DKV_QUEUE", queued)
+        switch(FOD_DKV_QUEUE=queued)
         model, _ = build_product(cfg, torch.bfloat16, 3)
         model.eval()
         out, _, loss, stats, od = model(data=data, distributed=False)
