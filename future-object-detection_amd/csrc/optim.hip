@@ -3,7 +3,8 @@
 // future_od/trainer.py:186-188 and runs/_helper.py:84-107.  HBM-bound: reads p, g, m, v once, writes
 // p, m, v once.  Every tensor is processed as its dense storage order, so parameter, gradient and both
 // moments must share one memory layout (the host wrapper checks).
-// Behind them: the exponential moving average of the weights and its in-place swap (include/fod_ext.h), same geometry.
+// Behind them: the exponential moving average of the weights, its in-place swap and the gradient accumulation between
+// the replays of a captured backward (include/fod_ext.h), same geometry.
 #include "common.h"
 
 #include "../../include/fod_ext.h"
@@ -234,6 +235,67 @@ __global__ __launch_bounds__(256) void multi_swap_kernel(const long* __restrict_
   }
 }
 
+// Gradient accumulation between replays of a captured backward (include/fod_ext.h): the geometry of multi_ema_kernel
+// over (accumulator, gradient) pairs.  MODE 0 moves words (acc = g, 8 B / element), MODE 1 adds (acc = acc + g,
+// 12 B / element), MODE 2 finishes (g = (acc + g) * scale, 12 B / element).  Every element is written by exactly one
+// thread, no atomics: the result does not depend on timing, which is what deterministic mode needs of it.
+FOD_DEVINL float accum_add(float a, float g) {
+#pragma clang fp contract(off)
+  return a + g;
+}
+
+// the sum and the product each rounded on their own, as ema_step does it
+FOD_DEVINL float accum_finish(float a, float g, float scale) {
+#pragma clang fp contract(off)
+  const float sum = a + g;
+  return sum * scale;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void multi_accum_kernel(const long* __restrict__ pairs, const long* __restrict__ numel,
+                                                          const int* __restrict__ blk_tensor,
+                                                          const int* __restrict__ blk_chunk, float scale) {
+  const int t = blk_tensor[blockIdx.x];
+  const long base = (long)blk_chunk[blockIdx.x] * CHUNK;
+  const long end = min(numel[t], base + CHUNK);
+  float* a = reinterpret_cast<float*>(pairs[t * 2 + 0]);
+  float* g = reinterpret_cast<float*>(pairs[t * 2 + 1]);
+  long tail = base;
+  if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(g)) & 15) == 0) {      // 16 bytes per lane and stream
+    const long end4 = base + ((end - base) & ~3L);
+    for (long i = base + 4 * threadIdx.x; i < end4; i += 1024) {
+      if (MODE == 0) {
+        *reinterpret_cast<uint4*>(a + i) = *reinterpret_cast<const uint4*>(g + i);
+      } else {
+        float4 aq = *reinterpret_cast<const float4*>(a + i);
+        const float4 gq = *reinterpret_cast<const float4*>(g + i);
+        if (MODE == 1) {
+          aq.x = accum_add(aq.x, gq.x);
+          aq.y = accum_add(aq.y, gq.y);
+          aq.z = accum_add(aq.z, gq.z);
+          aq.w = accum_add(aq.w, gq.w);
+          *reinterpret_cast<float4*>(a + i) = aq;
+        } else {
+          aq.x = accum_finish(aq.x, gq.x, scale);
+          aq.y = accum_finish(aq.y, gq.y, scale);
+          aq.z = accum_finish(aq.z, gq.z, scale);
+          aq.w = accum_finish(aq.w, gq.w, scale);
+          *reinterpret_cast<float4*>(g + i) = aq;
+        }
+      }
+    }
+    tail = end4;
+  }
+  for (long i = tail + threadIdx.x; i < end; i += 256) {
+    if (MODE == 0)
+      reinterpret_cast<unsigned*>(a)[i] = reinterpret_cast<const unsigned*>(g)[i];
+    else if (MODE == 1)
+      a[i] = accum_add(a[i], g[i]);
+    else
+      g[i] = accum_finish(a[i], g[i], scale);
+  }
+}
+
 }  // namespace
 
 extern "C" int fod_multi_sqnorm_acc(const long* ptrs, const long* numel, const int* blk_tensor, const int* blk_chunk,
@@ -280,6 +342,24 @@ extern "C" int fod_multi_swap(const long* pairs, const long* numel, const int* b
                               int nblocks, hipStream_t stream) {
   FOD_REQUIRE(pairs && numel && blk_tensor && blk_chunk && nblocks > 0, "multi_swap: bad args");
   hipLaunchKernelGGL(multi_swap_kernel, dim3(nblocks), dim3(256), 0, stream, pairs, numel, blk_tensor, blk_chunk);
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}
+
+extern "C" int fod_multi_accum(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk,
+                               int nblocks, int mode, float scale, hipStream_t stream) {
+  FOD_REQUIRE(pairs && numel && blk_tensor && blk_chunk && nblocks > 0, "multi_accum: bad args");
+  FOD_REQUIRE(mode >= 0 && mode <= 2, "multi_accum: mode %d is not 0 (store), 1 (add) or 2 (finish)", mode);
+  FOD_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "multi_accum: scale %g is not finite and > 0", (double)scale);
+  if (mode == 0)
+    hipLaunchKernelGGL(multi_accum_kernel<0>, dim3(nblocks), dim3(256), 0, stream, pairs, numel, blk_tensor, blk_chunk,
+                       scale);
+  else if (mode == 1)
+    hipLaunchKernelGGL(multi_accum_kernel<1>, dim3(nblocks), dim3(256), 0, stream, pairs, numel, blk_tensor, blk_chunk,
+                       scale);
+  else
+    hipLaunchKernelGGL(multi_accum_kernel<2>, dim3(nblocks), dim3(256), 0, stream, pairs, numel, blk_tensor, blk_chunk,
+                       scale);
   FOD_LAUNCH_CHECK();
   return FOD_OK;
 }

@@ -27,7 +27,18 @@ Dropout (train mode, p > 0): the masks are stateless hashes of (seed, index); a 
 seed as a constant, so the kernels additionally mix in a device scalar (`ops.DROP_BASE`) that the graph advances once
 per replay -- new masks every step, the same masks in the forward and the backward of one step.
 
-Restrictions (checked): one device per process, static shapes -- a batch with other shapes is re-captured.
+Gradient accumulation (`GraphedStep(..., accumulate=N)`, N > 1): the same two graphs, with or without data parallel.
+Each call takes ONE micro-batch: it replays graph A and then launches one multi-tensor kernel (optim.GradAccumulator,
+fod_multi_accum) over the flat gradient tensors graph A rewrites at static addresses -- store after the first
+micro-batch of a cycle, add after those in between, finish after the N-th, which leaves
+(((g1 + g2) + g3) + ... + gN) * float32(1 / N) where graph B reads its gradients.  Only the N-th call all-reduces (data
+parallel) and replays graph B: one clip + AdamW + EMA per cycle.  Nothing is accumulated inside a graph and no kernel
+of the step changes; with accumulate=1 (the default) the step is captured exactly as before.  Every micro-batch's loss
+is normalised by its OWN number of boxes (at least 1), so the update is the mean of the micro-batches' gradients -- the
+gradient of one batch N times as large only where the micro-batches carry equal numbers of boxes.
+
+Restrictions (checked): one device per process, static shapes -- a batch with other shapes is re-captured; all
+micro-batches of one accumulation cycle have one batch signature.
 """
 import torch
 import torch.distributed as dist
@@ -85,11 +96,19 @@ class GraphedStep:
     rolled back) and captures one more; later calls copy the batch into the captured input buffers and replay.
     Returned tensors are the graph's static outputs: valid until the next call."""
 
-    def __init__(self, model, optimizer, warmup=2, process_group=None, data_parallel=False, rollback_warmup=False):
+    def __init__(self, model, optimizer, warmup=2, process_group=None, data_parallel=False, rollback_warmup=False,
+                 accumulate=1):
         """`data_parallel=True` (or a `process_group`): `model` is the BARE model of this rank -- not a
         DistributedDataParallel wrapper: torch's wrapper stashes every parameter's AccumulateGrad node at construction,
         on the default stream, and a backward pass captured on another stream must not touch the default stream.  The
-        ranks' parameters must be equal on entry (`broadcast_parameters`)."""
+        ranks' parameters must be equal on entry (`broadcast_parameters`).
+        `accumulate=N` (an integer >= 1): one optimizer update per N calls, see the module's comment; the object then
+        carries the state of the open cycle (`pending`, `reset_cycle()`)."""
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError(f"GraphedStep: accumulate must be an integer >= 1, not {accumulate!r}")
+        self.accumulate = accumulate
+        self.pending = 0                  # micro-batches of the open cycle (0 .. accumulate - 1)
+        self._cycle_sig = None            # their batch signature
         self.model, self.opt, self.warmup = model, optimizer, max(int(warmup), 2)
         self.core = model
         self.group = process_group
@@ -120,6 +139,10 @@ class GraphedStep:
         # default (round 3): ON for a real multi-rank RCCL group, off for one rank and for gloo -- see the comment above
         # and profiles/r03e_ddp_overlap_probe_1rank.txt
         self.overlap = env if env is not None else (self.ddp and self.world > 1 and self._native_avg())
+        if self.accumulate > 1:
+            # the gradients are final only after the last micro-batch's accumulation launch, which runs behind the WHOLE
+            # of graph A: there is nothing to send while the backbone's backward runs, so graph A is not split
+            self.overlap = False
         self.overlap_mode = SW.FOD_GRAPH_OVERLAP_MODE     # "after": experiment, see __call__
         self.grad_bf16 = SW.FOD_GRAD_BF16
         self._bf16_bufs = {}
@@ -343,7 +366,7 @@ class GraphedStep:
         torch.cuda.synchronize(dev)
         wgrad.WGRADS.prepare(dev)                    # pinned job tables for the captures below (none can be made inside)
         ops.preallocate_graph_workspaces(dev)     # scratch of the captured launches: allocated and zeroed out here
-        if not self.ddp:
+        if not self.ddp and self.accumulate == 1:
             graph = torch.cuda.CUDAGraph()
             with capture.Record() as record, torch.cuda.graph(graph):
                 outs = self._forward_backward(static)
@@ -353,9 +376,11 @@ class GraphedStep:
             # warm-up steps; python's step counter ran one ahead during capture
             self.opt._step_no -= 1
             return {"graph": graph, "static": static, "outs": outs, "record": record}
-        # data parallel: the collectives stay outside the two graphs
-        self._global_num_boxes(static, static["_num_boxes"])
-        torch.cuda.synchronize(dev)
+        # data parallel: the collectives stay outside the two graphs.  Accumulation: the accumulation launch does; without
+        # data parallel no `_num_boxes` is fed, the criterion counts on the device as in the single-graph step
+        if self.ddp:
+            self._global_num_boxes(static, static["_num_boxes"])
+            torch.cuda.synchronize(dev)
         # The backward pass in two pieces (native/functional.py: BackboneCut): A1 = forward + everything down to the
         # backbone's output (all transformer gradients), A2 = the backbone's backward.  The transformer gradients are
         # all-reduced while A2 runs -- the overlap the eager reducer has (parallel.py), without a collective in a graph.
@@ -385,13 +410,25 @@ class GraphedStep:
         both = first + second
         self.comm_stats = {"tensors": len(both), "bytes": sum(t.numel() * t.element_size() for t in both),
                            "overlapped_bytes": sum(t.numel() * t.element_size() for t in first) if graph_a2 else 0}
+        accum = None
+        if self.accumulate > 1:
+            # one accumulator per captured signature over what graph A leaves for graph B (allocated here, outside the
+            # captures); the graph's record keeps it with everything else the step's launches read and write
+            from future_od.optim import GradAccumulator
+            accum = GradAccumulator(first)
+            record.held[id(accum)] = ("grad accumulator", accum)
         return {"graph": graph_a, "graph_bb": graph_a2, "graph_opt": graph_b, "targets": first, "targets_bb": second,
-                "static": static, "outs": outs, "record": record}
+                "static": static, "outs": outs, "record": record, "accum": accum}
 
     # ------------------------------------------------------------------------------------------
+    def reset_cycle(self):
+        """Drop the open accumulation cycle without an update: the next call is micro-batch 1 of a new one."""
+        self.pending, self._cycle_sig = 0, None
+
     def __call__(self, data, sync=True):
-        """One optimizer step on `data`.  `sync=False` (data parallel only) skips the gradient average -- the ranks'
-        parameters then DIVERGE; it exists to time the step without communication."""
+        """One optimizer step on `data` -- with accumulate=N, one micro-batch: forward, backward and the accumulation
+        launch, and on every N-th call the one optimizer step of the cycle.  `sync=False` (data parallel only) skips the
+        gradient average -- the ranks' parameters then DIVERGE; it exists to time the step without communication."""
         ema = getattr(self.opt, "_ema", None)
         if ema is not None and ema.is_applied:
             raise RuntimeError("GraphedStep inside WeightEMA.applied(): the model holds the averaged weights")
@@ -401,16 +438,23 @@ class GraphedStep:
             # may be in flight when the old graphs, and with them what their records hold, are dropped
             torch.cuda.synchronize()
             self._graphs = {}
+            self.reset_cycle()                            # (its accumulator went with the graphs)
         self._opt_token = token
         sig = self._signature(data)
+        if self.pending and sig != self._cycle_sig:
+            raise RuntimeError(f"GraphedStep: a batch of another signature after {self.pending} of {self.accumulate} "
+                               "micro-batches: one accumulation cycle has one batch signature (reset_cycle() drops "
+                               "the open one)")
+        final = self.pending + 1 == self.accumulate       # this call ends the cycle (always, without accumulation)
         g = self._graphs.get(sig)
         if g is None:
             g = self._graphs[sig] = self._capture_agreed(data)
         _check_matcher(g)                                 # a failure of the previous replay's device solver: raised here
         _stage_inputs(g, data)
-        self.opt.sync_hyperparams()                       # the current plan (eager steps) ...
-        if g.get("plan") is not None:
-            self.opt.sync_hyperparams(g["plan"])          # ... and the one baked into this graph, if it is another
+        if final:                                         # (a learning rate changed mid-cycle: at the cycle's update)
+            self.opt.sync_hyperparams()                   # the current plan (eager steps) ...
+            if g.get("plan") is not None:
+                self.opt.sync_hyperparams(g["plan"])      # ... and the one baked into this graph, if it is another
         import time
         dbg = SW.FOD_GRAPH_TIMING
         def tick(label, _t=[time.perf_counter()]):
@@ -425,6 +469,22 @@ class GraphedStep:
         tick("num_boxes")
         g["graph"].replay()
         tick("graph A")
+        if g.get("accum") is not None:
+            # one launch over the flat gradient tensors, behind graph A on this stream; the N-th leaves the cycle's mean
+            # gradient where graph B (and, data parallel, the all-reduce below) reads it
+            if self.pending == 0:
+                g["accum"].store()
+            elif not final:
+                g["accum"].add()
+            else:
+                g["accum"].finish(self.accumulate)
+            tick("accumulate")
+            if not final:
+                # no collective on the gradients, no graph B: parameters, moments, step count, EMA and the kernels'
+                # prepared weight copies are as they were
+                self.pending, self._cycle_sig = self.pending + 1, sig
+                self.replays += 1
+                return g["outs"]
         if self.ddp:
             pending = []
             if sync:
@@ -449,7 +509,9 @@ class GraphedStep:
                         w.wait()                     # stream-ordered for RCCL: the launching stream waits, not the host
                         if not self._native_avg() and not isinstance(w, _Bf16Pending):
                             t.div_(self.world)       # (gloo sums; a bf16 hand-off scales in its own wait)
+        if g.get("graph_opt") is not None:
             g["graph_opt"].replay()
+        self.reset_cycle()
         self.opt._step_no += 1
         self.replays += 1
         prepared.PREP.mark_stale()          # the replay changed the parameters without bumping their python-side versions

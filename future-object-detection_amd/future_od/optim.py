@@ -461,3 +461,105 @@ class WeightEMA:
             assert n in sd, n
             sd[n] = e.detach().clone()
         return sd
+
+
+class GradAccumulator:
+    """acc = GradAccumulator(tensors);  acc.store() / acc.add() / acc.finish(n)
+
+    Gradient accumulation over a fixed set of dense f32 device tensors -- the gradients a backward pass rewrites in
+    place -- as ONE `fod_multi_accum` launch per micro-batch on the current stream: `store()` after the first backward
+    of a cycle (accumulator = g), `add()` after the ones in between (accumulator += g) and `finish(n)` after the last,
+    which leaves  (((g1 + g2) + g3) + ... + gn) * float32(1 / n)  in the gradient tensors themselves, where the
+    optimizer reads it.  The order of the sum is fixed and no element is written by more than one thread, so the
+    result is the same bits run after run (deterministic mode keeps its claim).
+
+    One f32 accumulator holds all tensors back to back, each starting on a 16-byte boundary (so a pair takes the
+    16-byte path whenever its gradient is aligned); `nbytes` is its size.  The tables are built the way WeightEMA
+    builds its own.  `rebind(tensors)` points the pair table at gradients that have moved (the eager loop: autograd
+    allocates some sums itself, at new addresses every step); their sizes must not change."""
+
+    STORE, ADD, FINISH = 0, 1, 2                     # the modes of fod_multi_accum (include/fod_ext.h)
+
+    def __init__(self, tensors):
+        tensors = list(tensors)
+        if not tensors:
+            raise L.FodError("GradAccumulator: no tensors")
+        dev = tensors[0].device
+        self._check(tensors, dev)
+        self._sizes = [t.numel() for t in tensors]
+        self._offsets, at = [], 0
+        for n in self._sizes:
+            self._offsets.append(at)
+            at += (n + 3) // 4 * 4
+        self.numel = sum(self._sizes)
+        self._acc = torch.zeros(at, dtype=torch.float32, device=dev)
+        self.nbytes = 4 * at
+        chunk = L.LIB.fod_multi_chunk()
+        bt, bc = [], []
+        for t, n in enumerate(self._sizes):
+            for c in range((n + chunk - 1) // chunk):
+                bt.append(t)
+                bc.append(c)
+        self._nblocks = len(bt)
+        host = (self._pair_table(tensors), torch.tensor(self._sizes, dtype=torch.int64),
+                torch.tensor(bt, dtype=torch.int32), torch.tensor(bc, dtype=torch.int32))
+        up = [FusedAdamW._upload(x, dev) for x in host]
+        self._tab = tuple(u[0] for u in up)
+        self._keep = [u[1] for u in up]              # the uploads read the pinned copies when they run
+        self._ptrs = [t.data_ptr() for t in tensors]
+        self._tensors = tensors                      # the launches write them through raw pointers: kept alive here
+
+    @staticmethod
+    def _check(tensors, dev):
+        for i, t in enumerate(tensors):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != dev:
+                raise L.FodError(f"GradAccumulator handles float32 tensors on one device only (tensor {i}: "
+                                 f"{getattr(t, 'dtype', type(t))}, {getattr(t, 'device', None)})")
+            if t.numel() == 0 or not _dense(t):
+                raise L.FodError(f"GradAccumulator: tensor {i} is empty or not dense (shape {tuple(t.shape)}, "
+                                 f"strides {t.stride()})")
+
+    def _pair_table(self, tensors):
+        base = self._acc.data_ptr()
+        return torch.tensor([[base + 4 * off, t.data_ptr()] for off, t in zip(self._offsets, tensors)], dtype=torch.int64)
+
+    def accumulated(self):
+        """The accumulator's slice of every tensor, in the constructor's order (flat views of the live memory)."""
+        return [self._acc[off:off + n] for off, n in zip(self._offsets, self._sizes)]
+
+    def moved(self, tensors):
+        """True if `tensors` are not at the addresses the pair table holds (then: rebind)."""
+        return [t.data_ptr() for t in tensors] != self._ptrs
+
+    def rebind(self, tensors):
+        """The same tensors, in the same order and of the same sizes, at other addresses: a new pair table (a pinned
+        upload on the current stream, behind the launches that read the old one); what is accumulated stays."""
+        tensors = list(tensors)
+        self._check(tensors, self._acc.device)
+        if [t.numel() for t in tensors] != self._sizes:
+            raise L.FodError("GradAccumulator.rebind: the tensors' sizes changed; build a new accumulator")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("GradAccumulator.rebind() inside a capture: the upload would allocate pinned memory")
+        pinned = self._pair_table(tensors).pin_memory()
+        self._tab[0].copy_(pinned, non_blocking=True)    # in place: a record that holds the tables holds the live one
+        self._keep = self._keep[:4] + [pinned]           # the upload reads the pinned copy when it runs
+        self._ptrs = [t.data_ptr() for t in tensors]
+        self._tensors = tensors
+
+    @torch.no_grad()
+    def _launch(self, mode, scale):
+        pairs, numel, bt, bc = self._tab
+        L.call("fod_multi_accum", ptr(pairs), ptr(numel), ptr(bt), ptr(bc), self._nblocks, mode, scale, stream())
+        # a capture that recorded the launch keeps what it reads and writes
+        capture.hold_or_ask("grad accumulator", (self._tab, self._acc, self._tensors))
+
+    def store(self):
+        self._launch(self.STORE, 1.0)
+
+    def add(self):
+        self._launch(self.ADD, 1.0)
+
+    def finish(self, n):
+        if int(n) != n or n < 2:
+            raise ValueError(f"GradAccumulator.finish: a cycle has at least 2 micro-batches, not {n}")
+        self._launch(self.FINISH, float(torch.tensor(1.0 / int(n), dtype=torch.float32)))

@@ -63,6 +63,55 @@ class Trainer:
         self._ema = ema
         if ema is not None:
             optimizer.attach_ema(ema)
+        # gradient accumulation (set_accumulate): one optimizer update per this many loader items.  1: nothing changes
+        self._accumulate = 1
+        self._eager_accum, self._eager_pending = None, 0
+
+    def set_accumulate(self, n):
+        """One optimizer update per `n` loader items (micro-batches), each normalised by its own number of boxes: the
+        update is the mean of their gradients (future_od/graph.py: GraphedStep(accumulate=n); the eager loop accumulates
+        with the same kernel).  The loop, its statistics and `_training_iterations` stay per loader item; a cycle left
+        open at the end of a training epoch is dropped, with a printed line.  To be set before the first training step.
+        (A method, not a constructor keyword: the constructor is the reference's plus `ema`.)"""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"Trainer.set_accumulate: an integer >= 1, not {n!r}")
+        if getattr(self, "_graphed", None) not in (None, False) or self._eager_pending:
+            raise RuntimeError("Trainer.set_accumulate: the training step is already built")
+        self._accumulate = n
+        return self
+
+    def _accumulate_eager(self):
+        """The eager loop's accumulation, after a micro-batch's backward pass: one launch of the kernel the captured step
+        uses (optim.GradAccumulator) over the parameters' gradients, re-pointed when autograd moved some.  True when the
+        cycle is complete: the gradients then hold its mean and the optimizer steps.  Gradients the accumulator cannot
+        take (not f32 on the device, another set than at the cycle's start) raise: the loop never trains at another
+        effective batch size than it was asked for."""
+        from future_od.optim import GradAccumulator
+        grads = [p.grad for p in self._model.parameters() if p.requires_grad and p.grad is not None]
+        acc = self._eager_accum
+        if acc is None:
+            acc = self._eager_accum = GradAccumulator(grads)
+        elif acc.moved(grads):
+            acc.rebind(grads)
+        k, n = self._eager_pending, self._accumulate
+        if k == 0:
+            acc.store()
+        elif k + 1 < n:
+            acc.add()
+        else:
+            acc.finish(n)
+        self._eager_pending = (k + 1) % n
+        return self._eager_pending == 0
+
+    def _drop_open_cycle(self, graphed):
+        """End of a training epoch (or a batch of another shape mid-cycle): micro-batches that did not reach an update."""
+        dropped = (graphed.pending if graphed is not None else 0) + self._eager_pending
+        if dropped:
+            print(f"[fod] gradient accumulation: dropped {dropped} micro-batch(es) of an open cycle "
+                  f"(accumulate={self._accumulate}): no update from them")
+        if graphed is not None:
+            graphed.reset_cycle()
+        self._eager_pending = 0
 
     # ------------------------------------------------------------------ public API
     def train(self, max_epochs):
@@ -136,7 +185,8 @@ class Trainer:
                 self._graphed = False
                 return None
             from future_od.graph import GraphedStep
-            g = self._graphed = GraphedStep(self._model, self._optimizer, warmup=2, rollback_warmup=True)
+            g = self._graphed = GraphedStep(self._model, self._optimizer, warmup=2, rollback_warmup=True,
+                                            accumulate=self._accumulate)
         return g
 
     def _graphed_forward(self):
@@ -198,6 +248,8 @@ class Trainer:
             if EXIT.is_set():
                 return
             if graphed is not None:
+                if graphed.pending and graphed._signature(data) != graphed._cycle_sig:
+                    self._drop_open_cycle(graphed)            # (a short last batch: a cycle has one batch signature)
                 try:
                     out, loss, stats, od = graphed(data)      # zero_grad + forward + backward + clip + AdamW: one launch
                 except CaptureError as e:                     # not capturable here (parameters rolled back, all ranks
@@ -231,9 +283,10 @@ class Trainer:
                     for name, p in self._model.named_parameters():
                         if p.requires_grad and p.grad is None:
                             print(name, "got no gradient")
-                if self._max_norm > 0 and not self._optimizer_clips:
-                    torch.nn.utils.clip_grad_norm_(self._model.parameters(), self._max_norm)
-                self._optimizer.step()
+                if self._accumulate == 1 or self._accumulate_eager():         # (the N-th micro-batch of a cycle)
+                    if self._max_norm > 0 and not self._optimizer_clips:
+                        torch.nn.utils.clip_grad_norm_(self._model.parameters(), self._max_norm)
+                    self._optimizer.step()
                 self._training_iterations += 1
             if self._distributed:
                 stats = reduce_distrib_loss(stats, average=True)
@@ -257,6 +310,8 @@ class Trainer:
                 print(f"[{mode}: {self._epoch}, {i + 1:4d}/{len(data_loader)}] Loss: {msg}.")
         if pending is not None:
             consume(pending)
+        if mode == "train" and self._accumulate > 1:
+            self._drop_open_cycle(graphed)
         join_matchers()                    # a matcher failure of the last iteration is raised here, not lost
         msg = "  ".join(f"{self._stats[f'{mode} {k} loss'].avg:.5f} ({k})" for k in stat_keys)
         print(f"[{mode}: {self._epoch}] Loss: {msg}")

@@ -65,7 +65,7 @@ def get_trainer(args, config, detr_args, lr_sched, model, optimizer, train_loade
         from future_od.optim import WeightEMA
         bare = model.module if isinstance(model, torch.nn.parallel.DistributedDataParallel) else model
         ema = WeightEMA(bare, decay=args.ema_decay)
-    return Trainer(
+    trainer = Trainer(
         model=model, optimizer=optimizer, lr_sched=lr_sched, train_loader=train_loader, val_loaders=val_loaders,
         checkpoint_path=config["checkpoint_path"],
         visualization_path=os.path.join(config["visualization_path"], args.experiment_idf),
@@ -74,3 +74,4 @@ def get_trainer(args, config, detr_args, lr_sched, model, optimizer, train_loade
         visualization_iterations=[0], category_dict=CATEGORY_DICT, distributed=args.distributed,
         is_master=(args.world_rank == 0),
         wandb_config=WandBConfig(enabled=False), max_norm=detr_args.max_norm, ema=ema)
+    return trainer.set_accumulate(int(getattr(args, "accumulate", 1) or 1))

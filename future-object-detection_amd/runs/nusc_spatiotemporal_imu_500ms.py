@@ -43,8 +43,7 @@ def train(model, args, detr_args, config):
     return trainer
 
 
-def main(argv=None):
-    print(f"{os.path.basename(__file__)}: pytorch {torch.__version__}, hip {torch.version.hip}")
+def build_parser():
     parser = build_base_parser()
     parser.add_argument("--epochs", default=160, type=int, help="Number of training epochs")
     parser.add_argument("--steps_per_epoch", default=8, type=int, help="synthetic batches per epoch")
@@ -55,7 +54,15 @@ def main(argv=None):
     parser.add_argument("--ema-decay", dest="ema_decay", default=None, type=float,
                         help="keep an exponential moving average of the weights with this decay (e.g. 0.9998): "
                              "evaluation runs under it, checkpoints carry it; default: none")
-    args = parser.parse_args(argv)
+    parser.add_argument("--accumulate", default=1, type=int,
+                        help="gradient accumulation: one optimizer update per this many batches (each normalised by "
+                             "its own number of boxes); default: 1, none")
+    return parser
+
+
+def main(argv=None):
+    print(f"{os.path.basename(__file__)}: pytorch {torch.__version__}, hip {torch.version.hip}")
+    args = build_parser().parse_args(argv)
     if args.stage_sizes:
         args.stages = tuple((tuple(int(v) for v in sz.split("x")), int(b))
                             for sz, b in (item.split(":") for item in args.stage_sizes.split(",")))

@@ -36,6 +36,22 @@ int fod_multi_ema(const long* pairs, const long* numel, const int* blk_tensor, c
  * identity.  Same tables as fod_multi_ema.  The tensors of a pair must not overlap. */
 int fod_multi_swap(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk, int nblocks,
                    fod_stream_t stream);
+/* Gradient accumulation over many tensors in ONE launch: what a trainer does between the backward passes of the
+ * micro-batches of one update (torch: `acc.add_(g)` per tensor, then `g.div_(n)`).  Same tables as fod_multi_ema, with
+ *   pairs i64 [T,2] = {accumulator, gradient} f32 pointers (same dense layout each, not overlapping).
+ * mode (a number: this header declares no constants):
+ *   0  store   acc = g                   words are moved, not interpreted; g is untouched           (8 B / element)
+ *   1  add     acc = acc + g             g is untouched                                             (12 B / element)
+ *   2  finish  g = (acc + g) * scale     acc is untouched; the sum and the product are each rounded to f32
+ *                                        (no fused multiply-add)                                    (12 B / element)
+ * so N micro-batches -- store, N - 2 adds, finish with scale = (float)(1.0 / N) -- leave
+ *   (((g1 + g2) + g3) + ... + gN) * scale  in the gradient tensors, where the optimizer reads it; a float32 restatement
+ * gives the same bits.  No atomics, every element is written by exactly one thread: the result does not depend on timing.
+ * scale is read by mode 2 only and checked in every mode.  16-byte accesses where both tensors of a pair are 16-byte
+ * aligned, a scalar tail; 4-byte accesses otherwise.  A mode outside 0..2, or a scale that is not finite or not > 0, is
+ * FOD_ERR_ARG. */
+int fod_multi_accum(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk, int nblocks,
+                    int mode, float scale, fod_stream_t stream);
 
 #ifdef __cplusplus
 }
