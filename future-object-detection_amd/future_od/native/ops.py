@@ -1091,7 +1091,8 @@ def pack_targets_dev(anno_boxes, anno_classes, anno_active, H, W):
 
 def lap_solve_batch_dev(cost, tgt_offset, status):
     """cost f32 [L,B,M,ld] on the device, tgt_offset i32 [B+1] on the device -> match i32 [L,B,M] (GLOBAL target index
-    or -1), solved on the GPU (bit-identical to lap_solve_batch_host); `status` i32 [1] device, non-zero on failure."""
+    or -1), solved on the GPU (bit-identical to lap_solve_batch_host); `status` i32 [1] device, non-zero on failure.
+    M, ld <= L.LAP_MAX_DIM (1024); beyond 256 in either, a problem is solved from LDS when n * M <= L.LAP_STAGE_FLOATS."""
     _chk(cost, "cost", torch.float32); _chk(tgt_offset, "tgt_offset", torch.int32); _chk(status, "status", torch.int32)
     Lv, B, M, ld = cost.shape
     assert tgt_offset.numel() == B + 1 and status.numel() == 1

@@ -381,6 +381,11 @@ typedef struct fod_attn_shape {
   float dq_scale;
 } fod_attn_shape;
 #define FOD_ATTN_SPLIT_WS_FLOATS_PER_TILE (8 * 2176)
+/* fod_lap_solve_batch_dev: the largest M / ld_n it takes, and, for launches beyond 256 in either, the number of costs
+ * a workgroup can stage in LDS: a problem of n targets is solved from LDS when n * M <= FOD_LAP_STAGE_FLOATS and from
+ * global memory otherwise (150 KiB less the solver's state for 1024 rows and columns). */
+#define FOD_LAP_MAX_DIM 1024
+#define FOD_LAP_STAGE_FLOATS 27648
 
 /* o = softmax((q1.k1 + q2.k2) * scale) v per head; head h = channels [32h, 32h+32) of every tensor.
  * q2/k2 NULL -> one part.  lse2 f32 [B,H,Tq] (log2 units) is saved for the backward.
@@ -572,7 +577,9 @@ int fod_pack_targets(const float* anno_boxes, const int64_t* anno_classes, const
  * (column + tgt_offset[b]) or -1.  *status (one device int, zeroed by the caller) becomes non-zero if a problem has
  * non-finite costs or is infeasible (the host solver's error cases; that problem's matches are -1).  With it the
  * reference's `C.cpu()` + scipy step (set_criterion.py:182,204) needs no host round trip, and a training step can
- * be captured as one hipGraph.  M, ld_n <= 256. */
+ * be captured as one hipGraph.  M, ld_n <= FOD_LAP_MAX_DIM (1024), FOD_ERR_ARG beyond; a target count above ld_n
+ * sets *status = 2 (1: non-finite costs, 3: infeasible).  M, ld_n <= 256 is one launch form (costs in LDS when all
+ * M * ld_n fit), anything larger another (each problem staged when its own n * M costs fit). */
 int fod_lap_solve_batch_dev(const float* cost, int nprob, int B, int M, int ld_n, const int32_t* tgt_offset,
                             int32_t* match_out, int32_t* status, fod_stream_t stream);
 
