@@ -264,7 +264,7 @@ class Mlp2MulFn(Function):
         x2 = x.view(-1, D)
         out, h, q = ops.mlp2_mul_fwd(x2, prep_linear(w1, x.dtype, False), b1, prep_linear(w2, x.dtype, False), b2, table)
         ctx.save_for_backward(x2, h, q, table)
-        ctx.params, ctx.acc, ctx.hands_on = (w1, b1, w2, b2), acc, hands_on
+        ctx.params, ctx.acc, ctx.hands_on, ctx.x_shape = (w1, b1, w2, b2), acc, hands_on, x.shape
         return out.view(x.shape)
 
     @staticmethod
@@ -281,7 +281,8 @@ class Mlp2MulFn(Function):
         dtable = None
         if ctx.needs_input_grad[1] and (ctx.acc is None or ctx.hands_on):
             dtable = cast(acc.take(), table.dtype).view(table.shape)
-        return (dx.view(-1, D).view(x2.shape) if ctx.needs_input_grad[0] else None), dtable, dw1, db1, dw2, db2, None, None
+        # (x's own shape: the decoder hands in [B * M, D], but the wrapper takes any [..., D])
+        return (dx.view(ctx.x_shape) if ctx.needs_input_grad[0] else None), dtable, dw1, db1, dw2, db2, None, None
 
 
 def mlp2_mul_fits(x, mlp, table):
@@ -949,18 +950,18 @@ def cast_ad(x, dtype, pad_cols=None):
 
 
 class WideLinearFn(Function):
-    """y[*, P*D] = x[*, Din] @ cat_p(W_p)^T + cat_p(b_p): P Linear layers sharing one input, one GEMM.
-    `x_grad=False` for an input without gradient (the positional table).  When `batch_sum` > 1 the
-    incoming gradient is [batch_sum, rows, P*D] although x is [rows, Din] (x was shared by the batch)."""
+    """y[*, P*D] = x[*, Din] @ cat_p(W_p)^T + cat_p(b_p): P Linear layers sharing one input, one GEMM.  An input without
+    gradient (the positional table) gets none.  (A batch-shared table's gradient arrives already summed over the batch:
+    HoistedCrossAttnFn does that before it hands the buffer on.)"""
 
     @staticmethod
-    def forward(ctx, x, batch_sum, *params):
+    def forward(ctx, x, *params):
         P = len(params) // 2
         weights, biases = params[:P], params[P:]
         wcat, bcat, _ = CAT.get(weights, biases, x.dtype)
         y = ops.gemm_nt(x, wcat, shift=bcat).view(*x.shape[:-1], wcat.shape[0])
         ctx.save_for_backward(x)
-        ctx.params, ctx.batch_sum = params, batch_sum
+        ctx.params = params
         return y
 
     @staticmethod
@@ -970,10 +971,7 @@ class WideLinearFn(Function):
         weights, biases = ctx.params[:P], ctx.params[P:]
         D_out, D_in = weights[0].shape
         _, _, wcat_t = CAT.get(weights, biases, x.dtype)
-        dy = dy.contiguous()
-        if ctx.batch_sum > 1:
-            dy = _sum_leading(dy, ctx.batch_sum)
-        g = dy.view(-1, P * D_out)
+        g = dy.contiguous().view(-1, P * D_out)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = ops.gemm_nt(g, wcat_t).view(x.shape)
@@ -982,7 +980,7 @@ class WideLinearFn(Function):
         WGRADS.tn(WGRADS.site(ctx.params), g, x.view(-1, D_in), dw, db)
         gw = [dw[i * D_out:(i + 1) * D_out] for i in range(P)]
         gb = [db[i * D_out:(i + 1) * D_out] for i in range(P)]
-        return (dx, None) + tuple(gw) + tuple(gb)
+        return (dx,) + tuple(gw) + tuple(gb)
 
 
 class GroupLinearFn(Function):
@@ -1070,18 +1068,20 @@ def _gather_segments(gs, rows, D, dtype, device):
 
 def group_linear(x, linears, residual=None, res_row_mod=0):
     """[m(x) for m in linears] for nn.Linear-like holders of equal shape; grouped launches in bf16, plain
-    per-layer launches otherwise (fp32 parity mode, odd widths).  `residual`: a list of [R, D] tables added to the first
-    len(residual) results, row m + table[m % res_row_mod] -- inside the launch when the tables are consecutive blocks of
-    one buffer (what an earlier group_linear returns), as separate additions otherwise."""
+    per-layer launches otherwise (fp32 parity mode, odd widths).  `residual`: a list of [res_row_mod, D] tables added to
+    the first len(residual) results, row m + table[m % res_row_mod] -- inside the launch when the tables are consecutive
+    blocks of one buffer (what an earlier group_linear returns), as separate additions otherwise.  A table has exactly
+    res_row_mod rows (the decoder's query positions): the gradient of a longer one would need zero rows behind the sum."""
     D, K = linears[0].weight.shape
     same = all(tuple(m.weight.shape) == (D, K) and m.bias is not None for m in linears)
     res = list(residual) if residual is not None else []
+    assert not res_row_mod or all(r.shape[0] == res_row_mod for r in res), "group_linear(residual=...): tables of res_row_mod rows"
     if x.dtype != torch.bfloat16 or not same or D % 64 or K % 32 or len(linears) < 2:
         out = [linear(x, m.weight, m.bias) for m in linears]
         fused = False
     else:
         fused = bool(res) and SW.FOD_GROUP_RESIDUAL and all(r.dim() == 2 and r.shape[1] == D and r.dtype == x.dtype for r in res) \
-            and _as_segments(res, res[0].shape[0], D) is not None and 0 < res_row_mod <= res[0].shape[0]
+            and _as_segments(res, res[0].shape[0], D) is not None and 0 < res_row_mod == res[0].shape[0]
         out = list(GroupLinearFn.apply(x.contiguous(), len(res) if fused else 0, res_row_mod if fused else 0,
                                        *(res if fused else []), *[m.weight for m in linears], *[m.bias for m in linears]))
     if res and not fused:
@@ -1227,10 +1227,10 @@ def _sum_leading(t, n):
     return acc.contiguous()
 
 
-def wide_linear(x, linears, batch_sum=1):
+def wide_linear(x, linears):
     ws = [m.weight for m in linears]
     bs = [m.bias for m in linears]
-    return WideLinearFn.apply(x.contiguous(), batch_sum, *ws, *bs)
+    return WideLinearFn.apply(x.contiguous(), *ws, *bs)
 
 
 class MemorySide:
