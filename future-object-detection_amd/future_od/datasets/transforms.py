@@ -16,6 +16,10 @@ Plannable is: crops (a rectangle inside a rectangle composes exactly), then at m
 `JointHorizontalFlip`, with `SizeFilter` / no-ops anywhere; `RandomSelect` plans the branch it draws.  Anything else
 would need a second resampling: `plan` raises ValueError naming the step, it never approximates.
 
+`JointPhotometricDistortion` is the colour half: per-pixel work, which commutes exactly with crops and flips but not
+with resampling.  A plan carries at most one row of it (`Plan.photo`), drawn once per clip, and a `JointResize` may not
+follow it; `fod_clip_crop_resize_photo` applies the row to the resampled pixels in the same pass.
+
 Random numbers come from a `random.Random`-like `rng`; `rng=None` (and `__call__`) means Python's global `random`
 module, so `random.seed(s); t(...)` and `t.plan(h, w, random.Random(s))` draw the same numbers.
 
@@ -68,6 +72,58 @@ def annotate(step, boxes, classes):
     raise ValueError(f"unknown annotation step {step!r}")
 
 
+# ---- the photometric row: (delta, alpha, sat, hue, first), one per clip ------------------------------------------------
+PHOTO_NEUTRAL = (0.0, 1.0, 1.0, 0.0, 0.0)
+
+
+def sanitise_photo_row(row):
+    """The row as the kernel uses it, in float32: a non-finite delta / alpha / sat / hue becomes its neutral value, then
+    delta -> [-1, 1], alpha and sat -> [0, 4], hue -> hue - floor(hue); first counts as set unless it equals 0.
+    -> (delta, alpha, sat, hue, first) as python floats that are float32 values, and a bool."""
+    v = torch.tensor([float(x) for x in row], dtype=torch.float32)
+    if v.shape != (5,):
+        raise ValueError(f"a photometric row is (delta, alpha, sat, hue, first), got {tuple(row)!r}")
+    v[:4] = torch.where(torch.isfinite(v[:4]), v[:4], torch.tensor(PHOTO_NEUTRAL[:4]))
+    delta, alpha, sat = v[0].clamp(-1, 1), v[1].clamp(0, 4), v[2].clamp(0, 4)
+    hue = v[3] - torch.floor(v[3])
+    return float(delta), float(alpha), float(sat), float(hue), not bool(v[4] == 0)
+
+
+def photometric(images, row):
+    """The photometric map of include/fod_ext.h (fod_clip_crop_resize_photo, steps 1-5) on a float32 clip [..., 3, h, w]
+    in 0..1, every step in float32: ONE row for all frames.  A neutral row returns `images` itself."""
+    delta, alpha, sat, hue, first = sanitise_photo_row(row)
+    hsv = sat != 1.0 or hue != 0.0
+    if delta == 0.0 and alpha == 1.0 and not hsv:
+        return images
+    if images.dtype != torch.float32 or images.dim() < 3 or images.shape[-3] != 3:
+        raise ValueError(f"the photometric map takes a float32 clip [..., 3, h, w], got {images.dtype} {tuple(images.shape)}")
+    p = images + delta
+    if first:
+        p = p * alpha
+    if hsv:
+        r, g, b = p.clamp(0, 1).unbind(-3)
+        v, m = torch.maximum(r, torch.maximum(g, b)), torch.minimum(r, torch.minimum(g, b))
+        c = v - m
+        grey = c == 0
+        cs = torch.where(grey, torch.ones_like(c), c)                     # a safe divisor; grey pixels take the zeros
+        s = torch.where(grey, torch.zeros_like(c), c / torch.where(grey, torch.ones_like(v), v))
+        h6 = torch.where(v == r, torch.remainder((g - b) / cs, 6.0),
+                         torch.where(v == g, (b - r) / cs + 2.0, (r - g) / cs + 4.0))
+        h6 = torch.where(grey, torch.zeros_like(c), h6)
+        s = (s * sat).clamp(max=1)
+        h = h6 / 6.0 + hue
+        h = h - torch.floor(h)
+
+        def f(n):
+            k = torch.fmod(n + 6.0 * h, 6.0)
+            return v - v * s * torch.minimum(torch.minimum(k, 4.0 - k), torch.ones_like(k)).clamp(min=0)
+        p = torch.stack([f(5.0), f(3.0), f(1.0)], dim=-3)
+    if not first:
+        p = p * alpha
+    return p.clamp(0, 1)
+
+
 class Plan:
     """Composed geometry of a joint transform for one frame size: `rect` = (top, left, height, width) in the source
     frame, `size` = (H, W) of the output, `flip`, and the annotation `steps` in the order they were composed."""
@@ -78,11 +134,17 @@ class Plan:
         self.size = (int(h), int(w))
         self.flip = False
         self.steps = []
+        self.photo = None                     # (delta, alpha, sat, hue, first) of a JointPhotometricDistortion, if any
         self._resized = self._flip_seen = False
 
     def row(self):
         """(top, left, height, width, flip): a row of the `plans` operand of ops.clip_crop_resize."""
         return (*self.rect, int(self.flip))
+
+    def photo_row(self):
+        """(delta, alpha, sat, hue, first): a row of the `photo` operand of ops.clip_crop_resize_photo; the neutral row
+        for a plan without a photometric step."""
+        return PHOTO_NEUTRAL if self.photo is None else tuple(float(v) for v in self.photo)
 
     def annotate(self, boxes, classes):
         for step in self.steps:
@@ -158,6 +220,9 @@ class JointResize(JointTransform):
     def _extend(self, plan, rng):
         if self._interpolation != "bilinear":
             raise ValueError(f"JointResize(interpolation={self._interpolation!r}) cannot be planned: the device pass is bilinear")
+        if plan.photo is not None:
+            raise ValueError("JointResize after a JointPhotometricDistortion cannot be planned: per-pixel colour work "
+                             "does not commute with resampling (put the photometric step last)")
         if plan._resized:
             raise ValueError("JointResize after a JointResize cannot be planned: two resamplings are not one bilinear pass")
         if plan._flip_seen:
@@ -286,3 +351,75 @@ class SizeFilter(JointTransform):
 
     def _extend(self, plan, rng):
         plan.steps.append(("size_filter", plan.size[1], plan.size[0], self.min_size))
+
+
+class JointPhotometricDistortion(JointTransform):
+    """Brightness, contrast, saturation and hue jitter, drawn ONCE per clip and applied identically to all its frames
+    (the standard colour augmentation of camera detectors; the reference has none).  The map is `photometric` above.
+
+    Nine numbers are drawn, always, in this order -- so the generator ends in the same state whatever they decide:
+        u_b, delta in [-brightness_delta, brightness_delta]      brightness is applied iff u_b < p
+        u_c, alpha in contrast_range                             contrast likewise
+        u_s, sat   in saturation_range                           saturation
+        u_h, hue   in [-hue_delta, hue_delta] (turns)            hue
+        u_f                                                      first = u_f < 0.5: contrast before the HSV stage
+    A stage that is not applied takes its neutral value.  Boxes and classes pass through.
+
+    `__call__` takes a float clip [L, 3, h, w] in 0..1 and does not normalise; with `pixel_mean` / `pixel_std` (three
+    numbers each) the clip is a normalised one: it is de-normalised first and re-normalised after."""
+
+    def __init__(self, brightness_delta=32 / 255, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5),
+                 hue_delta=18 / 360, p=0.5, pixel_mean=None, pixel_std=None):
+        self._brightness_delta, self._hue_delta, self._p = float(brightness_delta), float(hue_delta), float(p)
+        self._contrast_range = tuple(float(v) for v in contrast_range)
+        self._saturation_range = tuple(float(v) for v in saturation_range)
+        if not 0.0 <= self._brightness_delta <= 1.0:
+            raise ValueError(f"brightness_delta {brightness_delta!r} is not in [0, 1] (the 0..1 scale)")
+        if not 0.0 <= self._hue_delta <= 0.5:
+            raise ValueError(f"hue_delta {hue_delta!r} is not in [0, 0.5] turns")
+        for name, rng_ in (("contrast_range", self._contrast_range), ("saturation_range", self._saturation_range)):
+            if len(rng_) != 2 or not 0.0 <= rng_[0] <= rng_[1] <= 4.0:
+                raise ValueError(f"{name} {rng_!r} is not (low, high) with 0 <= low <= high <= 4")
+        if not 0.0 <= self._p <= 1.0:
+            raise ValueError(f"p {p!r} is not a probability")
+        if (pixel_mean is None) != (pixel_std is None):
+            raise ValueError("pixel_mean and pixel_std are given together or not at all")
+        self._norm = None
+        if pixel_mean is not None:
+            mean, std = (torch.tensor([float(v) for v in t], dtype=torch.float32) for t in (pixel_mean, pixel_std))
+            if mean.shape != (3,) or std.shape != (3,) or not bool((std > 0).all()):
+                raise ValueError("pixel_mean / pixel_std are three numbers each, the deviations positive")
+            self._norm = (mean.view(3, 1, 1), std.view(3, 1, 1))
+
+    def _draw(self, rng):
+        row = []
+        for neutral, low, high in ((0.0, -self._brightness_delta, self._brightness_delta),
+                                   (1.0, *self._contrast_range), (1.0, *self._saturation_range),
+                                   (0.0, -self._hue_delta, self._hue_delta)):
+            applied, value = rng.random() < self._p, rng.uniform(low, high)
+            row.append(value if applied else neutral)
+        row.append(1.0 if rng.random() < 0.5 else 0.0)
+        return tuple(row)
+
+    def __call__(self, images, boxes, classes):
+        row = self._draw(_random)
+        if self._norm is None:
+            return photometric(images, row), boxes, classes
+        mean, std = self._norm
+        return (photometric(images * std + mean, row) - mean) / std, boxes, classes
+
+    def _extend(self, plan, rng):
+        if plan.photo is not None:
+            raise ValueError("JointPhotometricDistortion after a JointPhotometricDistortion cannot be planned: a clip "
+                             "has one photometric row")
+        plan.photo = self._draw(rng)
+
+
+def has_photometric(transform):
+    """Whether a JointPhotometricDistortion stands anywhere in `transform` (inside JointCompose / RandomSelect too): then
+    its plans may carry a row, and the device half takes the `photo` operand."""
+    if isinstance(transform, JointPhotometricDistortion):
+        return True
+    inner = list(getattr(transform, "transforms", ())) if isinstance(transform, JointCompose) else \
+        [transform.transforms1, transform.transforms2] if isinstance(transform, RandomSelect) else []
+    return any(has_photometric(t) for t in inner)

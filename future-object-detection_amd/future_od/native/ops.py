@@ -402,29 +402,56 @@ def clip_to_stem_layout(video, dtype, mean=None, std=None):
     return out
 
 
-def clip_crop_resize(video_u8, plans, size, mean, std):
-    """Raw uint8 frames [B,L,C<=3,H0,W0] + device plans int32 [B,5] = (top, left, height, width, flip) -> the normalised
-    f32 clip [B,L,C,*size]: crop, bilinear resize (align_corners=False), flip and pixel pipeline in one pass; see
-    fod_clip_crop_resize.  The kernel reads the plans from device memory and clamps a rectangle that leaves the frame."""
+def _clip_crop_resize(who, video_u8, plans, size, mean, std, photo=None):
     if not isinstance(video_u8, torch.Tensor) or not video_u8.is_cuda or video_u8.dtype != torch.uint8 \
             or video_u8.dim() != 5:
-        raise L.FodError("clip_crop_resize: video must be a uint8 device tensor [B, L, C, H0, W0] "
+        raise L.FodError(f"{who}: video must be a uint8 device tensor [B, L, C, H0, W0] "
                          "(the HIP path has no CPU fallback)")
     b, l, c, h0, w0 = video_u8.shape
     sb, sl, sc, sh, sw = video_u8.stride()
     if c > 3 or (sc, sh, sw) != (h0 * w0, w0, 1):
-        raise L.FodError(f"clip_crop_resize: frame planes must be contiguous, got strides {video_u8.stride()}")
+        raise L.FodError(f"{who}: frame planes must be contiguous, got strides {video_u8.stride()}")
     _chk(plans, "plans", torch.int32); _chk(mean, "mean", torch.float32); _chk(std, "std", torch.float32)
     if tuple(plans.shape) != (b, 5) or mean.numel() != c or std.numel() != c:
-        raise L.FodError(f"clip_crop_resize: plans {tuple(plans.shape)} / mean {mean.numel()} / std {std.numel()} do not "
+        raise L.FodError(f"{who}: plans {tuple(plans.shape)} / mean {mean.numel()} / std {std.numel()} do not "
                          f"fit a clip of {b} x {c} planes")
     if not (plans.device == mean.device == std.device == video_u8.device):
-        raise L.FodError("clip_crop_resize: operands live on different devices")
+        raise L.FodError(f"{who}: operands live on different devices")
     h, w = (int(v) for v in size)
+    if photo is None:
+        out = torch.empty((b, l, c, h, w), dtype=torch.float32, device=video_u8.device)
+        call("fod_clip_crop_resize", ptr(video_u8), ptr(out), b, l, c, h0, w0, h, w, sb, sl, ptr(plans), ptr(mean),
+             ptr(std), stream())
+        return out
+    if not isinstance(photo, torch.Tensor):
+        raise L.FodError(f"{who}: photo must be an f32 device tensor [B, 5]")
+    _chk(photo, "photo", torch.float32)
+    if tuple(photo.shape) != (b, 5) or photo.device != video_u8.device:
+        raise L.FodError(f"{who}: photo {tuple(photo.shape)} on {photo.device} is not one row of 5 per clip of {b} on "
+                         f"{video_u8.device}")
+    if c != 3:
+        raise L.FodError(f"{who}: the photometric map mixes three planes, got C = {c}")
     out = torch.empty((b, l, c, h, w), dtype=torch.float32, device=video_u8.device)
-    call("fod_clip_crop_resize", ptr(video_u8), ptr(out), b, l, c, h0, w0, h, w, sb, sl, ptr(plans), ptr(mean), ptr(std),
-         stream())
+    call("fod_clip_crop_resize_photo", ptr(video_u8), ptr(out), b, l, c, h0, w0, h, w, sb, sl, ptr(plans), ptr(mean),
+         ptr(std), ptr(photo), stream())
     return out
+
+
+def clip_crop_resize(video_u8, plans, size, mean, std):
+    """Raw uint8 frames [B,L,C<=3,H0,W0] + device plans int32 [B,5] = (top, left, height, width, flip) -> the normalised
+    f32 clip [B,L,C,*size]: crop, bilinear resize (align_corners=False), flip and pixel pipeline in one pass; see
+    fod_clip_crop_resize.  The kernel reads the plans from device memory and clamps a rectangle that leaves the frame."""
+    return _clip_crop_resize("clip_crop_resize", video_u8, plans, size, mean, std)
+
+
+def clip_crop_resize_photo(video_u8, plans, size, mean, std, photo):
+    """clip_crop_resize with the photometric half in the same pass: `photo` f32 [B,5] = (delta, alpha, sat, hue, first)
+    on the clip's device, one row per clip for all its frames (include/fod_ext.h, fod_clip_crop_resize_photo, states the
+    map).  C must be 3.  The kernel reads the rows from device memory and sanitises them; a neutral row gives
+    clip_crop_resize's bits.  There is no CPU fallback."""
+    if photo is None:
+        raise L.FodError("clip_crop_resize_photo: photo must be an f32 device tensor [B, 5]")
+    return _clip_crop_resize("clip_crop_resize_photo", video_u8, plans, size, mean, std, photo)
 
 
 def conv_stem_fwd(xp, w, h, wd, *, shift=None, relu=True):

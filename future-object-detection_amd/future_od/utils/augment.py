@@ -8,6 +8,9 @@ upload, which is a quarter of the bytes a float clip would take over PCIe.
     batch = ...to(device)...
     batch = t.device(batch)        # after it, on the current stream: video becomes f32 [B, L, 3, 448, 800]
 
+With a `JointPhotometricDistortion` in the joint transform the plans also carry one photometric row per clip: `host`
+adds `photo` f32 [B, 5], and `device` runs `ops.clip_crop_resize_photo` -- the same single launch -- instead.
+
 `DevicePrefetcher` calls the two halves for a loader that carries a `device_transform` attribute.  The batch that
 reaches the model has the usual keys, shapes and dtypes, so a captured step is captured once and replayed.
 There is no CPU fallback for the kernel."""
@@ -15,15 +18,17 @@ import random
 
 import torch
 
+from future_od.datasets.transforms import has_photometric
 from future_od.utils.recursive_functions import HOST_ANNOTATIONS
 
-PLANS, PLAN_SIZE = "plans", "_plan_size"
+PLANS, PLAN_SIZE, PHOTO = "plans", "_plan_size", "photo"
 
 
 class DeviceJointTransform:
     def __init__(self, joint_transform, seed=0, rank=0):
         self.joint_transform = joint_transform
         self.seed, self.rank = int(seed), int(rank)
+        self.photometric = has_photometric(joint_transform)      # then every batch carries `photo`
         self._index = 0                       # batches planned so far
         self._norm = {}                       # device -> (mean, std)
 
@@ -37,8 +42,9 @@ class DeviceJointTransform:
     def host(self, batch, index=None):
         """-> a new batch dict: `boxes`, `classes`, `active` (and the non-zero rows of `ignore_boxes`) transformed --
         kept rows first, in their old order, freed rows zero / inactive, the dense padding of the reference's datasets
-        (datasets/utils.py:19-38) -- plus `plans` int32 [B, 5] for the device half.  `_host_annotations` holds the
-        transformed tensors.  A batch with none of `boxes`, `classes`, `active` is label-free: see _host_label_free."""
+        (datasets/utils.py:19-38) -- plus `plans` int32 [B, 5] (and, with a photometric step, `photo` f32 [B, 5]) for the
+        device half.  `_host_annotations` holds the transformed tensors.  A batch with none of `boxes`, `classes`,
+        `active` is label-free: see _host_label_free."""
         video = batch["video"]
         if video.dtype != torch.uint8 or video.dim() != 5:
             raise ValueError(f"the device transform takes raw uint8 clips [B, L, 3, H0, W0], got {video.dtype} {tuple(video.shape)}")
@@ -55,10 +61,13 @@ class DeviceJointTransform:
         boxes, classes, active = (torch.zeros_like(batch[k]) for k in ("boxes", "classes", "active"))
         ignore = torch.zeros_like(batch["ignore_boxes"]) if "ignore_boxes" in batch else None
         plans, size = torch.zeros(B, 5, dtype=torch.int32), None
+        photo = torch.zeros(B, 5, dtype=torch.float32) if self.photometric else None
         for b in range(B):
             plan = self._plan(index, b, h0, w0, size)
             size = plan.size
             plans[b] = torch.tensor(plan.row(), dtype=torch.int32)
+            if photo is not None:
+                photo[b] = torch.tensor(plan.photo_row(), dtype=torch.float32)
             rows = batch["active"][b].bool()
             bx, cl = plan.annotate(batch["boxes"][b][rows], batch["classes"][b][rows])
             n = bx.shape[0]
@@ -73,6 +82,8 @@ class DeviceJointTransform:
         if ignore is not None:
             out["ignore_boxes"] = ignore
         out[PLANS], out[PLAN_SIZE] = plans, size
+        if photo is not None:
+            out[PHOTO] = photo
         out[HOST_ANNOTATIONS] = {"active": active, "boxes": boxes, "classes": classes}
         return out
 
@@ -89,10 +100,13 @@ class DeviceJointTransform:
         (SpatioTemporalDETR.predict reads it).  `ignore_boxes`, if there, is transformed as for a labelled batch."""
         plans, box_map, size = torch.zeros(B, 5, dtype=torch.int32), torch.zeros(B, 4, dtype=torch.float32), None
         ignore = torch.zeros_like(batch["ignore_boxes"]) if "ignore_boxes" in batch else None
+        photo = torch.zeros(B, 5, dtype=torch.float32) if self.photometric else None
         for b in range(B):
             plan = self._plan(index, b, h0, w0, size)
             size = plan.size
             plans[b] = torch.tensor(plan.row(), dtype=torch.int32)
+            if photo is not None:
+                photo[b] = torch.tensor(plan.photo_row(), dtype=torch.float32)
             box_map[b] = torch.tensor(plan.box_map(), dtype=torch.float32)
             if ignore is not None:
                 old = batch["ignore_boxes"][b]
@@ -103,11 +117,13 @@ class DeviceJointTransform:
         if ignore is not None:
             out["ignore_boxes"] = ignore
         out[PLANS], out[PLAN_SIZE], out["box_map"] = plans, size, box_map
+        if photo is not None:
+            out[PHOTO] = photo
         return out
 
     def device(self, batch):
         """-> the batch with `video` = the transformed, normalised f32 clip at the plans' output size (queued on the
-        current stream) and without the plan entries."""
+        current stream) and without the plan entries (`photo`, if the host half added it, among them)."""
         from future_od.native import ops
         from future_od.native.backbone import ResNetBody
         video = batch["video"]
@@ -118,6 +134,10 @@ class DeviceJointTransform:
         if norm is None:
             norm = self._norm[video.device] = tuple(torch.tensor(v, dtype=torch.float32, device=video.device)
                                                     for v in (ResNetBody.PIXEL_MEAN, ResNetBody.PIXEL_STD))
-        out = {k: v for k, v in batch.items() if k not in (PLANS, PLAN_SIZE)}
-        out["video"] = ops.clip_crop_resize(video, batch[PLANS], batch[PLAN_SIZE], *norm)
+        if not self.photometric:
+            out = {k: v for k, v in batch.items() if k not in (PLANS, PLAN_SIZE)}
+            out["video"] = ops.clip_crop_resize(video, batch[PLANS], batch[PLAN_SIZE], *norm)
+            return out
+        out = {k: v for k, v in batch.items() if k not in (PLANS, PLAN_SIZE, PHOTO)}
+        out["video"] = ops.clip_crop_resize_photo(video, batch[PLANS], batch[PLAN_SIZE], *norm, batch[PHOTO])
         return out

@@ -12,7 +12,11 @@ training clips go through `JointCompose([random_aug, JointResize(img_size)])` an
 `JointCompose([JointCenterCrop(img_size)])`.  The source then yields RAW uint8 frames at the camera's size with boxes
 in those coordinates, and the loader carries the transform as `device_transform`: `DevicePrefetcher` transforms the
 annotations on the host and the frames on the GPU (future_od/utils/augment.py).  `random_aug=None` is the plain
-source: normalised float clips at `img_size`, no transform."""
+source: normalised float clips at `img_size`, no transform.
+
+`photometric` (a `T.JointPhotometricDistortion`; the reference has no colour augmentation) is appended to the training
+transform, after the resize: `JointCompose([random_aug, JointResize(img_size), photometric])`.  Its row is drawn once per
+clip and applied by the same device pass.  The validation transform stays as it is."""
 import torch
 
 import future_od.datasets.transforms as T
@@ -72,12 +76,13 @@ class SyntheticLoader:
 
 def get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_aug=None,
                      val_annotated_frame_override=None, filter_offsets=None, val_batch_size=None, steps_per_epoch=None,
-                     val_steps=None, raw_size=None):
+                     val_steps=None, raw_size=None, photometric=None):
     """-> (train_loader, {"val": val_loader}); `train_batch_size` is GLOBAL (reference :110-112).  `offsets` may be a
     dict {"train": ..., "val": ...} (reference :64-68).  `random_aug`: a joint transform (the reference's default is
     `T.RandomSizedCrop(0.5, 1.0)`) switches both loaders to raw uint8 frames of `raw_size` (default: the camera's
     `nu_scenes.ORIGINAL_IMSIZE`) plus the reference's transforms, applied by `DevicePrefetcher`; None (the default
-    here) keeps the plain source.  The filter arguments exist for call compatibility; the synthetic source has no
+    here) keeps the plain source.  `photometric`: a `T.JointPhotometricDistortion` appended to the training transform
+    (it needs a `random_aug`: the plain source has no device pass to apply it in).  The filter arguments exist for call compatibility; the synthetic source has no
     offsets to filter."""
     size = img_size
     if isinstance(offsets, dict):
@@ -92,9 +97,13 @@ def get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_a
     steps = steps_per_epoch or getattr(args, "steps_per_epoch", 8)
     vsteps = val_steps or getattr(args, "val_steps", 2)
     train_tf = val_tf = None
+    if photometric is not None and random_aug is None:
+        raise ValueError("photometric needs a random_aug: without one the loaders yield the plain source, which no "
+                         "device transform touches")
     if random_aug is not None:
         raw_size = tuple(raw_size) if raw_size is not None else nu_scenes.ORIGINAL_IMSIZE
-        train_tf = T.JointCompose([random_aug, T.JointResize(size=img_size)])
+        train_tf = T.JointCompose([random_aug, T.JointResize(size=img_size)]
+                                  + ([photometric] if photometric is not None else []))
         val_tf = T.JointCompose([T.JointCenterCrop(size=img_size)])
     train = SyntheticLoader(size, offsets, per_gpu, steps, rank, world, seed=1234, raw_size=raw_size,
                             joint_transform=train_tf)
@@ -104,8 +113,8 @@ def get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_a
 
 
 def get_nuim_loaders(img_size, offsets, args, config, train_batch_size, random_aug=None,
-                     val_annotated_frame_override=None, **kw):
+                     val_annotated_frame_override=None, *, photometric=None, **kw):
     """Reference runs/_loader.py:10-50: NuImages clips are addressed by FRAME INDEX offsets around the annotated frame
     (`nu_images.ANNOTATED_FRAME + offset`); only their count matters to the synthetic source."""
     return get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_aug,
-                            val_annotated_frame_override, **kw)
+                            val_annotated_frame_override, photometric=photometric, **kw)

@@ -52,6 +52,33 @@ int fod_multi_swap(const long* pairs, const long* numel, const int* blk_tensor, 
  * FOD_ERR_ARG. */
 int fod_multi_accum(const long* pairs, const long* numel, const int* blk_tensor, const int* blk_chunk, int nblocks,
                     int mode, float scale, fod_stream_t stream);
+/* fod_clip_crop_resize (fod.h) with the photometric half of the augmentation in the same pass: brightness, contrast,
+ * saturation and hue jitter, drawn once per clip and applied identically to its L frames.  Arguments, geometry and
+ * checks are fod_clip_crop_resize's, plus
+ *   photo: DEVICE f32 [B][5] = (delta, alpha, sat, hue, first), one row per clip: brightness added on the 0..1 scale,
+ *   contrast factor, saturation factor, hue rotation in turns, and first != 0: contrast before the HSV stage, else after.
+ * The map mixes the three planes of a pixel: C must be 3 (anything else is FOD_ERR_ARG).  The neutral row is
+ * (0, 1, 1, 0, any).  For a pixel p = (r, g, b) = the bilinear sample / 255 (what fod_clip_crop_resize holds just before
+ * it normalises), every step in f32:
+ *   1. p += delta
+ *   2. if first: p *= alpha
+ *   3. only if sat != 1 or hue != 0, the HSV stage:
+ *        p = clamp(p, 0, 1);  v = max(r, g, b), m = min(r, g, b), c = v - m;  s = c > 0 ? c / v : 0
+ *        h6 = 0 if c == 0;  else fmod((g - b) / c, 6) made non-negative if v == r;  else (b - r) / c + 2 if v == g;
+ *             else (r - g) / c + 4;   h = h6 / 6
+ *        s = min(s * sat, 1);  h = h + hue, h -= floor(h)
+ *        with k(n) = fmod(n + 6 h, 6) and f(n) = v - v * s * max(0, min(k, 4 - k, 1)):  (r, g, b) = (f(5), f(3), f(1))
+ *   4. if not first: p *= alpha
+ *   5. p = clamp(p, 0, 1)
+ *   6. (p[c] - mean[c]) / std[c], as fod_clip_crop_resize
+ * The map is continuous in (r, g, b): a grey pixel has s = 0, so its undefined hue never reaches the output.  A clip
+ * whose row is neutral skips steps 1-5: its output is bit-equal to fod_clip_crop_resize's.
+ * The row is read by the kernel and never trusted: a non-finite delta, alpha, sat or hue is replaced by its neutral
+ * value; then delta is clamped to [-1, 1], alpha and sat to [0, 4], and hue becomes hue - floor(hue); first counts as set
+ * unless it equals 0.  Whatever the row holds, every output is finite. */
+int fod_clip_crop_resize_photo(const unsigned char* src, float* dst, int B, int L, int C, int H0, int W0, int H, int W,
+                               long src_stride_b, long src_stride_l, const int* plans, const float* mean,
+                               const float* std, const float* photo, fod_stream_t stream);
 
 #ifdef __cplusplus
 }
