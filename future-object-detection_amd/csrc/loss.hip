@@ -161,22 +161,23 @@ FOD_DEVINL void giou_loss_grad(const float* pbox, const float* tbox, float* g) {
   const float hh_raw = fmaxf(a.y1, t.y1) - fminf(a.y0, t.y0);
   const float hw = fmaxf(hw_raw, 0.f), hh = fmaxf(hh_raw, 0.f);
   const float hull = hw * hh;
-  // partials wrt (x0, y0, x1, y1) of the predicted box
+  // partials wrt (x0, y0, x1, y1) of the predicted box; the subgradients are torch autograd's: clamp(min=0) passes the
+  // gradient where its argument is exactly 0 (`raw >= 0`, touching boxes), a tied min / max splits it evenly (+-0.5)
   float d_area[4] = {-ah, -aw, ah, aw};
   float d_iw[4] = {0, 0, 0, 0}, d_ih[4] = {0, 0, 0, 0}, d_hw[4] = {0, 0, 0, 0}, d_hh[4] = {0, 0, 0, 0};
-  if (iw_raw > 0.f) {
+  if (iw_raw >= 0.f) {
     if (a.x0 > t.x0) d_iw[0] = -1.f; else if (a.x0 == t.x0) d_iw[0] = -0.5f;
     if (a.x1 < t.x1) d_iw[2] = 1.f; else if (a.x1 == t.x1) d_iw[2] = 0.5f;
   }
-  if (ih_raw > 0.f) {
+  if (ih_raw >= 0.f) {
     if (a.y0 > t.y0) d_ih[1] = -1.f; else if (a.y0 == t.y0) d_ih[1] = -0.5f;
     if (a.y1 < t.y1) d_ih[3] = 1.f; else if (a.y1 == t.y1) d_ih[3] = 0.5f;
   }
-  if (hw_raw > 0.f) {
+  if (hw_raw >= 0.f) {
     if (a.x0 < t.x0) d_hw[0] = -1.f; else if (a.x0 == t.x0) d_hw[0] = -0.5f;
     if (a.x1 > t.x1) d_hw[2] = 1.f; else if (a.x1 == t.x1) d_hw[2] = 0.5f;
   }
-  if (hh_raw > 0.f) {
+  if (hh_raw >= 0.f) {
     if (a.y0 < t.y0) d_hh[1] = -1.f; else if (a.y0 == t.y0) d_hh[1] = -0.5f;
     if (a.y1 > t.y1) d_hh[3] = 1.f; else if (a.y1 == t.y1) d_hh[3] = 0.5f;
   }

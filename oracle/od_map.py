@@ -65,7 +65,9 @@ def prepare_od_map_stuffs(pred_boxes, pred_scores, anno_boxes, anno_classes, ann
         for c in range(C):
             avail = (aa[b] == 1) & ((ac[b] == c) | (c == C - 1))    # od_map.py:120-129
             num_annos[c] += (avail[:, None] & anno_cats[b]).sum(0)
-            order = torch.from_numpy(ps[b, :, c]).sort(descending=True)[1].numpy()[:K]
+            # stable: equal scores keep their index order (a saturated sigmoid gives exact ties); identical to the
+            # reference's sort wherever the scores are distinct
+            order = torch.from_numpy(ps[b, :, c]).sort(descending=True, stable=True)[1].numpy()[:K]
             confs[:, c, b * K:(b + 1) * K] = ps[b, order, c]
             sizes[c, :, b * K:(b + 1) * K] = pred_cats[b, order].T
             for t in range(T):
