@@ -1,0 +1,243 @@
+// Visualisation (reference future_od/utils/visualization.py: revert_imagenet_normalization, draw_boxes, the `* 255` and
+// `.byte()` of visualize): one frame per sample of a clip becomes an 8-bit interleaved RGB picture with box outlines
+// painted on it, in ONE launch.  include/fod_ext.h (fod_render_boxes) states the map; future_od/utils/visualization.py
+// (draw_boxes) is its CPU form.
+//
+// Memory-bound when few boxes reach a pixel: 12 B read (f32) or 3 B (uint8) and 3 B written per pixel.  A block owns a
+// tile of RB_TILE_H rows x RB_TILE_W pixels.  It first stages the sample's boxes into LDS -- the four integer edges and
+// the packed colour, in index order, without the boxes that are not drawn and (RB_CULL) without those whose bars cannot
+// reach the tile -- then every thread produces four consecutive pixels of a row: one 16-byte load per plane, the staged
+// boxes scanned from the last to the first until each pixel has its colour (the painter's order: the highest index
+// wins), twelve bytes out as three dword stores.  A wave is one row of the tile, so a box's row tests are wave-uniform
+// and the LDS reads are broadcasts.  Rows whose addresses are not aligned, and the W % 4 tail, go element by element.
+// No atomics, no traffic between blocks, every output byte written by exactly one thread.
+#include "common.h"
+#include "../../include/fod_ext.h"
+
+#include <climits>
+
+// 1: boxes whose bars miss the block's tile are not staged.  Measured (profiles/render_boxes_cost.txt); the product
+// build keeps the faster form, tools/measure_render.py builds the other one beside it.
+#ifndef RB_CULL
+#define RB_CULL 1
+#endif
+
+namespace {
+
+constexpr int RB_THREADS = 256;
+constexpr int RB_WAVES = RB_THREADS / 64;
+constexpr int RB_TILE_W = 64 * 4;           // one wave, four pixels per lane
+constexpr int RB_TILE_H = 16;               // RB_WAVES rows at a time
+constexpr int RB_MAX_BOXES = 1024;          // the matcher's query limit
+
+// v = x * std + mean, then v * 255: three roundings, no fused multiply-add.  Truncated towards zero and clamped to
+// 0..255; a value that is not finite gives 0.  The pragma keeps the product and the sum apart (optim.hip, ema_step:
+// hipcc's default contraction fuses them otherwise, and a float32 restatement then differs at the truncation).
+FOD_DEVINL unsigned to_byte(float x, float sd, float m) {
+#pragma clang fp contract(off)
+  const float v = x * sd;
+  const float u = v + m;
+  const float w = u * 255.f;
+  if (!(fabsf(w) <= 3.402823466e38f)) return 0u;            // NaN: false
+  return (unsigned)fminf(fmaxf(w, 0.f), 255.f);              // in range: the cast truncates
+}
+FOD_DEVINL unsigned to_byte(unsigned char x, float, float) { return x; }
+
+FOD_DEVINL int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// Bit j set iff column x + j lies in [lo, hi), j = 0..3: the bits from clamp(lo - x) up to clamp(hi - x).  An empty or
+// reversed range gives 0.
+FOD_DEVINL unsigned columns(int x, int lo, int hi) {
+  const int a = min(max(lo - x, 0), 4), b = min(max(hi - x, 0), 4);
+  return ((1u << b) - 1u) & ~((1u << a) - 1u);
+}
+
+template <typename T>
+struct Quad;                                 // four consecutive elements of a plane in one load
+template <>
+struct Quad<float> {
+  float4 v;
+  FOD_DEVINL void load(const float* p) { v = *reinterpret_cast<const float4*>(p); }
+  FOD_DEVINL float at(int j) const { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+  static constexpr unsigned ALIGN = 16;
+};
+template <>
+struct Quad<unsigned char> {
+  unsigned v;
+  FOD_DEVINL void load(const unsigned char* p) { v = *reinterpret_cast<const unsigned*>(p); }
+  FOD_DEVINL unsigned char at(int j) const { return (unsigned char)(v >> (8 * j)); }
+  static constexpr unsigned ALIGN = 4;
+};
+
+template <typename T>
+__global__ __launch_bounds__(RB_THREADS) void render_boxes_kernel(const T* __restrict__ src,
+                                                                  unsigned char* __restrict__ dst, int L, int H, int W,
+                                                                  long src_stride_b, long src_stride_l,
+                                                                  const int* __restrict__ frame_idx,
+                                                                  const float* __restrict__ mean,
+                                                                  const float* __restrict__ stdv,
+                                                                  const float* __restrict__ boxes,
+                                                                  const int* __restrict__ labels, int N,
+                                                                  const unsigned char* __restrict__ palette, int P,
+                                                                  int t) {
+  __shared__ int4 s_edge[RB_MAX_BOXES];      // (Lf, Tp, Rt, Bt)
+  __shared__ unsigned s_colour[RB_MAX_BOXES];
+  __shared__ int s_count[RB_WAVES];
+  const int b = blockIdx.z;
+  const int tx0 = blockIdx.x * RB_TILE_W, ty0 = blockIdx.y * RB_TILE_H;
+  const int lane = threadIdx.x & 63, wave = uniform((int)threadIdx.x >> 6);
+
+  // ---- stage the sample's boxes: index order is kept, so the scan below sees the painter's order
+  int staged = 0;                            // the same in every thread
+  const float lo = (float)t, hx = (float)(W - t), hy = (float)(H - t);
+  for (int base = 0; base < N; base += RB_THREADS) {
+    const int i = base + (int)threadIdx.x;
+    bool keep = false;
+    int4 e = make_int4(0, 0, 0, 0);
+    unsigned colour = 0;
+    if (i < N) {
+      const int label = labels[(long)b * N + i];
+      const float* q = boxes + ((long)b * N + i) * 4;
+      const float x1 = q[0], y1 = q[1], x2 = q[2], y2 = q[3];
+      if (label >= 0 && label < P && x1 == x1 && y1 == y1 && x2 == x2 && y2 == y2) {
+        e.x = (int)fminf(fmaxf(x1, lo), hx);
+        e.y = (int)fminf(fmaxf(y1, lo), hy);
+        e.z = (int)fminf(fmaxf(x2, lo), hx);
+        e.w = (int)fminf(fmaxf(y2, lo), hy);
+        const unsigned char* c = palette + 3 * label;
+        colour = (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16);
+        keep = true;
+#if RB_CULL
+        // the bars lie inside [min - t, max + t) of the two edges in each direction (a reversed box has max < min of
+        // the plain order: its remaining bars still lie in this range)
+        keep = min(e.x, e.z) - t < tx0 + RB_TILE_W && max(e.x, e.z) + t > tx0 &&
+               min(e.y, e.w) - t < ty0 + RB_TILE_H && max(e.y, e.w) + t > ty0;
+#endif
+      }
+    }
+    const unsigned long long votes = __ballot(keep);
+    if (lane == 0) s_count[wave] = __popcll(votes);
+    __syncthreads();
+    int at = staged, total = 0;
+#pragma unroll
+    for (int w = 0; w < RB_WAVES; ++w) {
+      if (w < wave) at += s_count[w];
+      total += s_count[w];
+    }
+    if (keep) {
+      at += __popcll(votes & ((1ull << lane) - 1ull));
+      s_edge[at] = e;
+      s_colour[at] = colour;
+    }
+    staged += total;
+    __syncthreads();                         // the counts are rewritten next round; after the last, the stage is whole
+  }
+
+  // ---- the picture
+  int f = frame_idx ? frame_idx[b] : 0;
+  if (f < 0) f += L;
+  f = min(max(f, 0), L - 1);
+  const T* frame = src + (long)b * src_stride_b + (long)f * src_stride_l;
+  const long hw = (long)H * W;
+  float m[3] = {0.f, 0.f, 0.f}, sd[3] = {1.f, 1.f, 1.f};
+  if (mean && stdv) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      m[c] = mean[c];
+      sd[c] = stdv[c];
+    }
+  }
+  const int x = tx0 + 4 * lane;
+  if (x >= W) return;                        // (after the last barrier)
+  for (int y = ty0 + wave; y < min(ty0 + RB_TILE_H, H); y += RB_WAVES) {
+    const T* p = frame + (long)y * W + x;
+    unsigned char* o = dst + (((long)b * H + y) * W + x) * 3;
+    const bool whole = x + 3 < W;
+    const bool aligned = whole && (((uintptr_t)p | (uintptr_t)(p + hw) | (uintptr_t)(p + 2 * hw)) % Quad<T>::ALIGN) == 0;
+    Quad<T> q[3] = {};
+    if (aligned) {                           // issued before the scan: the loads fly while the boxes are tested
+#pragma unroll
+      for (int c = 0; c < 3; ++c) q[c].load(p + c * hw);
+    }
+    unsigned px[4] = {0u, 0u, 0u, 0u};
+    unsigned done = whole ? 0u : (0xFu << (W - x)) & 0xFu;  // bit j: pixel x + j has its colour (or lies past the row)
+    // y, k and what s_edge[k] holds are the same in every lane of the wave: the row tests and the bars' extents are
+    // scalar work (readfirstlane says so to the compiler), a lane only places its four pixels in a bar's columns
+    for (int k = staged - 1; k >= 0; --k) {
+      if (__ballot(done != 0xFu) == 0) break;               // every pixel of the wave's row has met its topmost box
+      const int4 e = s_edge[k];
+      const int lf = uniform(e.x), tp = uniform(e.y), rt = uniform(e.z), bt = uniform(e.w);
+      const bool left = y >= tp - t && y < bt, bottom = y >= bt && y < bt + t;
+      const bool right = y >= tp && y < bt + t, top = y >= tp - t && y < tp;
+      if (!(left || bottom || right || top)) continue;
+      unsigned hit = 0u;
+      if (left) hit |= columns(x, lf - t, lf);
+      if (bottom) hit |= columns(x, lf - t, rt);
+      if (right) hit |= columns(x, rt, rt + t);
+      if (top) hit |= columns(x, lf, rt + t);
+      const unsigned fresh = hit & ~done;
+      const unsigned colour = (unsigned)uniform((int)s_colour[k]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) px[j] = (fresh >> j & 1u) ? colour : px[j];
+      done |= hit;
+    }
+    const unsigned painted = done;
+    if (aligned) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (!(painted >> j & 1u))
+          px[j] = to_byte(q[0].at(j), sd[0], m[0]) | (to_byte(q[1].at(j), sd[1], m[1]) << 8) |
+                  (to_byte(q[2].at(j), sd[2], m[2]) << 16);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (x + j < W && !(painted >> j & 1u))
+          px[j] = to_byte(p[j], sd[0], m[0]) | (to_byte(p[hw + j], sd[1], m[1]) << 8) |
+                  (to_byte(p[2 * hw + j], sd[2], m[2]) << 16);
+    }
+    if (whole && ((uintptr_t)o & 3u) == 0) {
+      unsigned* o4 = reinterpret_cast<unsigned*>(o);         // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+      o4[0] = px[0] | (px[1] << 24);
+      o4[1] = (px[1] >> 8) | (px[2] << 16);
+      o4[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (x + j < W) {
+          o[3 * j] = (unsigned char)px[j];
+          o[3 * j + 1] = (unsigned char)(px[j] >> 8);
+          o[3 * j + 2] = (unsigned char)(px[j] >> 16);
+        }
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int fod_render_boxes(const void* src, int src_is_u8, unsigned char* dst, int B, int L, int H, int W,
+                                long src_stride_b, long src_stride_l, const int* frame_idx, const float* mean,
+                                const float* stdv, const float* boxes, const int* labels, int N,
+                                const unsigned char* palette, int P, int thickness, hipStream_t stream) {
+  FOD_REQUIRE(thickness >= 1, "render_boxes: thickness %d is below 1", thickness);
+  FOD_REQUIRE(N >= 0 && N <= RB_MAX_BOXES, "render_boxes: %d boxes per sample, not 0..%d", N, RB_MAX_BOXES);
+  FOD_REQUIRE(P >= 1, "render_boxes: a palette of %d colours", P);
+  FOD_REQUIRE(H > 0 && W > 0 && (long)H >= 2L * thickness && (long)W >= 2L * thickness,
+              "render_boxes: a %dx%d frame does not hold bars of thickness %d", H, W, thickness);
+  FOD_REQUIRE((long)3 * H * W <= INT_MAX, "render_boxes: frame %dx%d is too large", H, W);
+  FOD_REQUIRE(B > 0 && B <= 65535 && L > 0, "render_boxes: bad clip extent %dx%d", B, L);
+  FOD_REQUIRE(src_stride_l >= (long)3 * H * W && src_stride_b >= (long)3 * H * W,
+              "render_boxes: frame strides %ld / %ld overlap the 3x%dx%d planes", src_stride_b, src_stride_l, H, W);
+  FOD_REQUIRE(src_is_u8 || (mean && stdv), "render_boxes: an f32 source needs mean and std (null pointer)");
+  FOD_REQUIRE(src && dst && (N == 0 || (boxes && labels && palette)), "render_boxes: null pointer");
+  const dim3 grid((W + RB_TILE_W - 1) / RB_TILE_W, (H + RB_TILE_H - 1) / RB_TILE_H, B);
+  FOD_REQUIRE(grid.y <= 65535, "render_boxes: frame %dx%d is too tall", H, W);
+  if (src_is_u8)
+    hipLaunchKernelGGL(render_boxes_kernel<unsigned char>, grid, dim3(RB_THREADS), 0, stream,
+                       (const unsigned char*)src, dst, L, H, W, src_stride_b, src_stride_l, frame_idx, mean, stdv, boxes,
+                       labels, N, palette, P, thickness);
+  else
+    hipLaunchKernelGGL(render_boxes_kernel<float>, grid, dim3(RB_THREADS), 0, stream, (const float*)src, dst, L, H, W,
+                       src_stride_b, src_stride_l, frame_idx, mean, stdv, boxes, labels, N, palette, P, thickness);
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}

@@ -454,6 +454,58 @@ def clip_crop_resize_photo(video_u8, plans, size, mean, std, photo):
     return _clip_crop_resize("clip_crop_resize_photo", video_u8, plans, size, mean, std, photo)
 
 
+def render_boxes(video, boxes, labels, *, frame_idx=None, mean=None, std=None, palette, thickness=3, out=None):
+    """One frame per sample of a clip as uint8 RGB [B, H, W, 3] with box outlines painted on it, in one launch
+    (include/fod_ext.h, fod_render_boxes, states the map).  video [B, L, 3, H, W]: f32 normalised with `mean` / `std`
+    (f32 [3] each) or raw uint8; boxes f32 [B, N, 4] xyxy pixels, labels i32 [B, N] (drawn where 0 <= label < P, no
+    coordinate NaN; later boxes cover earlier ones), palette uint8 [P, 3], frame_idx i32 [B] or None for frame 0 --
+    all on the clip's device.  `out`: a contiguous uint8 [B, H, W, 3] to write into.  There is no CPU fallback."""
+    who = "render_boxes"
+    if not isinstance(video, torch.Tensor) or not video.is_cuda or video.dim() != 5 or video.shape[2] != 3 \
+            or video.dtype not in (torch.float32, torch.uint8):
+        raise L.FodError(f"{who}: video must be an f32 or uint8 device tensor [B, L, 3, H, W] "
+                         "(the HIP path has no CPU fallback)")
+    b, l, _, h, w = video.shape
+    sb, sl, sc, sh, sw = video.stride()
+    if b == 1:
+        sb = 3 * h * w                       # (the stride of an extent of one is never walked, and torch keeps any)
+    if l == 1:
+        sl = 3 * h * w
+    if (sc, sh, sw) != (h * w, w, 1) or min(sb, sl) < 3 * h * w:
+        raise L.FodError(f"{who}: frame planes must be contiguous, got strides {video.stride()}")
+    u8 = video.dtype == torch.uint8
+    operands = {"boxes": (boxes, torch.float32), "labels": (labels, torch.int32), "palette": (palette, torch.uint8)}
+    if not u8:
+        operands.update(mean=(mean, torch.float32), std=(std, torch.float32))
+    if frame_idx is not None:
+        operands["frame_idx"] = (frame_idx, torch.int32)
+    if out is not None:
+        operands["out"] = (out, torch.uint8)
+    for name, (t, dtype) in operands.items():
+        if not isinstance(t, torch.Tensor):
+            raise L.FodError(f"{who}: {name} must be a {dtype} device tensor")
+        _chk(t, f"{who}: {name}", dtype)
+        if t.device != video.device:
+            raise L.FodError(f"{who}: {name} lives on {t.device}, the clip on {video.device}")
+    if boxes.dim() != 3 or boxes.shape[0] != b or boxes.shape[2] != 4 or tuple(labels.shape) != tuple(boxes.shape[:2]):
+        raise L.FodError(f"{who}: boxes {tuple(boxes.shape)} / labels {tuple(labels.shape)} are not [B, N, 4] / [B, N] "
+                         f"for a clip of {b}")
+    if palette.dim() != 2 or palette.shape[1] != 3 or palette.shape[0] < 1:
+        raise L.FodError(f"{who}: palette {tuple(palette.shape)} is not [P, 3]")
+    if not u8 and (mean.numel() != 3 or std.numel() != 3):
+        raise L.FodError(f"{who}: mean {mean.numel()} / std {std.numel()} do not fit three planes")
+    if frame_idx is not None and tuple(frame_idx.shape) != (b,):
+        raise L.FodError(f"{who}: frame_idx {tuple(frame_idx.shape)} is not one index per sample of {b}")
+    if out is None:
+        out = torch.empty((b, h, w, 3), dtype=torch.uint8, device=video.device)
+    elif tuple(out.shape) != (b, h, w, 3):
+        raise L.FodError(f"{who}: out {tuple(out.shape)} is not [{b}, {h}, {w}, 3]")
+    call("fod_render_boxes", ptr(video), int(u8), ptr(out), b, l, h, w, sb, sl, ptr(frame_idx),
+         None if u8 else ptr(mean), None if u8 else ptr(std), ptr(boxes), ptr(labels), boxes.shape[1], ptr(palette),
+         palette.shape[0], int(thickness), stream())
+    return out
+
+
 def conv_stem_fwd(xp, w, h, wd, *, shift=None, relu=True):
     """xp: haloed layout of an [*, 3, h, wd] clip; w [Cout, 7, 8, 4] -> y NHWC [F, Ho, Wo, Cout]."""
     _chk(xp, "xp"); _chk(w, "w", xp.dtype)

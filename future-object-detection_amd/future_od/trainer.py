@@ -1,6 +1,7 @@
 """Training / evaluation loop with the reference Trainer's constructor, checkpoint format and printed
-metrics (reference future_od/trainer.py), driving the HIP-backed model.  wandb and the PNG
-visualisation are optional imports: absent packages disable those features instead of failing."""
+metrics (reference future_od/trainer.py), driving the HIP-backed model.  wandb is an optional import: without the
+package its logging is off.  The PNG visualisation (visualize_batch) is rendered on the device by one HIP launch per
+picture set (future_od/utils/visualization.py) and needs no package."""
 import contextlib
 import os
 
@@ -288,6 +289,10 @@ class Trainer:
                         torch.nn.utils.clip_grad_norm_(self._model.parameters(), self._max_norm)
                     self._optimizer.step()
                 self._training_iterations += 1
+            if i in self._visualization_iterations and self._epoch in self._visualization_epochs and self._is_master:
+                # on the step's own stream, right behind it: a captured step's outputs live in buffers that the next
+                # replay overwrites
+                self.visualize_batch(data, out, mode, self._wandb_config.enabled and wandb is not None)
             if self._distributed:
                 stats = reduce_distrib_loss(stats, average=True)
             keys = list(stats.keys())
@@ -327,6 +332,62 @@ class Trainer:
         print("MAP for medium objects is:", fmt(ap["threshavg"][:, 2]))
         print("MAP for large objects is:", fmt(ap["threshavg"][:, 3]))
         self.last_ap = ap
+
+    # ------------------------------------------------------------------ visualisation (reference :334-413)
+    @torch.no_grad()
+    def visualize_batch(self, data, model_output, mode, log_to_wandb, prefix=""):
+        """Two PNG files per sample b of the batch, of its annotated frame (`annotated_frame_idx`), in
+        `visualization_path`: `{prefix}{mode}_b{b}_anno.png` with the active annotations (the reference's file), and
+        `{prefix}{mode}_b{b}_pred.png` with the annotations first and on top of them the last decoder level's
+        predictions for that frame whose best class scores at least 0.5.  Each set is ONE launch for the whole batch
+        (visualization.render); only the two uint8 pictures per sample cross to the host, the clip stays where it is.
+        With `log_to_wandb` (and the package) the first `wandb_config.num_images` samples are also logged as
+        wandb.Image with their box dictionaries, under the reference's key."""
+        from future_od.utils import visualization as V
+        scores, pred_boxes = model_output["class_scores"][:, :, -1], model_output["boxes"][:, :, -1]   # [B, Lo, M, C / 4]
+        B, L_out, M, C = scores.shape
+        video = data["video"]
+        L_in = video.shape[1]
+        assert L_in == L_out or L_out == 1
+        dev = video.device
+        frame = data["annotated_frame_idx"].to(dev)
+        if L_out == L_in:                                    # a detection set per frame: the annotated frame's
+            at = torch.where(frame < 0, frame + L_in, frame).clamp(0, L_in - 1)
+            scores, pred_boxes = scores[torch.arange(B, device=dev), at], pred_boxes[torch.arange(B, device=dev), at]
+        else:                                                # one set: it is the annotated frame's
+            scores, pred_boxes = scores[:, 0], pred_boxes[:, 0]
+        anno_classes = data["classes"].to(dev).masked_fill(data["active"].to(dev) == 0, -1)
+        anno_boxes = data["boxes"].to(dev).float()
+        best, pred_classes = scores.float().max(dim=2)
+        pred_classes = pred_classes.masked_fill(best < 0.5, -1)
+        pred_boxes = all_pred_boxes = pred_boxes.float()
+        room = 1024 - anno_boxes.shape[1]                    # the renderer takes 1024 boxes per sample
+        if M > room:                                         # more queries than that: the best-scoring ones
+            keep = best.topk(room, dim=1).indices.sort(dim=1).values
+            pred_classes, pred_boxes = pred_classes.gather(1, keep), pred_boxes.gather(1, keep[..., None].expand(-1, -1, 4))
+        anno = V.render(video, anno_boxes, anno_classes, frame)
+        pred = V.render(video, torch.cat([anno_boxes, pred_boxes], dim=1), torch.cat([anno_classes, pred_classes], dim=1),
+                        frame)
+        anno, pred = anno.cpu(), pred.cpu()
+        for b in range(B):
+            for kind, picture in (("anno", anno[b]), ("pred", pred[b])):
+                fpath = os.path.join(self._visualization_path, f"{prefix}{mode}_b{b}_{kind}.png")
+                print("Storing visualization at", fpath)
+                V.write_png(picture, fpath)
+        if not (log_to_wandb and wandb is not None):
+            return
+        images = []
+        moods = model_output.get("moods")
+        at = torch.where(frame < 0, frame + L_in, frame).clamp(0, L_in - 1).tolist()
+        for b in range(min(B, self._wandb_config.num_images)):
+            images.append(V.visualize_wandb(
+                image=video[b, at[b]].cpu(), background_class=C, category_dict=self._category_dict,
+                pred_scores=scores[b].float().cpu(), pred_boxes=all_pred_boxes[b].cpu(),
+                anno_classes=data["classes"][b].cpu().masked_fill(data["active"][b].cpu() == 0, C),
+                anno_boxes=anno_boxes[b].cpu(), ignore_boxes=data["ignore_boxes"][b].cpu(),
+                model_mood=moods[b][at[b]] if moods is not None else None))
+        if images:
+            wandb.log({f"visualization/{prefix}{mode}_bounding_boxes": images, "epoch": self._epoch})
 
     # ------------------------------------------------------------------ checkpoints (reference :282-328)
     def save_checkpoint(self, is_final: bool = False):

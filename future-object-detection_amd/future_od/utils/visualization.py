@@ -1,0 +1,209 @@
+"""Looking at frames and boxes (reference future_od/utils/visualization.py, same names): the annotated frame of each
+sample as an 8-bit RGB picture with box outlines, written as PNG.
+
+The reference copies the whole normalised f32 clip to the host, draws with a Python loop over boxes and encodes with
+torchvision.  Here a clip that lives on the GPU is rendered there by one launch (`render` -> ops.render_boxes,
+include/fod_ext.h: fod_render_boxes) and only the finished uint8 picture crosses to the host; the PNG is written with
+zlib and struct.  `draw_boxes` is the per-sample CPU form and the definition of the kernel's map, the way
+datasets.transforms.photometric is for the photometric kernel; `render` on CPU tensors is built on it and gives the
+kernel's bytes.
+
+Not built: text or captions in the picture, filled or alpha-blended boxes, a thickness per box, bf16 sources, PNG
+compression tuning, drawing every frame of a clip to disk."""
+import os
+import struct
+import zlib
+
+import torch
+
+_LEVELS = (0.0, 0.25, 0.5, 0.75, 1.0)
+# f32 [125, 3]: entry a*25 + b*5 + c is (lv[c], lv[b], lv[a]) -- red runs fastest
+COLOURS = torch.tensor([[_LEVELS[c], _LEVELS[b], _LEVELS[a]] for a in range(5) for b in range(5) for c in range(5)],
+                       dtype=torch.float32)
+PIXEL_MEAN, PIXEL_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)        # ImageNet's, as the loaders normalise
+
+
+def revert_imagenet_normalization(sample):
+    """sample [..., 3, H, W], normalised -> 0..1 scale: sample * std + mean (product and sum each rounded to f32)."""
+    mean = torch.tensor(PIXEL_MEAN, dtype=torch.float32, device=sample.device).view(3, 1, 1)
+    std = torch.tensor(PIXEL_STD, dtype=torch.float32, device=sample.device).view(3, 1, 1)
+    return sample * std + mean
+
+
+def to_bytes(values):
+    """Float values on the 0..1 scale -> uint8: v * 255 truncated towards zero and clamped to 0..255; a product that is
+    not finite gives 0.  (The reference's `.byte()` of an out-of-range float is undefined.)"""
+    w = values * 255
+    w = torch.where(torch.isfinite(w), w, torch.zeros_like(w))
+    return w.clamp(0, 255).to(torch.uint8)
+
+
+def draw_boxes(image, boxes, colours, thickness=3):
+    """Outlines of `boxes` f32 [N, 4] (xyxy pixels) in `colours` [N, 3] on the float image [3, H, W], in place and
+    returned.  A painter's loop: later boxes cover earlier ones.  With t = thickness, in f32 and then truncated:
+        Lf = trunc(min(max(x1, t), W - t))   Rt = trunc(min(max(x2, t), W - t))
+        Tp = trunc(min(max(y1, t), H - t))   Bt = trunc(min(max(y2, t), H - t))
+    and four bars, rows x columns:
+        left    [Tp - t, Bt)     x [Lf - t, Lf)        bottom  [Bt, Bt + t)     x [Lf - t, Rt)
+        right   [Tp, Bt + t)     x [Rt, Rt + t)        top     [Tp - t, Tp)     x [Lf, Rt + t)
+    An empty range holds nothing, so a reversed or collapsed box draws the bars that remain; the clamps keep every bar
+    inside the image.  A box with a NaN coordinate is skipped (the reference raises on it)."""
+    _, H, W = image.shape
+    t = int(thickness)
+    if t < 1 or H < 2 * t or W < 2 * t:
+        raise ValueError(f"draw_boxes: a {H}x{W} image does not hold bars of thickness {thickness}")
+    boxes = boxes.detach().to(torch.float32)
+    for n in range(boxes.shape[0]):
+        if bool(torch.isnan(boxes[n]).any()):
+            continue
+        Lf = int(boxes[n, 0].clamp(t, W - t))
+        Tp = int(boxes[n, 1].clamp(t, H - t))
+        Rt = int(boxes[n, 2].clamp(t, W - t))
+        Bt = int(boxes[n, 3].clamp(t, H - t))
+        colour = colours[n].to(image.dtype).view(3, 1, 1)
+        image[:, Tp - t:Bt, Lf - t:Lf] = colour
+        image[:, Bt:Bt + t, Lf - t:Rt] = colour
+        image[:, Tp:Bt + t, Rt:Rt + t] = colour
+        image[:, Tp - t:Tp, Lf:Rt + t] = colour
+    return image
+
+
+_DEVICE_CONSTANTS = {}
+
+
+def _device_constants(device):
+    """(COLOURS as bytes, mean, std) on `device`, made once."""
+    hit = _DEVICE_CONSTANTS.get(device)
+    if hit is None:
+        hit = _DEVICE_CONSTANTS[device] = (to_bytes(COLOURS).to(device),
+                                           torch.tensor(PIXEL_MEAN, dtype=torch.float32, device=device),
+                                           torch.tensor(PIXEL_STD, dtype=torch.float32, device=device))
+    return hit
+
+
+def render(video, boxes, labels, frame_idx=None, thickness=3, palette=COLOURS):
+    """The frame `frame_idx[b]` (None: frame 0; negative: from the end; clamped into the clip) of every sample of
+    `video` [B, L, 3, H, W] -- f32 normalised, or raw uint8 -- with the outlines of `boxes` [B, N, 4] (xyxy pixels)
+    -> uint8 [B, H, W, 3] on the clip's device.  Box n is drawn where 0 <= labels[b, n] < len(palette) (and no
+    coordinate is NaN) in the colour palette[label]; `palette` is float [P, 3] on the 0..1 scale and becomes bytes by
+    `to_bytes` (COLOURS: 0, 63, 127, 191, 255).  `labels` may be i64.  A device clip is one launch of ops.render_boxes;
+    CPU tensors go through `draw_boxes` per sample and give the same bytes."""
+    if video.dim() != 5 or video.shape[2] != 3 or video.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"render: video must be f32 or uint8 [B, L, 3, H, W], got {video.dtype} {tuple(video.shape)}")
+    B, L = video.shape[:2]
+    if video.is_cuda:
+        from future_od.native import ops
+        colours, mean, std = _device_constants(video.device)
+        if palette is not COLOURS:
+            colours = to_bytes(palette.to(video.device, torch.float32)).contiguous()
+        if frame_idx is not None:
+            frame_idx = frame_idx.to(video.device, torch.int32).contiguous()
+        return ops.render_boxes(video, boxes.to(video.device, torch.float32).contiguous(),
+                                labels.to(video.device, torch.int32).contiguous(), frame_idx=frame_idx, mean=mean,
+                                std=std, palette=colours, thickness=thickness)
+    u8 = video.dtype == torch.uint8
+    palette = palette.to(torch.float32)
+    colours = to_bytes(palette).to(torch.float32) if u8 else palette
+    out = []
+    for b in range(B):
+        f = 0 if frame_idx is None else int(frame_idx[b])
+        f = min(max(f + L if f < 0 else f, 0), L - 1)
+        keep = (labels[b] >= 0) & (labels[b] < palette.shape[0])
+        image = video[b, f].to(torch.float32) if u8 else revert_imagenet_normalization(video[b, f])
+        image = draw_boxes(image, boxes[b][keep], colours[labels[b][keep].long()], thickness)
+        out.append((image.to(torch.uint8) if u8 else to_bytes(image)).permute(1, 2, 0))
+    return torch.stack(out).contiguous()
+
+
+def render_detections(video, det, min_score=0.5, frame_idx=None, thickness=3, palette=COLOURS):
+    """`render` of what `predict()` returns ({"scores" [B, K], "labels" [B, K], "boxes" [B, K, 4], "count" [B]}): the
+    slots that hold a detection (index < count) with a score of at least `min_score`.  A few tiny torch ops on the
+    tensors' device, no read-back."""
+    scores, labels = det["scores"], det["labels"]
+    slot = torch.arange(labels.shape[1], device=labels.device)
+    hidden = (scores < min_score) | (slot[None, :] >= det["count"][:, None])
+    return render(video, det["boxes"], labels.masked_fill(hidden, -1), frame_idx, thickness, palette)
+
+
+def _chunk(kind, body):
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+
+
+def write_png(img_hwc_uint8, path):
+    """uint8 [H, W, 3] -> an 8-bit RGB PNG: non-interlaced, filter 0 on every line, one IDAT.  Creates the directory."""
+    img = img_hwc_uint8.detach().cpu() if isinstance(img_hwc_uint8, torch.Tensor) else torch.as_tensor(img_hwc_uint8)
+    if img.dim() != 3 or img.shape[2] != 3 or img.dtype != torch.uint8:
+        raise ValueError(f"write_png: uint8 [H, W, 3], got {img.dtype} {tuple(img.shape)}")
+    H, W, _ = img.shape
+    lines = torch.cat([torch.zeros(H, 1, dtype=torch.uint8), img.reshape(H, 3 * W)], dim=1)    # the filter byte first
+    data = (b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+            + _chunk(b"IDAT", zlib.compress(lines.contiguous().numpy().tobytes())) + _chunk(b"IEND", b""))
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
+def visualize(image, classes, boxes, fpath, BACKGROUND_CLASS):
+    """image [3, H, W] normalised; classes float [M, C] (scores: best class, background below 0.5) or integer [M];
+    boxes [M, 4] xyxy pixels or None.  Writes the picture to `fpath` and returns it, uint8 [H, W, 3] on the image's
+    device."""
+    print("Storing visualization at", fpath)
+    if boxes is None:
+        boxes, classes = image.new_zeros((0, 4), dtype=torch.float32), torch.zeros(0, dtype=torch.int64)
+    elif classes.is_floating_point():
+        scores, classes = classes.max(dim=1)
+        classes = classes.masked_fill(scores < 0.5, BACKGROUND_CLASS)
+    classes = classes.to(boxes.device)
+    keep = classes != BACKGROUND_CLASS
+    picture = render(image[None, None], boxes[keep][None], classes[keep][None])[0]
+    write_png(picture, fpath)
+    return picture
+
+
+def _pixel_box(box, class_id):
+    x1, y1, x2, y2 = (int(v) for v in box.round())
+    return {"position": {"minX": x1, "maxX": x2, "minY": y1, "maxY": y2}, "domain": "pixel", "class_id": class_id}
+
+
+def wandb_box_data(background_class, category_dict, pred_scores=None, pred_boxes=None, anno_classes=None,
+                   anno_boxes=None, ignore_boxes=None):
+    """The `boxes` argument of a wandb.Image, as the reference's visualize_wandb builds it: "predictions" (best class of
+    pred_scores [M, C] where its score is above 0.1, captioned "<index> <category>"), "ground_truth" (anno_classes [N]
+    other than the background class) and "ignore_regions"; positions are rounded pixel integers.  A pure function of
+    host or device tensors; nothing of wandb is touched."""
+    host = lambda t: t.detach().cpu().numpy()
+    out = {}
+    if pred_boxes is not None:
+        scores, classes = pred_scores.max(dim=1)
+        data = []
+        for idx, (score, cls, box) in enumerate(zip(host(scores), host(classes), host(pred_boxes))):
+            if score > 0.1:
+                data.append({**_pixel_box(box, int(cls)), "scores": {"score": float(score)},
+                             "box_caption": f"{idx} {category_dict[int(cls)]}"})
+        out["predictions"] = {"box_data": data, "class_labels": category_dict}
+    if anno_classes is not None:
+        out["ground_truth"] = {"box_data": [_pixel_box(box, int(cls)) for cls, box in zip(host(anno_classes), host(anno_boxes))
+                                            if cls != background_class],
+                               "class_labels": category_dict}
+    if ignore_boxes is not None:
+        out["ignore_regions"] = {"box_data": [_pixel_box(box, 0) for box in host(ignore_boxes)],
+                                 "class_labels": {0: "Ignore"}}
+    return out
+
+
+def visualize_wandb(image, background_class, category_dict, pred_scores=None, pred_boxes=None, anno_classes=None,
+                    anno_boxes=None, ignore_boxes=None, model_mood=None):
+    """wandb.Image of the frame [3, H, W] (normalised float, or raw uint8) on the 0..1 scale with `wandb_box_data`'s
+    boxes; RuntimeError without wandb."""
+    try:
+        import wandb
+    except ImportError:
+        raise RuntimeError("visualize_wandb: the wandb package is not installed; `visualize` writes PNG files "
+                           "without it") from None
+    boxes = wandb_box_data(background_class, category_dict, pred_scores, pred_boxes, anno_classes, anno_boxes,
+                           ignore_boxes)
+    image = image.detach()
+    picture = image.float() / 255 if image.dtype == torch.uint8 else revert_imagenet_normalization(image.float())
+    picture = picture.cpu().numpy().transpose(1, 2, 0)
+    return wandb.Image(picture, boxes=boxes, caption=model_mood)

@@ -79,6 +79,40 @@ int fod_multi_accum(const long* pairs, const long* numel, const int* blk_tensor,
 int fod_clip_crop_resize_photo(const unsigned char* src, float* dst, int B, int L, int C, int H0, int W0, int H, int W,
                                long src_stride_b, long src_stride_l, const int* plans, const float* mean,
                                const float* std, const float* photo, fod_stream_t stream);
+/* Visualisation: one frame of each sample of a clip as an 8-bit RGB picture with box outlines painted on it, in ONE
+ * launch (the reference's revert_imagenet_normalization + draw_boxes + `* 255` + `.byte()`, which it runs on the host
+ * after copying the whole f32 clip there).  future_od/utils/visualization.py (draw_boxes, render) is the CPU form.
+ *   src: [B][L][3][H][W], planar and dense inside a frame, src_stride_b / src_stride_l in ELEMENTS (each at least
+ *        3*H*W); src_is_u8 == 0: f32, normalised with mean / std (DEVICE f32 [3] each); != 0: raw uint8 (mean / std are
+ *        not read and may be NULL).
+ *   frame_idx: DEVICE i32 [B], the frame of each sample, or NULL for frame 0.  A negative value counts from the end
+ *        (-1 is L - 1); after that step the value is clamped into [0, L).
+ *   dst: uint8 [B][H][W][3], interleaved RGB (a PNG scanline).
+ * Background pixel, per channel c.  f32:  v = x * std[c] + mean[c],  w = v * 255 -- the product, the sum and the second
+ * product each rounded to f32, no fused multiply-add, as in fod_multi_ema -- then w truncated towards zero and clamped
+ * to 0..255; a w that is not finite (NaN, +-inf) gives 0.  uint8: the byte is copied.  (The reference's `.byte()` of an
+ * out-of-range float is undefined; this clamps.)
+ * Boxes: boxes f32 [B][N][4], xyxy in pixels of the frame; labels i32 [B][N]; palette DEVICE uint8 [P][3].  Box n of a
+ * sample is DRAWN iff 0 <= label < P and none of its four coordinates is NaN; its colour is palette[label].  With
+ * t = thickness, all in f32 and then truncated to int:
+ *   Lf = trunc(min(max(x1, t), W - t))   Rt = trunc(min(max(x2, t), W - t))
+ *   Tp = trunc(min(max(y1, t), H - t))   Bt = trunc(min(max(y2, t), H - t))
+ * and pixel (y, x) lies on the box's outline iff it lies in one of four bars:
+ *   left:    Tp - t <= y < Bt       and  Lf - t <= x < Lf
+ *   bottom:  Bt     <= y < Bt + t   and  Lf - t <= x < Rt
+ *   right:   Tp     <= y < Bt + t   and  Rt     <= x < Rt + t
+ *   top:     Tp - t <= y < Tp       and  Lf     <= x < Rt + t
+ * An empty range holds nothing: a reversed or collapsed box draws the bars that remain (what slicing does in the
+ * reference); the clamps keep every bar inside the picture; +-inf clamps like any other value.  A pixel takes the colour
+ * of the HIGHEST-index drawn box whose outline holds it (the painter's order: later boxes cover earlier ones), else its
+ * background.  N == 0 converts only (boxes, labels and palette may then be NULL).
+ * FOD_ERR_ARG before any launch: thickness < 1; H or W below 2 * thickness; N < 0 or N > 1024 (the matcher's query
+ * limit); P < 1; an f32 source without mean or std; a NULL src or dst; strides below 3*H*W; B outside 1..65535.
+ * Reads 12 B (f32) or 3 B (uint8) and writes 3 B per pixel; 16-byte loads and dword stores where a row's addresses
+ * allow, element by element otherwise (no alignment is required of any pointer). */
+int fod_render_boxes(const void* src, int src_is_u8, unsigned char* dst, int B, int L, int H, int W, long src_stride_b,
+                     long src_stride_l, const int* frame_idx, const float* mean, const float* std, const float* boxes,
+                     const int* labels, int N, const unsigned char* palette, int P, int thickness, fod_stream_t stream);
 
 #ifdef __cplusplus
 }
