@@ -212,6 +212,130 @@ __global__ __launch_bounds__(RB_THREADS) void render_boxes_kernel(const T* __res
   }
 }
 
+// ---- attention overlay (fod_render_attention): the maps of one detection per sample blended over their past frames.
+// One launch for all B x J pictures; a thread produces four consecutive pixels of a row, as above.  The small map is
+// sampled bilinearly from global memory (a 29x50 map is 5.8 KB: cache hits), the colour table is staged in LDS.
+
+struct Tap {                                 // the two source rows (columns) of a destination row (column) and their weights
+  int i0, i1;
+  float w0, w1;
+};
+// F.interpolate's bilinear source coordinate with align_corners=False, every step one f32 operation
+FOD_DEVINL Tap tap(int d, float ratio, int n) {
+#pragma clang fp contract(off)
+  float f = (float)d + 0.5f;
+  f = f * ratio;
+  f = f - 0.5f;
+  f = fmaxf(f, 0.f);
+  Tap t;
+  t.i0 = min((int)f, n - 1);
+  t.i1 = min(t.i0 + 1, n - 1);
+  t.w1 = f - (float)t.i0;
+  t.w0 = 1.f - t.w1;
+  return t;
+}
+
+// background byte bg under the map sample a -> the blended byte of one channel; colour is the table's byte
+FOD_DEVINL unsigned blend(unsigned bg, unsigned colour, float alpha) {
+#pragma clang fp contract(off)
+  const float keep = 1.f - alpha;
+  const float u = (float)bg * keep;
+  const float v = (float)colour * alpha;
+  const float w = u + v;
+  return (unsigned)fminf(fmaxf(w, 0.f), 255.f);
+}
+
+template <typename T>
+__global__ __launch_bounds__(RB_THREADS) void render_attention_kernel(
+    const T* __restrict__ src, unsigned char* __restrict__ dst, int L, int J, int H, int W, long src_stride_b,
+    long src_stride_l, const int* __restrict__ frame_idx, const float* __restrict__ mean, const float* __restrict__ stdv,
+    const float* __restrict__ maps, int h, int w, long map_stride_b, long map_stride_j,
+    const float* __restrict__ colour_scale, const unsigned char* __restrict__ lut, float gain, float max_alpha) {
+#pragma clang fp contract(off)
+  __shared__ unsigned s_lut[256];
+  {
+    const unsigned char* c = lut + 3 * threadIdx.x;          // RB_THREADS == 256 entries
+    s_lut[threadIdx.x] = (unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16);
+  }
+  __syncthreads();
+  const int b = blockIdx.z / J, j = blockIdx.z - b * J;
+  const int tx0 = blockIdx.x * RB_TILE_W, ty0 = blockIdx.y * RB_TILE_H;
+  const int lane = threadIdx.x & 63, wave = uniform((int)threadIdx.x >> 6);
+  int f = frame_idx[b * J + j];
+  if (f < 0) f += L;
+  f = min(max(f, 0), L - 1);
+  const T* frame = src + (long)b * src_stride_b + (long)f * src_stride_l;
+  const float* map = maps + (long)b * map_stride_b + (long)j * map_stride_j;
+  const float cs = colour_scale[b * J + j];
+  const long hw = (long)H * W;
+  float m[3] = {0.f, 0.f, 0.f}, sd[3] = {1.f, 1.f, 1.f};
+  if (mean && stdv) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      m[c] = mean[c];
+      sd[c] = stdv[c];
+    }
+  }
+  const float ry = (float)h / (float)H, rx = (float)w / (float)W;
+  const int x = tx0 + 4 * lane;
+  if (x >= W) return;                        // (after the barrier)
+  Tap cx[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cx[k] = tap(min(x + k, W - 1), rx, w);
+  for (int y = ty0 + wave; y < min(ty0 + RB_TILE_H, H); y += RB_WAVES) {
+    const T* p = frame + (long)y * W + x;
+    unsigned char* o = dst + ((((long)b * J + j) * H + y) * W + x) * 3;
+    const bool whole = x + 3 < W;
+    const bool aligned = whole && (((uintptr_t)p | (uintptr_t)(p + hw) | (uintptr_t)(p + 2 * hw)) % Quad<T>::ALIGN) == 0;
+    Quad<T> q[3] = {};
+    if (aligned) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) q[c].load(p + c * hw);
+    }
+    const Tap cy = tap(y, ry, h);
+    const float* r0 = map + (long)cy.i0 * w;
+    const float* r1 = map + (long)cy.i1 * w;
+    unsigned px[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (x + k >= W) continue;
+      unsigned bg[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) bg[c] = aligned ? to_byte(q[c].at(k), sd[c], m[c]) : to_byte(p[c * hw + k], sd[c], m[c]);
+      const float t0 = r0[cx[k].i0] * cx[k].w0, t1 = r0[cx[k].i1] * cx[k].w1, top = t0 + t1;
+      const float u0 = r1[cx[k].i0] * cx[k].w0, u1 = r1[cx[k].i1] * cx[k].w1, bot = u0 + u1;
+      const float a0 = top * cy.w0, a1 = bot * cy.w1, a = a0 + a1;
+      if (fabsf(a) <= 3.402823466e38f) {                     // NaN or +-inf: the background stays
+        float al = a * gain;
+        al = al >= 0.f ? al : 0.f;                            // (a NaN product counts as 0)
+        al = fminf(al, max_alpha);
+        float ci = a * cs;
+        ci = ci >= 0.f ? ci : 0.f;
+        ci = fminf(ci, 1.f);
+        ci = ci * 255.f;
+        const unsigned colour = s_lut[(int)ci];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bg[c] = blend(bg[c], colour >> (8 * c) & 255u, al);
+      }
+      px[k] = bg[0] | (bg[1] << 8) | (bg[2] << 16);
+    }
+    if (whole && ((uintptr_t)o & 3u) == 0) {
+      unsigned* o4 = reinterpret_cast<unsigned*>(o);         // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+      o4[0] = px[0] | (px[1] << 24);
+      o4[1] = (px[1] >> 8) | (px[2] << 16);
+      o4[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x + k < W) {
+          o[3 * k] = (unsigned char)px[k];
+          o[3 * k + 1] = (unsigned char)(px[k] >> 8);
+          o[3 * k + 2] = (unsigned char)(px[k] >> 16);
+        }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int fod_render_boxes(const void* src, int src_is_u8, unsigned char* dst, int B, int L, int H, int W,
@@ -238,6 +362,36 @@ extern "C" int fod_render_boxes(const void* src, int src_is_u8, unsigned char* d
   else
     hipLaunchKernelGGL(render_boxes_kernel<float>, grid, dim3(RB_THREADS), 0, stream, (const float*)src, dst, L, H, W,
                        src_stride_b, src_stride_l, frame_idx, mean, stdv, boxes, labels, N, palette, P, thickness);
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}
+
+extern "C" int fod_render_attention(const void* src, int src_is_u8, unsigned char* dst, int B, int L, int J, int H, int W,
+                                    long src_stride_b, long src_stride_l, const int* frame_idx, const float* mean,
+                                    const float* stdv, const float* maps, int h, int w, long map_stride_b,
+                                    long map_stride_j, const float* colour_scale, const unsigned char* lut, float gain,
+                                    float max_alpha, hipStream_t stream) {
+  FOD_REQUIRE(src && dst && frame_idx && maps && colour_scale && lut, "render_attention: null pointer");
+  FOD_REQUIRE(src_is_u8 || (mean && stdv), "render_attention: an f32 source needs mean and std (null pointer)");
+  FOD_REQUIRE(h >= 1 && w >= 1 && (long)h * w <= INT_MAX, "render_attention: a %dx%d map", h, w);
+  FOD_REQUIRE(J >= 1 && J <= 32, "render_attention: %d pictures per sample, not 1..32", J);
+  FOD_REQUIRE(max_alpha >= 0.f && max_alpha <= 1.f, "render_attention: max_alpha %f outside [0, 1]", max_alpha);
+  FOD_REQUIRE(fabsf(gain) <= 3.402823466e38f, "render_attention: gain is not finite");
+  FOD_REQUIRE(H > 0 && W > 0 && (long)3 * H * W <= INT_MAX, "render_attention: bad frame %dx%d", H, W);
+  FOD_REQUIRE(B > 0 && (long)B * J <= 65535 && L > 0, "render_attention: bad clip extent %dx%d", B, L);
+  FOD_REQUIRE(src_stride_l >= (long)3 * H * W && src_stride_b >= (long)3 * H * W,
+              "render_attention: frame strides %ld / %ld overlap the 3x%dx%d planes", src_stride_b, src_stride_l, H, W);
+  FOD_REQUIRE(map_stride_b >= 0 && map_stride_j >= 0, "render_attention: negative map stride");
+  const dim3 grid((W + RB_TILE_W - 1) / RB_TILE_W, (H + RB_TILE_H - 1) / RB_TILE_H, B * J);
+  FOD_REQUIRE(grid.y <= 65535, "render_attention: frame %dx%d is too tall", H, W);
+  if (src_is_u8)
+    hipLaunchKernelGGL(render_attention_kernel<unsigned char>, grid, dim3(RB_THREADS), 0, stream,
+                       (const unsigned char*)src, dst, L, J, H, W, src_stride_b, src_stride_l, frame_idx, mean, stdv, maps,
+                       h, w, map_stride_b, map_stride_j, colour_scale, lut, gain, max_alpha);
+  else
+    hipLaunchKernelGGL(render_attention_kernel<float>, grid, dim3(RB_THREADS), 0, stream, (const float*)src, dst, L, J, H,
+                       W, src_stride_b, src_stride_l, frame_idx, mean, stdv, maps, h, w, map_stride_b, map_stride_j,
+                       colour_scale, lut, gain, max_alpha);
   FOD_LAUNCH_CHECK();
   return FOD_OK;
 }

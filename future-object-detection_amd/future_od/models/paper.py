@@ -331,10 +331,37 @@ class FuturePredCore(nn.Module):
         self.skip_dead_frames = True
 
     drop_future = True                     # the last frame of the clip is the one to predict, never an input
+    # a transformer.AttentionTap (None: nothing changes): for the length of one forward it sits on the LAST decoder
+    # layer's cross-attention blocks and learns which clip frame every memory image is (SpatioTemporalDETR.predict)
+    attention_tap = None
 
     def forward(self, images: Tensor, imu: Tensor = None, temporal_offsets: Tensor = None, temporal_table=None):
         """temporal_table: optional f32 [B, past, D] that replaces the temporal term computed from this clip (the
         tracker baseline runs single frames with the term of a three-frame clip)."""
+        tap = self.attention_tap
+        if tap is None:
+            return self._forward(images, imu, temporal_offsets, temporal_table)
+        if isinstance(self.joint_encoder, JointEncoderF2F):
+            raise ValueError("attention maps: JointEncoderF2F folds the past frames into ONE frame; its detector has no "
+                             "per-frame memory to show")
+        blocks = self.detector.decoder.layers[-1].image_attend
+        for block in blocks:
+            block.attention_tap = tap
+        try:
+            return self._forward(images, imu, temporal_offsets, temporal_table)
+        finally:
+            for block in blocks:
+                block.attention_tap = None
+
+    def _memory_frames(self, past, keep):
+        """(frames, split) of the detector's memory images in a clip of `past` input frames, `keep` of them encoded:
+        'attend one at a time': image j is clip frame past - 1 - j (the current frame first, CDetrDetector.forward);
+        'attend all at once': ONE memory whose keep * N keys are frames past - keep .. past - 1, in that order."""
+        if self.detector.image_memory_mode == "attend all at once":
+            return list(range(past - keep, past)), keep
+        return [past - 1 - j for j in range(min(keep, self.detector.num_images))], 1
+
+    def _forward(self, images, imu, temporal_offsets, temporal_table):
         B, L = images.shape[:2]
         past = L - 1 if self.drop_future else L
         assert past > 0
@@ -346,6 +373,9 @@ class FuturePredCore(nn.Module):
         imu_k = imu[:, past - keep:past] if imu is not None else None
         tokens, (h, w), _ego = self.separate_encoder(clip, self.pos_encoder, imu_k, dtype=self.compute_dtype)
         F_, N, D = tokens.shape
+        if self.attention_tap is not None:
+            self.attention_tap.hw = (h, w)
+            self.attention_tap.frames, self.attention_tap.split = self._memory_frames(past, keep)
         frames = list(tokens.view(keep, B, N, D).unbind(0))
         spatial = self.pos_encoder.spatial_table(h, w, D, self.compute_dtype, tokens.device)      # [N, D]
         # encodings of (a) all kept frames as one token sequence, (b) the current (last) frame alone
@@ -448,6 +478,9 @@ class TrackerBaselineCore(SingleFrameCore):
         B, L = images.shape[:2]
         if L == 1:
             return super().forward(images, imu, temporal_offsets)
+        if self.attention_tap is not None:
+            raise ValueError("attention maps: TrackerBaselineCore extrapolates the future detections from two single-frame "
+                             "passes; no query attends to a past frame")
         if L != 3:
             raise ValueError("TrackerBaselineCore takes clips of 1 frame (detect) or 3 frames (detect, detect, extrapolate)")
         tt3 = None

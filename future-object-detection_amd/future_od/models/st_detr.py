@@ -146,7 +146,7 @@ class SpatioTemporalDETR(nn.Module):
         return {k: data[k] for k in keys}
 
     @torch.no_grad()
-    def predict(self, data, top_k=100, score_threshold=0.0, per_query=False, box_map=None):
+    def predict(self, data, top_k=100, score_threshold=0.0, per_query=False, box_map=None, attention=False):
         """Detections for frames WITHOUT annotations: the core exactly as `forward` calls it, then one launch
         (ops.detect_select) in place of the reference's post-processing chain (st_detr.py:190-234, ConditionalDETR's
         PostProcess, demo.ipynb:171-172,245) -- no targets, no matcher, no loss, no AP bookkeeping, no host sync.
@@ -154,20 +154,41 @@ class SpatioTemporalDETR(nn.Module):
         on the device: per sample the `top_k` best of all (query, class) pairs -- `per_query`: of the queries, each
         with its best class -- whose score reaches `score_threshold`, best first; rows from `count[b]` on are padding
         (score 0, label / query -1, box 0).  `box_map` f32 [B,4] = (sx, sy, ox, oy) (default: `data["box_map"]`, which
-        the label-free raw-frame path provides) takes the boxes from the network's input frame to the camera's."""
+        the label-free raw-frame path provides) takes the boxes from the network's input frame to the camera's.
+        `attention`: the dict also gets "attention" f32 [B, K, J, h, w] -- for every returned detection the attention of
+        its query over the J memory images of the LAST decoder layer, averaged over the heads (h x w: the backbone's
+        grid) -- and "attention_frames" i32 [J], the clip frame of each image.  ONE more launch (ops.attn_maps with
+        `query` as its index table; padding rows are zeros), nothing read back.  'attend one at a time': a map sums to 1
+        per image; 'attend all at once': the ONE memory's keys are returned split into its frames, and a map sums to 1
+        over all of them.  Off (the default) nothing is tapped and no launch, key or number changes."""
         if self.training:
             raise RuntimeError("predict: evaluation only (model.eval()); dropout would make the detections random")
         images = data["video"]
         H, W = images.shape[-2:]
         if box_map is None:
             box_map = data.get("box_map")
-        outputs, _moods = self._model(images, **self._core_kwargs(data))
+        tap = None
+        if attention:
+            from future_od.models.transformer import AttentionTap
+            if not hasattr(type(self._model), "attention_tap"):
+                raise ValueError(f"attention maps: {type(self._model).__name__} has no tapped cross-attention")
+            tap = self._model.attention_tap = AttentionTap()
+        try:
+            outputs, _moods = self._model(images, **self._core_kwargs(data))
+        finally:
+            if tap is not None:
+                self._model.attention_tap = None
         if not (isinstance(outputs, dict) and outputs["pred_logits"].dim() == 3):
             raise ValueError("cannot interpret output on the format: %s" % type(outputs))
         scores, labels, boxes, query, count = ops.detect_select(
             outputs["pred_logits"].detach().float().contiguous(), outputs["pred_boxes"].detach().float().contiguous(),
             H, W, top_k, score_threshold, per_query, box_map)
-        return {"scores": scores, "labels": labels, "boxes": boxes, "query": query, "count": count}
+        out = {"scores": scores, "labels": labels, "boxes": boxes, "query": query, "count": count}
+        if tap is not None:
+            out["attention"] = tap.maps(self._model.detector.decoder.layers[-1].self_attend.Nhead, query)
+            first, step = tap.frames[0], (tap.frames[1] - tap.frames[0] if len(tap.frames) > 1 else 1)
+            out["attention_frames"] = torch.arange(len(tap.frames), dtype=torch.int32, device=query.device) * step + first
+        return out
 
     def loss(self, data, outputs, distributed, targets=None, packed=None, num_boxes=None):
         if targets is None and packed is None:

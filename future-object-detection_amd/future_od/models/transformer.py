@@ -23,6 +23,7 @@ import torch
 from torch import Tensor, nn
 
 from future_od.native import functional as Fn
+from future_od.native import ops
 from future_od.switches import SW
 
 
@@ -222,6 +223,7 @@ class SlotToImageAttention(Attention):
         self.D, self.Nhead = D, Nhead
         self.droprate = dropout            # on the attention probabilities (reference :126)
         self.store_attention = False
+        self.attention_tap = None          # an AttentionTap: forward hands it this block's operands (predict(attention=True))
 
     def forward(self, x, qpos, query_sine, side, layer, image, is_first, qs=None, qpos_proj=None, keep=False,
                 attn_mask=None, key_padding_mask=None, qc_pre=None):
@@ -256,15 +258,57 @@ class SlotToImageAttention(Attention):
         # per head: q = [qc | qs], k = [kc | ks] (64 wide), scale (2D/heads)^-0.5
         a = Fn.hoisted_cross_attention(qc, qs, side, layer, image, 1.0 / math.sqrt(2 * D // self.Nhead),
                                        drop_p=self.droprate, training=self.training)
-        if self.store_attention:
+        if self.attention_tap is not None:
+            self.attention_tap(qc, qs, side, layer, image)       # references only: nothing is computed here
+        if self.store_attention and qc.is_cuda:
+            # the reference's demo surface, [B, M, N]: every query of this block, one fod_attn_maps launch
+            self.stored_attention = attention_maps([(qc, qs, side, layer, image)], self.Nhead)[:, :, 0]
+        elif self.store_attention:
             kc, ks, _v = side.slots(layer, image)
-            self.stored_attention = _head_mean_weights(qc, kc, qs, ks.unsqueeze(0).expand(B, -1, -1), self.Nhead)
+            ks = ks.unsqueeze(0).expand(B, -1, -1) if ks.dim() == 2 else ks
+            self.stored_attention = _head_mean_weights(qc, kc, qs, ks, self.Nhead)
         return (_Proj(a, self.fun.out_proj), x_keep) if keep else _Proj(a, self.fun.out_proj)
+
+
+class AttentionTap:
+    """Collects the operands of the conditional cross-attention blocks it is installed on
+    (SlotToImageAttention.attention_tap) during ONE forward pass: `blocks[image] = (qc, qs, side, layer, image)`,
+    references to what the block handed its attention kernel.  A later detector pass (slot states: one per past frame)
+    overwrites an earlier one, so the LAST pass is kept.  FuturePredCore adds where the keys come from: `hw` = (h, w) of
+    a memory image, `frames` = the clip frame of every returned image, `split` = how many images ONE memory's keys are
+    cut into ('attend all at once': keep, else 1)."""
+
+    def __init__(self):
+        self.blocks, self.hw, self.frames, self.split = {}, None, None, 1
+
+    def __call__(self, qc, qs, side, layer, image):
+        self.blocks[image] = (qc, qs, side, layer, image)
+
+    def maps(self, nhead, query_idx=None):
+        """f32 [B, Q, J, h, w] of the tapped blocks for the queries `query_idx` i32 [B, Q] (None: all, in order)."""
+        if not self.blocks or self.hw is None:
+            raise ValueError("AttentionTap: no cross-attention block has run since the tap was installed")
+        out = attention_maps([self.blocks[i] for i in sorted(self.blocks)], nhead, query_idx)     # [B, Q, images, S]
+        B, Q = out.shape[:2]
+        return out.view(B, Q, len(self.blocks) * self.split, self.hw[0], self.hw[1])
+
+
+@torch.no_grad()
+def attention_maps(blocks, nhead, query_idx=None):
+    """Head-averaged attention of the queries `query_idx` (None: all) over the keys of every block in `blocks` (tuples
+    (qc, qs, side, layer, image) as SlotToImageAttention hands them to its tap): f32 [B, Q, len(blocks), N] in ONE
+    launch (ops.attn_maps) that reads the key slots of the hoisted buffers where they lie.  Device tensors only."""
+    jobs = []
+    for qc, qs, side, layer, image in blocks:
+        kc, ks, _v = side.slots(layer, image)
+        jobs.append((qc.detach().contiguous(), qs.detach().contiguous(), kc.detach(), ks.detach()))
+    D = blocks[0][0].shape[-1]
+    return ops.attn_maps(jobs, 1.0 / math.sqrt(2 * D // nhead), query_idx)
 
 
 @torch.no_grad()
 def _head_mean_weights(qc, kc, qs, ks, H):
-    """Visualisation only (demo.ipynb): head-averaged attention map [B,M,N]; off the hot path."""
+    """Visualisation only (demo.ipynb): head-averaged attention map [B,M,N]; the form for CPU tensors."""
     B, M, D = qc.shape
     N = kc.shape[1]
     hd = D // H

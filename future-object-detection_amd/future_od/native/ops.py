@@ -506,6 +506,62 @@ def render_boxes(video, boxes, labels, *, frame_idx=None, mean=None, std=None, p
     return out
 
 
+def render_attention(video, maps, frame_idx, colour_scale, *, mean=None, std=None, lut, gain=50.0, max_alpha=0.4,
+                     out=None):
+    """The maps of one detection per sample blended over their past frames: uint8 RGB [B, J, H, W, 3] in one launch
+    (include/fod_ext.h, fod_render_attention, states the map).  video [B, L, 3, H, W] as render_boxes takes it; maps f32
+    [B, J, h, w] with dense [h, w] planes and any strides over B and J (a slice of predict's `attention`); frame_idx i32
+    [B, J]; colour_scale f32 [B, J]; lut uint8 [256, 3] -- all on the clip's device.  There is no CPU fallback."""
+    who = "render_attention"
+    if not isinstance(video, torch.Tensor) or not video.is_cuda or video.dim() != 5 or video.shape[2] != 3 \
+            or video.dtype not in (torch.float32, torch.uint8):
+        raise L.FodError(f"{who}: video must be an f32 or uint8 device tensor [B, L, 3, H, W] "
+                         "(the HIP path has no CPU fallback)")
+    b, l, _, h, w = video.shape
+    sb, sl, sc, sh, sw = video.stride()
+    if b == 1:
+        sb = 3 * h * w
+    if l == 1:
+        sl = 3 * h * w
+    if (sc, sh, sw) != (h * w, w, 1) or min(sb, sl) < 3 * h * w:
+        raise L.FodError(f"{who}: frame planes must be contiguous, got strides {video.stride()}")
+    u8 = video.dtype == torch.uint8
+    if not isinstance(maps, torch.Tensor) or maps.dim() != 4 or maps.shape[0] != b or maps.dtype != torch.float32 \
+            or maps.device != video.device:
+        raise L.FodError(f"{who}: maps must be an f32 tensor [B, J, h, w] on {video.device} for a clip of {b}")
+    j, mh, mw = maps.shape[1:]
+    mb, mj, mr, mc = maps.stride()
+    if (mh > 1 and mr != mw) or (mw > 1 and mc != 1) or min(mb, mj) < 0 or maps.numel() == 0:
+        raise L.FodError(f"{who}: the [h, w] planes of maps must be dense, got strides {maps.stride()}")
+    operands = {"frame_idx": (frame_idx, torch.int32), "colour_scale": (colour_scale, torch.float32),
+                "lut": (lut, torch.uint8)}
+    if not u8:
+        operands.update(mean=(mean, torch.float32), std=(std, torch.float32))
+    if out is not None:
+        operands["out"] = (out, torch.uint8)
+    for name, (t, dtype) in operands.items():
+        if not isinstance(t, torch.Tensor):
+            raise L.FodError(f"{who}: {name} must be a {dtype} device tensor")
+        _chk(t, f"{who}: {name}", dtype)
+        if t.device != video.device:
+            raise L.FodError(f"{who}: {name} lives on {t.device}, the clip on {video.device}")
+    if tuple(frame_idx.shape) != (b, j) or tuple(colour_scale.shape) != (b, j):
+        raise L.FodError(f"{who}: frame_idx {tuple(frame_idx.shape)} / colour_scale {tuple(colour_scale.shape)} are not "
+                         f"[{b}, {j}]")
+    if tuple(lut.shape) != (256, 3):
+        raise L.FodError(f"{who}: lut {tuple(lut.shape)} is not [256, 3]")
+    if not u8 and (mean.numel() != 3 or std.numel() != 3):
+        raise L.FodError(f"{who}: mean {mean.numel()} / std {std.numel()} do not fit three planes")
+    if out is None:
+        out = torch.empty((b, j, h, w, 3), dtype=torch.uint8, device=video.device)
+    elif tuple(out.shape) != (b, j, h, w, 3):
+        raise L.FodError(f"{who}: out {tuple(out.shape)} is not [{b}, {j}, {h}, {w}, 3]")
+    call("fod_render_attention", ptr(video), int(u8), ptr(out), b, l, j, h, w, sb, sl, ptr(frame_idx),
+         None if u8 else ptr(mean), None if u8 else ptr(std), ptr(maps), mh, mw, mb, mj, ptr(colour_scale), ptr(lut),
+         float(gain), float(max_alpha), stream())
+    return out
+
+
 def conv_stem_fwd(xp, w, h, wd, *, shift=None, relu=True):
     """xp: haloed layout of an [*, 3, h, wd] clip; w [Cout, 7, 8, 4] -> y NHWC [F, Ho, Wo, Cout]."""
     _chk(xp, "xp"); _chk(w, "w", xp.dtype)
@@ -849,6 +905,64 @@ def attn_bwd_dkv_multi(jobs, shp):
     two = jobs[0][1] is not None
     call("fod_attn_bwd_dkv_multi", BF16, n, C.addressof(arr), _Addr(shp), stream(),
          work=2.0 * n * shp.B * shp.H * shp.Tq * shp.S * 32 * ((2 if two else 1) + 2), tag="fod_attn_bwd")
+
+
+def attn_maps(jobs, scale, query_idx=None, out=None):
+    """Head-averaged attention maps of selected queries over the keys of len(jobs) <= 32 memory images in ONE launch
+    (include/fod_ext.h, fod_attn_maps, states the map).  A job = (q1, q2, k1, k2): q* [B,Tq,H*32], k1 [B,S,H*32] (any
+    batch / token strides: column slots of a wider buffer), k2 [B,S,E] or a batch-shared table [S,E]; q2 / k2 None for
+    all jobs or for none; every job has the shape and strides of the first.  query_idx: i32 [B,Q] on the operands'
+    device (an index outside [0, Tq) gives a row of zeros) or None for every query in order.
+    -> f32 [B, Q, len(jobs), S] (`out`: a contiguous tensor of that shape to write into).  No CPU fallback."""
+    who = "attn_maps"
+    n = len(jobs)
+    if not 0 < n <= 32:
+        raise L.FodError(f"{who}: 1..32 jobs, got {n}")
+    q1, q2, k1, k2 = jobs[0]
+    dtp = q1.dtype
+    B, Tq, E = q1.shape
+    S = k1.shape[1]
+    if E % 32 or tuple(k1.shape) != (B, S, E):
+        raise L.FodError(f"{who}: q1 {tuple(q1.shape)} / k1 {tuple(k1.shape)} are not [B,Tq,H*32] / [B,S,H*32]")
+    qb, qt = _bt(q1, "q1", dtp)
+    kb, kt = _bt(k1, "k1", dtp)
+    k2b = k2t = 0
+    if k2 is not None:
+        if tuple(k2.shape[-2:]) != (S, E):
+            raise L.FodError(f"{who}: k2 {tuple(k2.shape)} does not hold [{S}, {E}] per sample")
+        k2b, k2t = _bt(k2, "k2", dtp)
+    arr = (C.c_void_p * (4 * n))()
+    for i, job in enumerate(jobs):
+        a1, a2, b1, b2 = job
+        if (a2 is None) != (q2 is None) or (b2 is None) != (k2 is None) or (a2 is None) != (b2 is None):
+            raise L.FodError(f"{who}: q2 / k2 must be given for all jobs or for none")
+        if a1.shape != q1.shape or b1.shape != k1.shape or _bt(a1, "q1", dtp) != (qb, qt) or _bt(b1, "k1", dtp) != (kb, kt):
+            raise L.FodError(f"{who}: job {i} has another shape or other strides than job 0")
+        if a2 is not None:
+            _same_bt(a1, a2, "q2")
+            if b2.shape != k2.shape or _bt(b2, "k2", dtp) != (k2b, k2t):
+                raise L.FodError(f"{who}: k2 of job {i} has another shape or other strides than job 0's")
+        for k, t in enumerate(job):
+            arr[4 * i + k] = None if t is None else t.data_ptr()
+    Q = Tq
+    if query_idx is not None:
+        _chk(query_idx, f"{who}: query_idx", torch.int32)
+        if query_idx.dim() != 2 or query_idx.shape[0] != B or query_idx.device != q1.device:
+            raise L.FodError(f"{who}: query_idx {tuple(query_idx.shape)} on {query_idx.device} is not [B, Q] for {B} "
+                             f"samples on {q1.device}")
+        Q = query_idx.shape[1]
+    if out is None:
+        out = torch.empty((B, Q, n, S), dtype=torch.float32, device=q1.device)
+    else:
+        _chk(out, f"{who}: out", torch.float32)
+        if tuple(out.shape) != (B, Q, n, S) or out.device != q1.device:
+            raise L.FodError(f"{who}: out {tuple(out.shape)} is not [{B}, {Q}, {n}, {S}] on {q1.device}")
+    H = E // 32
+    shp = AttnShape(B, H, Tq, S, qb, qt, kb, kt, 0, 0, 0, 0, float(scale), k2b, k2t, 0, 0, 0.0, 0, None, None, None, 0.0)
+    parts = 2 if q2 is not None else 1
+    call("fod_attn_maps", dt(q1), n, C.addressof(arr), ptr(query_idx), Q, ptr(out), _Addr(shp), stream(),
+         work=2.0 * 2 * n * B * H * Q * S * 32 * parts)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ norm / eltwise

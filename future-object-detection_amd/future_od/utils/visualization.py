@@ -8,6 +8,11 @@ zlib and struct.  `draw_boxes` is the per-sample CPU form and the definition of 
 datasets.transforms.photometric is for the photometric kernel; `render` on CPU tensors is built on it and gives the
 kernel's bytes.
 
+`render_attention` blends the attention maps that `predict(attention=True)` returns over the past frames they belong to
+(reference demo.ipynb: F.interpolate of every query's map to full size, matplotlib on the host): one launch for all
+pictures of a device clip (ops.render_attention, include/fod_ext.h: fod_render_attention), a torch form with the same
+bytes for CPU tensors.
+
 Not built: text or captions in the picture, filled or alpha-blended boxes, a thickness per box, bf16 sources, PNG
 compression tuning, drawing every frame of a clip to disk."""
 import os
@@ -123,6 +128,100 @@ def render_detections(video, det, min_score=0.5, frame_idx=None, thickness=3, pa
     slot = torch.arange(labels.shape[1], device=labels.device)
     hidden = (scores < min_score) | (slot[None, :] >= det["count"][:, None])
     return render(video, det["boxes"], labels.masked_fill(hidden, -1), frame_idx, thickness, palette)
+
+
+# uint8 [256, 3], a diverging blue - white - red ramp by an integer rule: entry i is (2i, 2i, 255) for i <= 127 and
+# (255, 2(255 - i), 2(255 - i)) for i >= 128 -- blue at 0, (254, 254, 255) | (255, 254, 254) in the middle, red at 255.
+# (Not matplotlib's `coolwarm`, which the reference's notebook uses: same idea, other numbers.)
+ATTENTION_LUT = torch.tensor([[2 * i, 2 * i, 255] if i <= 127 else [255, 2 * (255 - i), 2 * (255 - i)] for i in range(256)],
+                             dtype=torch.uint8)
+
+
+def _taps(n_out, n_in):
+    """Bilinear source rows of `n_out` destination rows over `n_in` (F.interpolate's coordinate, align_corners=False),
+    every step one f32 operation: f = max((d + 0.5) * (n_in / n_out) - 0.5, 0), i0 = min(trunc(f), n_in - 1),
+    i1 = min(i0 + 1, n_in - 1), w1 = f - i0, w0 = 1 - w1."""
+    ratio = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    f = (((torch.arange(n_out, dtype=torch.float32) + 0.5) * ratio) - 0.5).clamp_min(0.0)
+    i0 = f.to(torch.int64).clamp_max(n_in - 1)
+    i1 = (i0 + 1).clamp_max(n_in - 1)
+    w1 = f - i0.to(torch.float32)
+    return i0, i1, 1.0 - w1, w1
+
+
+def overlay_map(background, amap, colour_scale, gain=50.0, max_alpha=0.4, lut=ATTENTION_LUT):
+    """One picture of `render_attention` on the CPU and the definition of the kernel's map: `background` uint8 [3, H, W],
+    `amap` f32 [h, w] -> uint8 [H, W, 3].  With a = the bilinear sample of the map (top = m[y0,x0] * wx0 + m[y0,x1] * wx1,
+    bot likewise on row y1, a = top * wy0 + bot * wy1):
+        alpha = min(max(a * gain, 0), max_alpha)      colour = lut[trunc(min(max(a * colour_scale, 0), 1) * 255)]
+        byte = trunc(min(max(bg * (1 - alpha) + colour * alpha, 0), 255))
+    every step one f32 operation; max(v, 0) of a NaN is 0; where a is not finite the background stays."""
+    f32 = torch.float32
+    _, H, W = background.shape
+    h, w = amap.shape
+    y0, y1, wy0, wy1 = _taps(H, h)
+    x0, x1, wx0, wx1 = _taps(W, w)
+    m = amap.to(f32)
+    top = m[y0][:, x0] * wx0 + m[y0][:, x1] * wx1
+    bot = m[y1][:, x0] * wx0 + m[y1][:, x1] * wx1
+    a = top * wy0[:, None] + bot * wy1[:, None]
+    zero = torch.zeros((), dtype=f32)
+    alpha = a * torch.tensor(float(gain), dtype=f32)
+    alpha = torch.minimum(torch.where(alpha >= 0, alpha, zero), torch.tensor(float(max_alpha), dtype=f32))
+    level = a * torch.as_tensor(colour_scale, dtype=f32)
+    level = torch.minimum(torch.where(level >= 0, level, zero), torch.ones((), dtype=f32)) * 255.0
+    colour = lut.to(f32)[level.to(torch.int64)]                                   # [H, W, 3]
+    bg = background.permute(1, 2, 0).to(f32)
+    mixed = bg * (1.0 - alpha)[..., None] + colour * alpha[..., None]
+    mixed = torch.where(torch.isfinite(a)[..., None], mixed, bg)
+    return mixed.clamp(0, 255).to(torch.uint8)
+
+
+_LUT_ON = {}
+
+
+def render_attention(video, attention, frames, slot, gain=50.0, max_alpha=0.4, lut=ATTENTION_LUT):
+    """The attention maps of ONE detection per sample over the past frames they look at -> uint8 [B, J, H, W, 3] on the
+    clip's device.  `video` [B, L, 3, H, W] f32 normalised or raw uint8; `attention` f32 [B, K, J, h, w] and `frames`
+    i32 [J] as `predict(attention=True)` returns them ("attention", "attention_frames": picture j is clip frame
+    frames[j]; negative counts from the end, then clamped); `slot`: which of the K detections, an int or i32 [B].
+    Per picture the map is upsampled bilinearly, coloured through `lut` (uint8 [256, 3]) after scaling by 1 / its
+    maximum, and blended with alpha = min(map * gain, max_alpha) (`overlay_map` states every step; the reference's
+    notebook uses 50 and 0.4).  A device clip is one launch of ops.render_attention; CPU tensors go through
+    `overlay_map` per picture and give the same bytes."""
+    if video.dim() != 5 or video.shape[2] != 3 or video.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"render_attention: video must be f32 or uint8 [B, L, 3, H, W], got {video.dtype} "
+                         f"{tuple(video.shape)}")
+    B, L = video.shape[:2]
+    if attention.dim() != 5 or attention.shape[0] != B:
+        raise ValueError(f"render_attention: attention must be [B, K, J, h, w] for {B} samples, got {tuple(attention.shape)}")
+    if not 0.0 <= float(max_alpha) <= 1.0:
+        raise ValueError(f"render_attention: max_alpha {max_alpha} outside [0, 1]")
+    K, J = attention.shape[1:3]
+    attention = attention.to(video.device, torch.float32)
+    if isinstance(slot, int):
+        maps = attention[:, slot]                                                  # a view: no copy
+    else:
+        maps = attention[torch.arange(B, device=video.device), slot.to(video.device, torch.int64)]
+    frames = torch.as_tensor(frames).to(video.device, torch.int32).reshape(J)
+    # matplotlib's auto-normalisation: the colour runs up to the map's maximum (an all-zero map stays at lut[0])
+    colour_scale = 1.0 / maps.amax(dim=(2, 3)).clamp_min(1e-30)
+    if video.is_cuda:
+        from future_od.native import ops
+        _, mean, std = _device_constants(video.device)
+        key = (video.device, id(lut))
+        if key not in _LUT_ON:
+            _LUT_ON[key] = (lut, lut.to(video.device).contiguous())       # (the table is kept: its id stays its own)
+        return ops.render_attention(video, maps, frames[None].expand(B, J).contiguous(), colour_scale.contiguous(),
+                                    mean=mean, std=std, lut=_LUT_ON[key][1], gain=gain, max_alpha=max_alpha)
+    out = []
+    for b in range(B):
+        for j in range(J):
+            f = int(frames[j])
+            f = min(max(f + L if f < 0 else f, 0), L - 1)
+            bg = video[b, f] if video.dtype == torch.uint8 else to_bytes(revert_imagenet_normalization(video[b, f]))
+            out.append(overlay_map(bg, maps[b, j], colour_scale[b, j], gain, max_alpha, lut))
+    return torch.stack(out).view(B, J, *out[0].shape).contiguous()
 
 
 def _chunk(kind, body):

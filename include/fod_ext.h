@@ -113,6 +113,56 @@ int fod_clip_crop_resize_photo(const unsigned char* src, float* dst, int B, int 
 int fod_render_boxes(const void* src, int src_is_u8, unsigned char* dst, int B, int L, int H, int W, long src_stride_b,
                      long src_stride_l, const int* frame_idx, const float* mean, const float* std, const float* boxes,
                      const int* labels, int N, const unsigned char* palette, int P, int thickness, fod_stream_t stream);
+/* Attention maps for looking at a trained model: the head-averaged cross-attention of SELECTED queries over the keys of
+ * up to 32 memory images in ONE launch (the reference's demo.ipynb reads SlotToImageAttention.stored_attention, the head
+ * mean of the softmax weights, one block at a time).
+ *   ptrs: HOST array of njobs x 4 addresses in the order q1, q2, k1, k2 (q2 / k2 NULL for all jobs or for none), 16-byte
+ *        aligned; njobs is 1..32.  The addresses travel in the kernel arguments, as in fod_attn_bwd_dkv_multi: a captured
+ *        launch needs no table in memory.  A job is one memory image: its queries [B,Tq,H*32], its keys [B,S,H*32].
+ *   shape: B, H (at most 64), Tq, S, the q / k / k2 strides and scale are honoured exactly as fod_attn_fwd honours them
+ *        (k2_token_stride = 0: the strides of k1; k2_batch_stride = 0: one positional key table shared by the batch;
+ *        strides are multiples of 8 elements).  The v / o strides, the split scratch and dq_scale are not read.
+ *        drop_p != 0 is FOD_ERR_ARG: the map is the probabilities before dropout.
+ *   query_idx: DEVICE i32 [B][Q], or NULL for the identity with Q == Tq.  An index outside [0, Tq) gives a row of zeros
+ *        (the padding of fod_detect_select is -1); duplicates are allowed.
+ *   out: f32 [B][Q][njobs][S], dense:
+ *        out[b,i,j,s] = (1/H) sum_h softmax_s((q1_h . k1_h + q2_h . k2_h) * scale)   for query query_idx[b,i] of job j,
+ *        head h = channels [32h, 32h+32).  Every element is written, by exactly one thread; no atomics: the result does
+ *        not depend on timing.
+ * dtype FOD_BF16: the products are exact and summed in f32; FOD_F32: an f32 fma chain on the unrounded operands.  With
+ * x = score * (scale * log2 e) rounded to f32, an element is 2^((x - max2) - log2 sum2) with max2 the row maximum of x
+ * and sum2 the f32 sum of 2^(x - max2) over the row, each 2^ one v_exp_f32; the head mean is the f32 sum times (1/H).
+ * FOD_ERR_ARG before any launch: njobs outside 1..32; Q or Tq outside 1..1024; S < 1; q2 / k2 given for some jobs or
+ * operands only; a NULL out, ptrs, shape, q1 or k1; NULL query_idx with Q != Tq; drop_p != 0; H above 64; a misaligned
+ * operand or stride. */
+int fod_attn_maps(int dtype, int njobs, const void* const* ptrs, const int* query_idx, int Q, float* out,
+                  const fod_attn_shape* shape, fod_stream_t stream);
+/* Visualisation: the maps of one detection per sample blended over their past frames, B x J pictures in ONE launch (the
+ * reference's demo.ipynb upsamples every query's map with F.interpolate and blends with matplotlib on the host).
+ * future_od/utils/visualization.py (render_attention) is the CPU form.  Picture (b, j) is frame frame_idx[b][j] of the
+ * clip with map (b, j) over it.
+ *   src, src_is_u8, L, H, W, src_stride_b, src_stride_l, mean, std: as fod_render_boxes, and so is the background BYTE
+ *        bg of a pixel and channel (f32: (x * std + mean) * 255 in three roundings, truncated, clamped, not finite -> 0).
+ *   frame_idx: DEVICE i32 [B][J]; a negative value counts from the end, then the value is clamped into [0, L).
+ *   maps: f32 [h][w] per (b, j) at maps + b * map_stride_b + j * map_stride_j (ELEMENTS; rows dense).
+ *   colour_scale: DEVICE f32 [B][J];  lut: DEVICE uint8 [256][3];  dst: uint8 [B][J][H][W][3], interleaved RGB.
+ * Per pixel (y, x), every step ONE f32 operation, no fused multiply-add:
+ *   fy = max(((y + 0.5) * (h / H)) - 0.5, 0)   (F.interpolate's bilinear coordinate, align_corners=False; h / H is one
+ *   f32 division), y0 = min(trunc(fy), h - 1), y1 = min(y0 + 1, h - 1), wy1 = fy - y0, wy0 = 1 - wy1; likewise x.
+ *   top = m[y0][x0] * wx0 + m[y0][x1] * wx1,  bot = m[y1][x0] * wx0 + m[y1][x1] * wx1,  a = top * wy0 + bot * wy1
+ *   alpha = min(max(a * gain, 0), max_alpha)
+ *   colour = lut[trunc(min(max(a * colour_scale[b][j], 0), 1) * 255)]
+ *   byte[c] = trunc(min(max(bg[c] * (1 - alpha) + colour[c] * alpha, 0), 255))
+ * where max(v, 0) of a NaN v is 0.  An a that is not finite (NaN, +-inf) leaves the background byte.  gain = 0 or
+ * max_alpha = 0 gives fod_render_boxes' picture without boxes.  The reference's values are gain 50, max_alpha 0.4.
+ * FOD_ERR_ARG before any launch: a NULL src, dst, frame_idx, maps, colour_scale or lut; an f32 source without mean or
+ * std; h or w below 1; J outside 1..32; max_alpha outside [0, 1]; a gain that is not finite; strides below 3*H*W; a
+ * negative map stride; B * J above 65535. */
+int fod_render_attention(const void* src, int src_is_u8, unsigned char* dst, int B, int L, int J, int H, int W,
+                         long src_stride_b, long src_stride_l, const int* frame_idx, const float* mean, const float* std,
+                         const float* maps, int h, int w, long map_stride_b, long map_stride_j,
+                         const float* colour_scale, const unsigned char* lut, float gain, float max_alpha,
+                         fod_stream_t stream);
 
 #ifdef __cplusplus
 }
