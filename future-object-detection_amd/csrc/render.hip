@@ -11,6 +11,8 @@
 // wins), twelve bytes out as three dword stores.  A wave is one row of the tile, so a box's row tests are wave-uniform
 // and the LDS reads are broadcasts.  Rows whose addresses are not aligned, and the W % 4 tail, go element by element.
 // No atomics, no traffic between blocks, every output byte written by exactly one thread.
+// fod_render_attention (the maps of a detection over their frames) and fod_render_labels (captions on the pictures
+// of fod_render_boxes) follow further down with the same tiles.
 #include "common.h"
 #include "../../include/fod_ext.h"
 
@@ -336,7 +338,231 @@ __global__ __launch_bounds__(RB_THREADS) void render_attention_kernel(
   }
 }
 
+// ---- captions (fod_render_labels): index, class name and score of every drawn box as text on a plate above it, in
+// place on the pictures fod_render_boxes wrote.  Built as render_boxes_kernel is: a block owns the same tile, stages
+// the labels whose plates reach it -- rectangle, colours and the composed characters, in index order -- and every
+// thread then decides four consecutive pixels of a row, scanning the staged labels from the last to the first until
+// each pixel has met its topmost plate.  A wave is one row, so a plate's row test and its glyph row are wave-uniform;
+// a lane divides its column into (character, glyph column) and reads one character and one font byte from LDS.
+// Pixels outside every plate are neither read nor written; a painted pixel has exactly one writer.
+constexpr int RL_MAX_CHARS = 32;             // FOD_LABEL_MAX_CHARS of the header
+constexpr int RL_FONT_BYTES = 256 * 16;      // at most 256 glyphs of at most 16 rows
+
+__global__ __launch_bounds__(RB_THREADS) void render_labels_kernel(
+    unsigned char* __restrict__ dst, int H, int W, const float* __restrict__ boxes, const int* __restrict__ labels, int N,
+    const int* __restrict__ idents, const float* __restrict__ scores, const unsigned char* __restrict__ names,
+    int n_names, int name_stride, const unsigned char* __restrict__ palette, int P,
+    const unsigned char* __restrict__ font, int font_first, int G, int FW, int FH, int s, int t) {
+  __shared__ int4 s_rect[RB_MAX_BOXES];      // (x0, y0, x1, y1): the plate's corner and its clipped end
+  __shared__ unsigned s_colour[RB_MAX_BOXES];                  // plate colour, bit 24: white ink
+  __shared__ unsigned char s_text[RB_MAX_BOXES * RL_MAX_CHARS];
+  __shared__ unsigned char s_font[RL_FONT_BYTES];
+  __shared__ int s_count[RB_WAVES];
+  const int b = blockIdx.z;
+  const int tx0 = blockIdx.x * RB_TILE_W, ty0 = blockIdx.y * RB_TILE_H;
+  const int lane = threadIdx.x & 63, wave = uniform((int)threadIdx.x >> 6);
+  const int cw = FW + 1, Hp = (FH + 2) * s;
+  // a / d as (a * (65536 / d + 1)) >> 16: exact for d <= 9 and a < 7273, and no plate is wider than 2312 pixels or has
+  // more than 288 font columns (the division the compiler writes for an unknown d is some thirty instructions, three
+  // times per pixel, in a kernel that waits on its own results: 36.7 -> 29.4 us at 300 captions)
+  const unsigned by_s = 65536u / (unsigned)s + 1u, by_cw = 65536u / (unsigned)cw + 1u;
+
+  for (int i = (int)threadIdx.x; i < G * FH; i += RB_THREADS) s_font[i] = font[i];
+
+  // ---- stage the labels whose plates reach the tile, in index order
+  int staged = 0;                            // the same in every thread
+  const float lo = (float)t, hx = (float)(W - t), hy = (float)(H - t);
+  for (int base = 0; base < N; base += RB_THREADS) {
+    const int i = base + (int)threadIdx.x;
+    bool keep = false;
+    int4 r = make_int4(0, 0, 0, 0);
+    unsigned colour = 0;
+    int ident = -1, pct = -1, len_id = 0, len_name = -1;       // -1: the part is absent
+    unsigned name[RL_MAX_CHARS / 4] = {};    // the bytes of the name's row, four to a word
+    if (i < N) {
+      // a block spends its time here waiting for loads, so they are issued together: first the label's own fields
+      // (none depends on another), then -- they need the label -- its colour and the whole row of its name
+      const long e = (long)b * N + i;
+      const int label = labels[e];
+      const float x1 = boxes[4 * e], y1 = boxes[4 * e + 1], x2 = boxes[4 * e + 2], y2 = boxes[4 * e + 3];
+      if (idents) ident = idents[e];
+      const float sc = scores ? scores[e] : __builtin_nanf("");
+      if (label >= 0 && label < P && x1 == x1 && y1 == y1 && x2 == x2 && y2 == y2) {
+        const unsigned char* c = palette + 3 * label;
+        const unsigned red = c[0], green = c[1], blue = c[2];
+        int n = 0, parts = 0;
+        if (names && label < n_names) {
+          const int first = label * name_stride, last = n_names * name_stride - 1;
+          bool open = true;                  // no 0 so far
+          len_name = 0;
+#pragma unroll
+          for (int j = 0; j < RL_MAX_CHARS; ++j) {             // no branch around a load: they all fly at once
+            const unsigned byte = names[min(first + j, last)];                    // (past the row: bytes that are not used)
+            name[j >> 2] |= byte << (8 * (j & 3));
+            open = open && byte;
+            len_name += open;
+          }
+          len_name = min(len_name, name_stride);
+          n += len_name;
+          ++parts;
+        }
+        if (ident >= 0) {
+          len_id = 1;
+          for (int v = ident; v >= 10; v /= 10) ++len_id;
+          n += len_id;
+          ++parts;
+        }
+        if (sc == sc) {
+          pct = (int)fminf(fmaxf(sc * 100.f, 0.f), 99.f);
+          n += 2;
+          ++parts;
+        }
+        n = min(n + max(parts - 1, 0), RL_MAX_CHARS);
+        if (n > 0) {
+          const int Wp = (n * cw + 1) * s;
+          const int lf = (int)fminf(fmaxf(x1, lo), hx), tp = (int)fminf(fmaxf(y1, lo), hy);
+          int x0 = lf - t, y0 = tp - t - Hp;
+          if (y0 < 0) y0 = tp;               // no room above the box: the caption moves inside
+          x0 = max(min(x0, W - Wp), 0);
+          y0 = max(min(y0, H - Hp), 0);
+          r = make_int4(x0, y0, min(x0 + Wp, W), min(y0 + Hp, H));
+          colour = red | (green << 8) | (blue << 16);
+          if (299u * red + 587u * green + 114u * blue < 128000u) colour |= 1u << 24;
+          keep = r.x < tx0 + RB_TILE_W && r.z > tx0 && r.y < ty0 + RB_TILE_H && r.w > ty0;
+        }
+      }
+    }
+    const unsigned long long votes = __ballot(keep);
+    if (lane == 0) s_count[wave] = __popcll(votes);
+    __syncthreads();
+    int at = staged, total = 0;
+#pragma unroll
+    for (int w = 0; w < RB_WAVES; ++w) {
+      if (w < wave) at += s_count[w];
+      total += s_count[w];
+    }
+    if (keep) {
+      at += __popcll(votes & ((1ull << lane) - 1ull));
+      s_rect[at] = r;
+      s_colour[at] = colour;
+      // the characters: the parts that are present, one space between them, cut at RL_MAX_CHARS
+      unsigned char* text = s_text + at * RL_MAX_CHARS;
+      int pos = 0;
+      bool sep = false;                      // a part came before: a space goes in front of the next one
+      if (ident >= 0) {
+        int v = ident;
+        for (int j = len_id - 1; j >= 0; --j, v /= 10) text[j] = (unsigned char)('0' + v % 10);   // len_id <= 10
+        pos = len_id;
+        sep = true;
+      }
+      if (len_name >= 0) {
+        if (sep) text[pos++] = ' ';          // pos <= 10 here
+#pragma unroll
+        for (int j = 0; j < RL_MAX_CHARS; ++j)
+          if (j < len_name && pos + j < RL_MAX_CHARS) text[pos + j] = (unsigned char)(name[j >> 2] >> (8 * (j & 3)));
+        pos += len_name;
+        sep = true;
+      }
+      if (pct >= 0) {
+        if (sep && pos < RL_MAX_CHARS) text[pos] = ' ';
+        pos += sep;
+        if (pos < RL_MAX_CHARS) text[pos] = (unsigned char)('0' + pct / 10);
+        if (pos + 1 < RL_MAX_CHARS) text[pos + 1] = (unsigned char)('0' + pct % 10);
+      }
+    }
+    staged += total;
+    __syncthreads();                         // the counts are rewritten next round; after the last, the stage is whole
+  }
+
+  // ---- the plates
+  const int x = tx0 + 4 * lane;
+  if (x >= W) return;                        // (after the last barrier)
+  for (int y = ty0 + wave; y < min(ty0 + RB_TILE_H, H); y += RB_WAVES) {
+    const bool whole = x + 3 < W;
+    const unsigned past = whole ? 0u : (0xFu << (W - x)) & 0xFu;   // bit j: pixel x + j lies past the row
+    unsigned px[4] = {0u, 0u, 0u, 0u};
+    unsigned done = past;                    // bit j: pixel x + j has met its topmost plate (or lies past the row)
+    for (int k = staged - 1; k >= 0; --k) {
+      if (__ballot(done != 0xFu) == 0) break;
+      const int4 r = s_rect[k];
+      const int x0 = uniform(r.x), y0 = uniform(r.y), x1 = uniform(r.z), y1 = uniform(r.w);
+      if (y < y0 || y >= y1) continue;
+      const unsigned hit = columns(x, x0, x1);
+      const unsigned fresh = hit & ~done;
+      if (fresh) {
+        const unsigned info = (unsigned)uniform((int)s_colour[k]);
+        const unsigned plate = info & 0xFFFFFFu, ink = (info >> 24 & 1u) ? 0xFFFFFFu : 0u;
+        const int v = (int)((unsigned)(y - y0) * by_s >> 16) - 1;                 // the glyph row: the same in every lane
+        const bool rows = v >= 0 && v < FH;
+        const unsigned char* text = s_text + k * RL_MAX_CHARS;
+        const unsigned char* glyph_row = s_font + (rows ? v : 0);
+        // no branch per pixel, so that the LDS reads of the four overlap: a pixel outside the plate works on clamped
+        // numbers and its result is dropped
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned a = (unsigned)min(max(x + j - x0, 0), 4095);
+          const int u = (int)(a * by_s >> 16) - 1;                                // a / s - 1
+          const unsigned uu = (unsigned)max(u, 0);
+          const unsigned ci = min(uu * by_cw >> 16, (unsigned)RL_MAX_CHARS - 1u); // uu / cw; below n inside the plate
+          const unsigned col = (uu - ci * (unsigned)cw) & 7u;
+          const int g = (int)text[ci] - font_first;
+          const bool has = g >= 0 && g < G;
+          const unsigned bits = glyph_row[(has ? g : 0) * FH];
+          const bool on = rows && u >= 0 && has && uu - ci * (unsigned)cw < (unsigned)FW && (bits >> (7u - col) & 1u);
+          px[j] = (fresh >> j & 1u) ? (on ? ink : plate) : px[j];
+        }
+      }
+      done |= hit;
+    }
+    const unsigned painted = done & ~past;
+    if (!painted) continue;
+    unsigned char* o = dst + (((long)b * H + y) * W + x) * 3;
+    if (painted == 0xFu && ((uintptr_t)o & 3u) == 0) {
+      unsigned* o4 = reinterpret_cast<unsigned*>(o);           // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+      o4[0] = px[0] | (px[1] << 24);
+      o4[1] = (px[1] >> 8) | (px[2] << 16);
+      o4[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (painted >> j & 1u) {
+          o[3 * j] = (unsigned char)px[j];
+          o[3 * j + 1] = (unsigned char)(px[j] >> 8);
+          o[3 * j + 2] = (unsigned char)(px[j] >> 16);
+        }
+    }
+  }
+}
+
 }  // namespace
+
+extern "C" int fod_render_labels(unsigned char* pictures, int B, int H, int W, const float* boxes, const int* labels,
+                                 int N, const int* idents, const float* scores, const unsigned char* names, int n_names,
+                                 int name_stride, const unsigned char* palette, int P, const unsigned char* font,
+                                 int font_first, int G, int FW, int FH, int scale, int thickness, hipStream_t stream) {
+  FOD_REQUIRE(thickness >= 1, "render_labels: thickness %d is below 1", thickness);
+  FOD_REQUIRE(N >= 0 && N <= RB_MAX_BOXES, "render_labels: %d labels per sample, not 0..%d", N, RB_MAX_BOXES);
+  FOD_REQUIRE(P >= 1, "render_labels: a palette of %d colours", P);
+  FOD_REQUIRE(H > 0 && W > 0 && (long)H >= 2L * thickness && (long)W >= 2L * thickness,
+              "render_labels: a %dx%d picture does not hold bars of thickness %d", H, W, thickness);
+  FOD_REQUIRE((long)3 * H * W <= INT_MAX, "render_labels: picture %dx%d is too large", H, W);
+  FOD_REQUIRE(B > 0 && B <= 65535, "render_labels: %d pictures, not 1..65535", B);
+  FOD_REQUIRE(scale >= 1 && scale <= 8, "render_labels: scale %d, not 1..8", scale);
+  FOD_REQUIRE(FW >= 1 && FW <= 8 && FH >= 1 && FH <= 16, "render_labels: a %dx%d font cell, not 1..8 x 1..16", FW, FH);
+  FOD_REQUIRE(font_first >= 0 && G >= 1 && font_first + (long)G <= 256,
+              "render_labels: %d glyphs from code %d on do not lie in 0..255", G, font_first);
+  FOD_REQUIRE(!names || (n_names >= 1 && n_names <= INT_MAX / RL_MAX_CHARS && name_stride >= 1 && name_stride <= RL_MAX_CHARS),
+              "render_labels: a name table of %d rows of %d bytes (rows >= 1, bytes 1..%d)", n_names, name_stride,
+              RL_MAX_CHARS);
+  FOD_REQUIRE(pictures && font && (N == 0 || (boxes && labels && palette)), "render_labels: null pointer");
+  const dim3 grid((W + RB_TILE_W - 1) / RB_TILE_W, (H + RB_TILE_H - 1) / RB_TILE_H, B);
+  FOD_REQUIRE(grid.y <= 65535, "render_labels: picture %dx%d is too tall", H, W);
+  if (N == 0 || !(idents || scores || names)) return FOD_OK;   // every text is empty: nothing is drawn
+  hipLaunchKernelGGL(render_labels_kernel, grid, dim3(RB_THREADS), 0, stream, pictures, H, W, boxes, labels, N, idents,
+                     scores, names, n_names, name_stride, palette, P, font, font_first, G, FW, FH, scale, thickness);
+  FOD_LAUNCH_CHECK();
+  return FOD_OK;
+}
 
 extern "C" int fod_render_boxes(const void* src, int src_is_u8, unsigned char* dst, int B, int L, int H, int W,
                                 long src_stride_b, long src_stride_l, const int* frame_idx, const float* mean,

@@ -506,6 +506,49 @@ def render_boxes(video, boxes, labels, *, frame_idx=None, mean=None, std=None, p
     return out
 
 
+def render_labels(pictures, boxes, labels, *, idents=None, scores=None, names=None, palette, font, font_first=32,
+                  font_width=5, scale=2, thickness=3):
+    """Captions on the pictures render_boxes wrote, in place and returned, in one launch (include/fod_ext.h,
+    fod_render_labels, states the map): pictures uint8 [B, H, W, 3]; boxes f32 [B, N, 4], labels i32 [B, N], palette
+    uint8 [P, 3] and thickness as render_boxes took them; idents i32 [B, N], scores f32 [B, N], names uint8 [n_names,
+    stride <= 32] -- each optional; font uint8 [G, FH] whose glyphs are `font_width` columns wide, for the codes from
+    `font_first` on -- all on the pictures' device.  There is no CPU fallback."""
+    who = "render_labels"
+    if not isinstance(pictures, torch.Tensor) or not pictures.is_cuda or pictures.dim() != 4 or pictures.shape[3] != 3 \
+            or pictures.dtype != torch.uint8 or not pictures.is_contiguous():
+        raise L.FodError(f"{who}: pictures must be a contiguous uint8 device tensor [B, H, W, 3] "
+                         "(the HIP path has no CPU fallback)")
+    b, h, w, _ = pictures.shape
+    operands = {"boxes": (boxes, torch.float32), "labels": (labels, torch.int32), "palette": (palette, torch.uint8),
+                "font": (font, torch.uint8)}
+    for name, t, dtype in (("idents", idents, torch.int32), ("scores", scores, torch.float32), ("names", names, torch.uint8)):
+        if t is not None:
+            operands[name] = (t, dtype)
+    for name, (t, dtype) in operands.items():
+        if not isinstance(t, torch.Tensor):
+            raise L.FodError(f"{who}: {name} must be a {dtype} device tensor")
+        _chk(t, f"{who}: {name}", dtype)
+        if t.device != pictures.device:
+            raise L.FodError(f"{who}: {name} lives on {t.device}, the pictures on {pictures.device}")
+    if boxes.dim() != 3 or boxes.shape[0] != b or boxes.shape[2] != 4 or tuple(labels.shape) != tuple(boxes.shape[:2]):
+        raise L.FodError(f"{who}: boxes {tuple(boxes.shape)} / labels {tuple(labels.shape)} are not [B, N, 4] / [B, N] "
+                         f"for {b} pictures")
+    for name in ("idents", "scores"):
+        if name in operands and tuple(operands[name][0].shape) != tuple(labels.shape):
+            raise L.FodError(f"{who}: {name} {tuple(operands[name][0].shape)} is not {tuple(labels.shape)}, one per label")
+    if palette.dim() != 2 or palette.shape[1] != 3 or palette.shape[0] < 1:
+        raise L.FodError(f"{who}: palette {tuple(palette.shape)} is not [P, 3]")
+    if font.dim() != 2 or font.numel() == 0:
+        raise L.FodError(f"{who}: font {tuple(font.shape)} is not [G, FH]")
+    if names is not None and (names.dim() != 2 or names.numel() == 0):
+        raise L.FodError(f"{who}: names {tuple(names.shape)} is not [n_names, stride]")
+    n_names, stride = (0, 0) if names is None else names.shape
+    call("fod_render_labels", ptr(pictures), b, h, w, ptr(boxes), ptr(labels), boxes.shape[1], ptr(idents), ptr(scores),
+         ptr(names), n_names, stride, ptr(palette), palette.shape[0], ptr(font), int(font_first), font.shape[0],
+         int(font_width), font.shape[1], int(scale), int(thickness), stream())
+    return pictures
+
+
 def render_attention(video, maps, frame_idx, colour_scale, *, mean=None, std=None, lut, gain=50.0, max_alpha=0.4,
                      out=None):
     """The maps of one detection per sample blended over their past frames: uint8 RGB [B, J, H, W, 3] in one launch

@@ -67,6 +67,18 @@ class Trainer:
         # gradient accumulation (set_accumulate): one optimizer update per this many loader items.  1: nothing changes
         self._accumulate = 1
         self._eager_accum, self._eager_pending = None, 0
+        # captions in the PNG files (set_captions).  None: coloured outlines only, as ever
+        self._captions = None
+
+    def set_captions(self, flag=True):
+        """Text in the pictures of `visualize_batch` (visualization.Captions; rasterised on the device by one more
+        launch per picture set): `_anno.png` carries the class name of every annotation from `category_dict`, `_pred.png`
+        "<query> <name> <score in percent>" on every prediction and the names on the annotations.  Off (the default):
+        the files are what they were.  (A method, not a constructor keyword: the constructor is the reference's plus
+        `ema`.)"""
+        from future_od.utils import visualization as V
+        self._captions = V.Captions(names=self._category_dict) if flag else None
+        return self
 
     def set_accumulate(self, n):
         """One optimizer update per `n` loader items (micro-batches), each normalised by its own number of boxes: the
@@ -365,9 +377,18 @@ class Trainer:
         if M > room:                                         # more queries than that: the best-scoring ones
             keep = best.topk(room, dim=1).indices.sort(dim=1).values
             pred_classes, pred_boxes = pred_classes.gather(1, keep), pred_boxes.gather(1, keep[..., None].expand(-1, -1, 4))
-        anno = V.render(video, anno_boxes, anno_classes, frame)
+        anno_captions = pred_captions = None
+        captions = getattr(self, "_captions", None)
+        if captions is not None:                             # annotations: the name alone (ident -1 and a NaN score are absent)
+            query = torch.arange(M, dtype=torch.int32, device=dev)[None].expand(B, M) if M <= room else keep.to(torch.int32)
+            shown = best if M <= room else best.gather(1, keep)
+            absent = anno_classes.new_full(anno_classes.shape, -1, dtype=torch.int32)
+            anno_captions = captions
+            pred_captions = captions.replace(ident=torch.cat([absent, query], dim=1),
+                                          scores=torch.cat([absent.float() * float("nan"), shown], dim=1))
+        anno = V.render(video, anno_boxes, anno_classes, frame, captions=anno_captions)
         pred = V.render(video, torch.cat([anno_boxes, pred_boxes], dim=1), torch.cat([anno_classes, pred_classes], dim=1),
-                        frame)
+                        frame, captions=pred_captions)
         anno, pred = anno.cpu(), pred.cpu()
         for b in range(B):
             for kind, picture in (("anno", anno[b]), ("pred", pred[b])):

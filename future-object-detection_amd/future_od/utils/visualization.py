@@ -13,8 +13,16 @@ kernel's bytes.
 pictures of a device clip (ops.render_attention, include/fod_ext.h: fod_render_attention), a torch form with the same
 bytes for CPU tensors.
 
-Not built: text or captions in the picture, filled or alpha-blended boxes, a thickness per box, bf16 sources, PNG
+Captions (`Captions`, the `captions=` argument of `render` and `render_detections`) write a box's index, class name and
+score on a plate above it (reference demo.ipynb: cv2.putText of every detection's index; visualize_wandb: "<idx>
+<category>" and the score): the text is composed and rasterised on the device by one more launch (ops.render_labels,
+include/fod_ext.h: fod_render_labels), so neither scores nor labels are read back; `label_text` and `draw_labels` are
+the CPU form with the same bytes, `FONT_5X7` the font.
+
+Not built: captions that avoid each other or stay inside their box, anti-aliased or proportional fonts, text that is
+not ASCII, text in `render_attention`'s overlays, filled or alpha-blended boxes, a thickness per box, bf16 sources, PNG
 compression tuning, drawing every frame of a clip to disk."""
+import copy
 import os
 import struct
 import zlib
@@ -86,16 +94,264 @@ def _device_constants(device):
     return hit
 
 
-def render(video, boxes, labels, frame_idx=None, thickness=3, palette=COLOURS):
+# ---- captions: the text a box carries, a 5x7 font, the CPU form of include/fod_ext.h: fod_render_labels ------------------
+LABEL_MAX_CHARS = 32                     # the text limit include/fod_ext.h states for fod_render_labels
+
+# The glyphs of the codes 32..126, seven rows of five columns each, top row first (profiles/font_5x7.txt shows them
+# enlarged; tools/font_art.py writes that file).  Drawn for this project.
+_GLYPHS = (
+    "..... ..... ..... ..... ..... ..... .....",  # space
+    "..#.. ..#.. ..#.. ..#.. ..#.. ..... ..#..",  # !
+    ".#.#. .#.#. .#.#. ..... ..... ..... .....",  # "
+    ".#.#. .#.#. ##### .#.#. ##### .#.#. .#.#.",  # #
+    "..#.. .#### #.#.. .###. ..#.# ####. ..#..",  # $
+    "##... ##..# ...#. ..#.. .#... #..## ...##",  # %
+    ".##.. #..#. #.#.. .#... #.#.# #..#. .##.#",  # &
+    "..#.. ..#.. ..#.. ..... ..... ..... .....",  # '
+    "...#. ..#.. .#... .#... .#... ..#.. ...#.",  # (
+    ".#... ..#.. ...#. ...#. ...#. ..#.. .#...",  # )
+    "..... ..#.. #.#.# .###. #.#.# ..#.. .....",  # *
+    "..... ..#.. ..#.. ##### ..#.. ..#.. .....",  # +
+    "..... ..... ..... ..... .##.. ..#.. .#...",  # ,
+    "..... ..... ..... ##### ..... ..... .....",  # -
+    "..... ..... ..... ..... ..... .##.. .##..",  # .
+    "..... ....# ...#. ..#.. .#... #.... .....",  # /
+    ".###. #...# #..## #.#.# ##..# #...# .###.",  # 0
+    "..#.. .##.. ..#.. ..#.. ..#.. ..#.. .###.",  # 1
+    ".###. #...# ....# ...#. ..#.. .#... #####",  # 2
+    "##### ...#. ..#.. ...#. ....# #...# .###.",  # 3
+    "...#. ..##. .#.#. #..#. ##### ...#. ...#.",  # 4
+    "##### #.... ####. ....# ....# #...# .###.",  # 5
+    "..##. .#... #.... ####. #...# #...# .###.",  # 6
+    "##### ....# ...#. ..#.. .#... .#... .#...",  # 7
+    ".###. #...# #...# .###. #...# #...# .###.",  # 8
+    ".###. #...# #...# .#### ....# ...#. .##..",  # 9
+    "..... .##.. .##.. ..... .##.. .##.. .....",  # :
+    "..... .##.. .##.. ..... .##.. ..#.. .#...",  # ;
+    "...#. ..#.. .#... #.... .#... ..#.. ...#.",  # <
+    "..... ..... ##### ..... ##### ..... .....",  # =
+    ".#... ..#.. ...#. ....# ...#. ..#.. .#...",  # >
+    ".###. #...# ....# ...#. ..#.. ..... ..#..",  # ?
+    ".###. #...# ....# .##.# #.#.# #.#.# .###.",  # @
+    ".###. #...# #...# #...# ##### #...# #...#",  # A
+    "####. #...# #...# ####. #...# #...# ####.",  # B
+    ".###. #...# #.... #.... #.... #...# .###.",  # C
+    "###.. #..#. #...# #...# #...# #..#. ###..",  # D
+    "##### #.... #.... ####. #.... #.... #####",  # E
+    "##### #.... #.... ####. #.... #.... #....",  # F
+    ".###. #...# #.... #.### #...# #...# .####",  # G
+    "#...# #...# #...# ##### #...# #...# #...#",  # H
+    ".###. ..#.. ..#.. ..#.. ..#.. ..#.. .###.",  # I
+    "..### ...#. ...#. ...#. ...#. #..#. .##..",  # J
+    "#...# #..#. #.#.. ##... #.#.. #..#. #...#",  # K
+    "#.... #.... #.... #.... #.... #.... #####",  # L
+    "#...# ##.## #.#.# #.#.# #...# #...# #...#",  # M
+    "#...# #...# ##..# #.#.# #..## #...# #...#",  # N
+    ".###. #...# #...# #...# #...# #...# .###.",  # O
+    "####. #...# #...# ####. #.... #.... #....",  # P
+    ".###. #...# #...# #...# #.#.# #..#. .##.#",  # Q
+    "####. #...# #...# ####. #.#.. #..#. #...#",  # R
+    ".#### #.... #.... .###. ....# ....# ####.",  # S
+    "##### ..#.. ..#.. ..#.. ..#.. ..#.. ..#..",  # T
+    "#...# #...# #...# #...# #...# #...# .###.",  # U
+    "#...# #...# #...# #...# #...# .#.#. ..#..",  # V
+    "#...# #...# #...# #.#.# #.#.# #.#.# .#.#.",  # W
+    "#...# #...# .#.#. ..#.. .#.#. #...# #...#",  # X
+    "#...# #...# #...# .#.#. ..#.. ..#.. ..#..",  # Y
+    "##### ....# ...#. ..#.. .#... #.... #####",  # Z
+    ".###. .#... .#... .#... .#... .#... .###.",  # [
+    "..... #.... .#... ..#.. ...#. ....# .....",  # \
+    ".###. ...#. ...#. ...#. ...#. ...#. .###.",  # ]
+    "..#.. .#.#. #...# ..... ..... ..... .....",  # ^
+    "..... ..... ..... ..... ..... ..... #####",  # _
+    ".#... ..#.. ...#. ..... ..... ..... .....",  # `
+    "..... ..... .###. ....# .#### #...# .####",  # a
+    "#.... #.... #.##. ##..# #...# #...# ####.",  # b
+    "..... ..... .###. #.... #.... #...# .###.",  # c
+    "....# ....# .##.# #..## #...# #...# .####",  # d
+    "..... ..... .###. #...# ##### #.... .###.",  # e
+    "..##. .#..# .#... ###.. .#... .#... .#...",  # f
+    "..... .#### #...# #...# .#### ....# .###.",  # g
+    "#.... #.... #.##. ##..# #...# #...# #...#",  # h
+    "..#.. ..... .##.. ..#.. ..#.. ..#.. .###.",  # i
+    "...#. ..... ..##. ...#. ...#. #..#. .##..",  # j
+    "#.... #.... #..#. #.#.. ##... #.#.. #..#.",  # k
+    ".##.. ..#.. ..#.. ..#.. ..#.. ..#.. .###.",  # l
+    "..... ..... ##.#. #.#.# #.#.# #...# #...#",  # m
+    "..... ..... #.##. ##..# #...# #...# #...#",  # n
+    "..... ..... .###. #...# #...# #...# .###.",  # o
+    "..... ####. #...# #...# ####. #.... #....",  # p
+    "..... .#### #...# #...# .#### ....# ....#",  # q
+    "..... ..... #.##. ##..# #.... #.... #....",  # r
+    "..... ..... .#### #.... .###. ....# ####.",  # s
+    ".#... .#... ###.. .#... .#... .#..# ..##.",  # t
+    "..... ..... #...# #...# #...# #..## .##.#",  # u
+    "..... ..... #...# #...# #...# .#.#. ..#..",  # v
+    "..... ..... #...# #...# #.#.# #.#.# .#.#.",  # w
+    "..... ..... #...# .#.#. ..#.. .#.#. #...#",  # x
+    "..... #...# #...# #...# .#### ....# .###.",  # y
+    "..... ..... ##### ...#. ..#.. .#... #####",  # z
+    "...#. ..#.. ..#.. .#... ..#.. ..#.. ...#.",  # {
+    "..#.. ..#.. ..#.. ..#.. ..#.. ..#.. ..#..",  # |
+    ".#... ..#.. ..#.. ...#. ..#.. ..#.. .#...",  # }
+    "..... ..... .#... #.#.# ...#. ..... .....",  # ~
+)
+# uint8 [95, 7]: one byte per glyph row, column col in bit 7 - col (the glyph in bits 7..3, the low three bits zero)
+FONT_5X7 = torch.tensor([[sum(128 >> col for col, mark in enumerate(row) if mark == "#") for row in glyph.split()]
+                         for glyph in _GLYPHS], dtype=torch.uint8)
+
+
+def encode_names(names):
+    """Class names -> the name table the captions read, uint8 [P, stride]: row i holds the bytes of names[i] (a list,
+    or a dict {class id: name} as the loaders' category_dict; an id that is missing gives an empty row), cut at
+    LABEL_MAX_CHARS and padded with 0; stride is the longest row's length (at least 1)."""
+    if isinstance(names, dict):
+        names = [names.get(i, "") for i in range(max(names, default=-1) + 1)]
+    rows = [str(name).encode("utf-8")[:LABEL_MAX_CHARS] for name in names]
+    stride = max([len(row) for row in rows] + [1])
+    table = torch.zeros((max(len(rows), 1), stride), dtype=torch.uint8)
+    for i, row in enumerate(rows):
+        table[i, :len(row)] = torch.tensor(list(row), dtype=torch.uint8)
+    return table
+
+
+def label_text(ident, label, score, names):
+    """The bytes of one caption (include/fod_ext.h, fod_render_labels): the parts that are present joined by one space,
+    cut at LABEL_MAX_CHARS.  `ident` (None, or an integer: present from 0 on) gives its decimal digits; `names` (None, or
+    uint8 [n_names, stride]) gives the bytes of row `label` up to its first 0 where 0 <= label < n_names; `score` (None,
+    or a number: present unless NaN) gives two digits of min(99, max(0, trunc(score * 100))), the product in f32."""
+    parts = []
+    if ident is not None and int(ident) >= 0:
+        parts.append(str(int(ident)).encode())
+    if names is not None and 0 <= int(label) < names.shape[0]:
+        parts.append(bytes(names[int(label)].tolist()).split(b"\0")[0])
+    if score is not None:
+        product = torch.as_tensor(score).detach().to("cpu", torch.float32) * torch.tensor(100.0, dtype=torch.float32)
+        if not bool(torch.isnan(product)):
+            parts.append(b"%02d" % int(product.clamp(0.0, 99.0)))
+    return b" ".join(parts)[:LABEL_MAX_CHARS]
+
+
+def draw_labels(picture, boxes, labels, idents=None, scores=None, names=None, palette=None, font=FONT_5X7,
+                font_first=32, font_width=5, scale=2, thickness=3):
+    """Captions of one sample on the uint8 picture [H, W, 3] that holds its outlines, in place and returned: the CPU
+    form of fod_render_labels (include/fod_ext.h states the map).  boxes f32 [N, 4], labels [N], idents [N] / scores
+    [N] / names uint8 [n_names, stride] or None, palette uint8 [P, 3] (None: COLOURS as bytes), font uint8 [G, FH] with
+    glyphs `font_width` columns wide for the codes from `font_first` on.  A painter's loop: label n's text on an opaque
+    plate of its class colour above its box (inside it at the top border), black or white ink by the plate's
+    brightness; later plates cover earlier ones."""
+    H, W, _ = picture.shape
+    t, s, FW = int(thickness), int(scale), int(font_width)
+    G, FH = font.shape
+    if t < 1 or H < 2 * t or W < 2 * t:
+        raise ValueError(f"draw_labels: a {H}x{W} picture does not hold bars of thickness {thickness}")
+    if not (1 <= s <= 8 and 1 <= FW <= 8 and 1 <= FH <= 16 and font_first >= 0 and font_first + G <= 256):
+        raise ValueError(f"draw_labels: scale {s} (1..8), a {FW}x{FH} font cell (1..8 x 1..16) or {G} glyphs from code "
+                         f"{font_first} on (inside 0..255)")
+    palette = to_bytes(COLOURS) if palette is None else palette
+    boxes = boxes.detach().to(torch.float32)
+    cw, Hp = FW + 1, (FH + 2) * s
+    shifts = 7 - torch.arange(FW)
+    for n in range(boxes.shape[0]):
+        label = int(labels[n])
+        if not 0 <= label < palette.shape[0] or bool(torch.isnan(boxes[n]).any()):
+            continue
+        text = label_text(None if idents is None else idents[n], label, None if scores is None else scores[n], names)
+        if not text:
+            continue
+        Wp = (len(text) * cw + 1) * s
+        Lf, Tp = int(boxes[n, 0].clamp(t, W - t)), int(boxes[n, 1].clamp(t, H - t))
+        x0, y0 = Lf - t, Tp - t - Hp
+        if y0 < 0:
+            y0 = Tp
+        x0, y0 = max(min(x0, W - Wp), 0), max(min(y0, H - Hp), 0)
+        mask = torch.zeros((FH + 2, len(text) * cw + 1), dtype=torch.bool)
+        for i, code in enumerate(text):
+            if font_first <= code < font_first + G:
+                rows = font[code - font_first].to(torch.int64)
+                mask[1:FH + 1, 1 + i * cw:1 + i * cw + FW] = (rows[:, None] >> shifts[None, :] & 1).bool()
+        mask = mask.repeat_interleave(s, dim=0).repeat_interleave(s, dim=1)[:H - y0, :W - x0]
+        plate = palette[label].to(torch.int64)
+        dark = int(299 * plate[0] + 587 * plate[1] + 114 * plate[2]) < 128000
+        ink = torch.full((3,), 255 if dark else 0, dtype=torch.uint8)
+        picture[y0:y0 + Hp, x0:x0 + Wp] = torch.where(mask[..., None], ink, plate.to(torch.uint8))
+    return picture
+
+
+class Captions:
+    """What `render` / `render_detections` write on a box, and how.  names: the class names (a list, a dict
+    {class id: name}, or an `encode_names` table) or None; ident: None, "slot" -- the label's position n in its sample,
+    which for `render_detections` is the slot that `render_attention(..., slot=n)` takes --, "query" (`render_detections`
+    only: det["query"]) or an integer tensor [B, N]; scores: False, True (`render_detections` only: det["scores"]) or a
+    float tensor [B, N]; scale: 1..8, the size of a font pixel; font: uint8 [G, FH] for the codes from `font_first`
+    on, `font_width` columns wide.  The tables are copied to a device once, at the first picture rendered there."""
+
+    def __init__(self, names=None, ident=None, scores=False, scale=2, font=FONT_5X7, font_first=32, font_width=5):
+        if not (ident is None or isinstance(ident, torch.Tensor) or ident in ("slot", "query")):
+            raise ValueError(f"Captions: ident is None, 'slot', 'query' or a tensor, not {ident!r}")
+        if not (isinstance(scores, (bool, torch.Tensor)) or scores is None):
+            raise ValueError(f"Captions: scores is a flag or a tensor, not {scores!r}")
+        if names is not None and not isinstance(names, torch.Tensor):
+            names = encode_names(names)
+        self.names, self.ident, self.scores = names, ident, (False if scores is None else scores)
+        self.scale, self.font, self.font_first, self.font_width = int(scale), font, int(font_first), int(font_width)
+        self._on = {}
+
+    def replace(self, ident, scores):
+        """A copy with another `ident` and `scores`; it shares the tables already on a device."""
+        other = copy.copy(self)
+        other.ident, other.scores = ident, scores
+        return other
+
+    def tables(self, device):
+        """(names or None, font) on `device`, made once."""
+        hit = self._on.get(device)
+        if hit is None:
+            hit = self._on[device] = (None if self.names is None else self.names.to(device, torch.uint8).contiguous(),
+                                      self.font.to(device, torch.uint8).contiguous())
+        return hit
+
+    def operands(self, labels, det=None):
+        """(idents or None, scores or None) for `labels` [B, N], on its device; `det`: what predict() returned."""
+        ident, scores = self.ident, self.scores
+        if isinstance(ident, str):
+            if ident == "query":
+                if det is None:
+                    raise ValueError("Captions: ident='query' needs the detections of render_detections")
+                ident = det["query"]
+            else:
+                ident = torch.arange(labels.shape[1], dtype=torch.int32, device=labels.device)[None].expand(labels.shape)
+        if scores is True:
+            if det is None:
+                raise ValueError("Captions: scores=True needs the detections of render_detections")
+            scores = det["scores"]
+        elif scores is False:
+            scores = None
+        for name, t in (("ident", ident), ("scores", scores)):
+            if t is not None and tuple(t.shape) != tuple(labels.shape):
+                raise ValueError(f"Captions: {name} {tuple(t.shape)} is not {tuple(labels.shape)}, one per label")
+        return ident, scores
+
+
+def render(video, boxes, labels, frame_idx=None, thickness=3, palette=COLOURS, captions=None):
     """The frame `frame_idx[b]` (None: frame 0; negative: from the end; clamped into the clip) of every sample of
     `video` [B, L, 3, H, W] -- f32 normalised, or raw uint8 -- with the outlines of `boxes` [B, N, 4] (xyxy pixels)
     -> uint8 [B, H, W, 3] on the clip's device.  Box n is drawn where 0 <= labels[b, n] < len(palette) (and no
     coordinate is NaN) in the colour palette[label]; `palette` is float [P, 3] on the 0..1 scale and becomes bytes by
     `to_bytes` (COLOURS: 0, 63, 127, 191, 255).  `labels` may be i64.  A device clip is one launch of ops.render_boxes;
-    CPU tensors go through `draw_boxes` per sample and give the same bytes."""
+    CPU tensors go through `draw_boxes` per sample and give the same bytes.  `captions` (a `Captions`, or None for
+    outlines only) writes its text above every drawn box: one more launch (ops.render_labels) on a device clip,
+    `draw_labels` on CPU tensors, the same bytes."""
+    return _render(video, boxes, labels, frame_idx, thickness, palette, captions, None)
+
+
+def _render(video, boxes, labels, frame_idx, thickness, palette, captions, det):
     if video.dim() != 5 or video.shape[2] != 3 or video.dtype not in (torch.float32, torch.uint8):
         raise ValueError(f"render: video must be f32 or uint8 [B, L, 3, H, W], got {video.dtype} {tuple(video.shape)}")
     B, L = video.shape[:2]
+    idents = scores = None
+    if captions is not None:
+        idents, scores = captions.operands(labels, det)
     if video.is_cuda:
         from future_od.native import ops
         colours, mean, std = _device_constants(video.device)
@@ -103,9 +359,18 @@ def render(video, boxes, labels, frame_idx=None, thickness=3, palette=COLOURS):
             colours = to_bytes(palette.to(video.device, torch.float32)).contiguous()
         if frame_idx is not None:
             frame_idx = frame_idx.to(video.device, torch.int32).contiguous()
-        return ops.render_boxes(video, boxes.to(video.device, torch.float32).contiguous(),
-                                labels.to(video.device, torch.int32).contiguous(), frame_idx=frame_idx, mean=mean,
-                                std=std, palette=colours, thickness=thickness)
+        boxes = boxes.to(video.device, torch.float32).contiguous()
+        labels = labels.to(video.device, torch.int32).contiguous()
+        pictures = ops.render_boxes(video, boxes, labels, frame_idx=frame_idx, mean=mean, std=std, palette=colours,
+                                    thickness=thickness)
+        if captions is None:
+            return pictures
+        names, font = captions.tables(video.device)
+        return ops.render_labels(pictures, boxes, labels,
+                                 idents=None if idents is None else idents.to(video.device, torch.int32).contiguous(),
+                                 scores=None if scores is None else scores.to(video.device, torch.float32).contiguous(),
+                                 names=names, palette=colours, font=font, font_first=captions.font_first,
+                                 font_width=captions.font_width, scale=captions.scale, thickness=thickness)
     u8 = video.dtype == torch.uint8
     palette = palette.to(torch.float32)
     colours = to_bytes(palette).to(torch.float32) if u8 else palette
@@ -116,18 +381,24 @@ def render(video, boxes, labels, frame_idx=None, thickness=3, palette=COLOURS):
         keep = (labels[b] >= 0) & (labels[b] < palette.shape[0])
         image = video[b, f].to(torch.float32) if u8 else revert_imagenet_normalization(video[b, f])
         image = draw_boxes(image, boxes[b][keep], colours[labels[b][keep].long()], thickness)
-        out.append((image.to(torch.uint8) if u8 else to_bytes(image)).permute(1, 2, 0))
+        picture = (image.to(torch.uint8) if u8 else to_bytes(image)).permute(1, 2, 0).contiguous()
+        if captions is not None:
+            draw_labels(picture, boxes[b], labels[b], None if idents is None else idents[b],
+                        None if scores is None else scores[b], captions.names, to_bytes(palette), captions.font,
+                        captions.font_first, captions.font_width, captions.scale, thickness)
+        out.append(picture)
     return torch.stack(out).contiguous()
 
 
-def render_detections(video, det, min_score=0.5, frame_idx=None, thickness=3, palette=COLOURS):
+def render_detections(video, det, min_score=0.5, frame_idx=None, thickness=3, palette=COLOURS, captions=None):
     """`render` of what `predict()` returns ({"scores" [B, K], "labels" [B, K], "boxes" [B, K, 4], "count" [B]}): the
     slots that hold a detection (index < count) with a score of at least `min_score`.  A few tiny torch ops on the
-    tensors' device, no read-back."""
+    tensors' device, no read-back.  With `captions`, ident="slot" numbers every box with its position k in `det` --
+    what `render_attention(..., slot=k)` takes --, ident="query" prints det["query"], scores=True det["scores"]."""
     scores, labels = det["scores"], det["labels"]
     slot = torch.arange(labels.shape[1], device=labels.device)
     hidden = (scores < min_score) | (slot[None, :] >= det["count"][:, None])
-    return render(video, det["boxes"], labels.masked_fill(hidden, -1), frame_idx, thickness, palette)
+    return _render(video, det["boxes"], labels.masked_fill(hidden, -1), frame_idx, thickness, palette, captions, det)
 
 
 # uint8 [256, 3], a diverging blue - white - red ramp by an integer rule: entry i is (2i, 2i, 255) for i <= 127 and

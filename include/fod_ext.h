@@ -163,6 +163,48 @@ int fod_render_attention(const void* src, int src_is_u8, unsigned char* dst, int
                          const float* maps, int h, int w, long map_stride_b, long map_stride_j,
                          const float* colour_scale, const unsigned char* lut, float gain, float max_alpha,
                          fod_stream_t stream);
+/* Visualisation: captions -- index, class name and score of every drawn box as text on a plate above it -- painted IN
+ * PLACE on the uint8 [B][H][W][3] pictures fod_render_boxes wrote, in ONE launch (the reference's notebook writes every
+ * detection's index with cv2.putText on the host; its W&B boxes carry "<idx> <category>" and a score).  The text is
+ * composed and rasterised by the kernel: nothing is read back.  future_od/utils/visualization.py (label_text,
+ * draw_labels) is the CPU form.  Integer arithmetic throughout, except the one f32 product of the score.
+ *   boxes f32 [B][N][4], labels i32 [B][N], palette DEVICE uint8 [P][3], thickness: as handed to fod_render_boxes.
+ *        Label n of sample b is DRAWN iff box n is: 0 <= label < P and no coordinate is NaN.  Lf and Tp are that
+ *        function's integers (clamped to [t, W - t] / [t, H - t] in f32, then truncated; t = thickness).
+ *   idents i32 [B][N], scores f32 [B][N], names uint8 [n_names][name_stride] (name_stride <= 32): each may be NULL.
+ *   font: DEVICE uint8 [G][FH], one byte per glyph row; the glyph of character code c is row c - font_first, column
+ *        col of a row is bit 7 - col (the most significant bit is leftmost); 1 <= FW <= 8, 1 <= FH <= 16.  A code
+ *        outside [font_first, font_first + G) draws as a blank cell.
+ * Text: at most FOD_LABEL_MAX_CHARS = 32 bytes (a number: this header declares no constants) -- the parts that are
+ * PRESENT, joined by one space (0x20), then cut at 32:
+ *   the decimal digits of ident (no sign, no padding), present iff idents is given and ident >= 0;
+ *   the bytes of names[label] up to its first 0 (a row without a 0 is name_stride bytes long), present iff names is
+ *        given and label < n_names -- present also when it is empty, so its space is kept;
+ *   two decimal digits of pct = min(99, max(0, trunc(score * 100.f))), present iff scores is given and the score is not
+ *        NaN; the product is one f32 multiplication, +inf gives 99, 0.07 gives "07".
+ * An empty text draws nothing.  Geometry, with s = scale, n = the number of characters:
+ *   Wp = (n * (FW + 1) + 1) * s,  Hp = (FH + 2) * s
+ *   x0 = Lf - t,  y0 = Tp - t - Hp;  if y0 < 0 then y0 = Tp (the caption moves inside the box)
+ *   x0 = max(min(x0, W - Wp), 0),  y0 = max(min(y0, H - Hp), 0)
+ * The plate is rows [y0, y0 + Hp) x columns [x0, x0 + Wp), clipped to the picture.  For a plate pixel (x, y):
+ *   u = (x - x0) / s - 1,  v = (y - y0) / s - 1   (integer division of non-negative numbers)
+ * and the pixel is INK iff u >= 0, 0 <= v < FH, u % (FW + 1) < FW, and bit 7 - u % (FW + 1) of row v of the glyph of
+ * character u / (FW + 1) is set; any other plate pixel takes the plate colour.  The plate is opaque in palette[label];
+ * with lum = 299 R + 587 G + 114 B of it the ink is black (0, 0, 0) if lum >= 128000 and white (255, 255, 255) otherwise.
+ * Painter's order: among the plates that cover a pixel the HIGHEST n wins, plate and ink together.  Pixels outside
+ * every plate are neither read nor written, so all captions lie above all outlines; every written byte has exactly one
+ * writer, no atomics.  N == 0, or idents, scores and names all NULL, draws nothing (no launch).
+ * FOD_ERR_ARG before any launch: thickness < 1; H or W below 2 * thickness; N < 0 or N > 1024; P < 1; scale outside
+ * 1..8; FW outside 1..8; FH outside 1..16; font_first < 0, G < 1 or font_first + G > 256 (codes are bytes); names with
+ * n_names < 1 (or above INT_MAX / 32) or name_stride outside 1..32; a NULL pictures or font; NULL boxes, labels or palette with N > 0; B outside
+ * 1..65535.
+ * Every block reads each label (up to 28 B and its name) and writes 3 B per plate pixel of its tile; dword stores where
+ * four consecutive pixels of a row are all painted and their address allows, byte stores otherwise (no alignment is
+ * required of any pointer). */
+int fod_render_labels(unsigned char* pictures, int B, int H, int W, const float* boxes, const int* labels, int N,
+                      const int* idents, const float* scores, const unsigned char* names, int n_names, int name_stride,
+                      const unsigned char* palette, int P, const unsigned char* font, int font_first, int G, int FW,
+                      int FH, int scale, int thickness, fod_stream_t stream);
 
 #ifdef __cplusplus
 }
