@@ -6,7 +6,10 @@ a partial result parked in bf16 does not (tests/test_exact_cases_cpu.py shows it
 non-zero integers (tests/exact_cases.py): every product and every partial sum in an f32 accumulator is an exact integer in
 any order, under any split and any interleaving of atomics, so each result must EQUAL the float64 reference rounded once to
 the output dtype -- torch.equal on the full tensor, no tolerance, no element exempted.  Every case sets its knobs, asks the
-library which kernel the call is about to take and holds that against the table before it runs."""
+library which kernel the call is about to take and holds that against the table before it runs.
+
+At the end of the file: the fused bottleneck and the forward of the fused projection + add + norm, on the operand profiles
+of tests/fused_exact_cases.py."""
 import contextlib
 
 import pytest
@@ -302,3 +305,118 @@ def test_one_flipped_operand_element_changes_exactly_its_products(knobs):
     msg = E.mismatch(dw, E.expected(p.outs["dw_zeroed"]), "flipped g")
     assert msg is not None and f"{K2}/{N1 * K2} elements differ" in msg and f"rows {N1 - 1}..{N1 - 1} x columns 0..{K2 - 1}" in msg, msg
     exact(dw, p.outs["dw_zeroed"]._replace(pre=(g.double().t() @ x.double()) * rs.double()[:, None]), "the gradient of the flipped operand")
+
+
+# ================================================================================================ the fused kernels
+# tests/fused_exact_cases.py: three operand profiles, each with ONE dense stage and two thin ones (signed gathers), for which
+# the two bf16 intermediates of the fused bottleneck are bf16 numbers before their rounding -- the whole block must EQUAL the
+# float64 reference rounded once.  test_fused_frozen_bottleneck_matches_the_layer_by_layer_path (Gaussian magnitudes, the BN
+# folding, 2e-2 of the span) stays as it is; tests/test_exact_cases_cpu.py shows what that bound lets through.
+import fused_exact_cases as FX                       # noqa: E402
+
+SENTINEL = -7.0                                      # no output of a block that ends in a relu
+
+
+def _bnk_launch(o, shape):
+    """ops.bottleneck_fused_fwd into the middle of a larger buffer: (result, buffer); guard images of the sentinel around it."""
+    n, h, w = shape
+    buf = torch.full((n + 2, h, w, 256), SENTINEL, dtype=torch.bfloat16, device=DEV)
+    got = ops.bottleneck_fused_fwd(o["x"], o["w1"], o["b1"], o["w2"], o["b2"], o["w3"], o["b3"], o["wd"], o["bd"], out=buf[1:-1])
+    assert got.data_ptr() == buf[1].data_ptr()
+    return got, buf
+
+
+def _guards_intact(buf, what):
+    guards = torch.stack((buf[0], buf[-1])).cpu()
+    assert bool((guards == SENTINEL).all()), f"{what}: {int((guards != SENTINEL).sum())} elements of the guard images were written"
+
+
+def test_the_exact_bottleneck_weights_are_in_the_layout_prep_conv_produces():
+    """[Cout][kh][kw][Cin]: prep_conv (no scale) of the OIHW channels_last parameter that holds the same taps gives the tensor
+    the exact cases hand to the kernel."""
+    o = FX.problem("s2", 64, (1, 1, 1)).ops
+    Fn.PREP.clear()
+    for name in ("w1", "w2", "w3", "wd"):
+        w = o[name].float().view(o[name].shape[0], *((3, 3) if name == "w2" else (1, 1)), -1)          # [Cout, kh, kw, Cin]
+        oihw = torch.nn.Parameter(w.permute(0, 3, 1, 2).contiguous(memory_format=torch.channels_last).to(DEV))
+        prep = Fn.prep_conv(oihw, torch.bfloat16, None, False)
+        assert torch.equal(prep.cpu().reshape(o[name].shape), o[name]), name
+
+
+@pytest.mark.parametrize("c", **FX.bnk_params())
+def test_fused_bottleneck_is_exact(knobs, c):
+    """Both kernels of csrc/bottleneck_fused.hip, both shortcut forms, the integer weights and shifts handed to
+    ops.bottleneck_fused_fwd directly (FrozenBatchNorm2d's rsqrt(var + eps) scale is not exactly 1): torch.equal on the full
+    tensor; the guard images around the output are untouched (partial tiles must not store past the image).  On the
+    persistent-walk shapes the device's CU count must give the walk the table intends (tiles per workgroup, a short last
+    range, ranges that start mid-image), and a second launch on the same stream -- it meets the LDS and the ring as the first
+    left them -- is compared too."""
+    knobs(FOD_BNK_VERSION=c.version)
+    p = FX.bnk_problem(c)
+    o = {k: dev(t) for k, t in p.ops.items()}
+    walk = FX.WALK.get(c.purpose)
+    if walk:
+        assert c.version == "4"
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        w = FX.walk_of(c.shape, cus)
+        assert w["per"] == walk["per"] and w["busy"] <= w["grid"] == cus, (cus, w)
+        if walk["short_last"]:
+            assert 0 < w["last"] < w["per"] and w["mid_image"], (cus, w)
+        else:
+            assert w["busy"] < w["grid"], (cus, w)               # workgroups that find no tiles and leave at once
+    runs = [_bnk_launch(o, c.shape) for _ in range(2 if walk else 1)]
+    for i, (got, buf) in enumerate(runs):
+        msg = E.mismatch(got, p.want, f"{FX.bnk_id(c)} launch {i}")
+        assert msg is None, msg
+        _guards_intact(buf, FX.bnk_id(c))
+
+
+@pytest.mark.parametrize("cin", FX.CINS)
+def test_fused_bottleneck_one_flipped_input_changes_exactly_its_outputs(knobs, cin):
+    """(1, 12, 60), the dense 3x3 (s2): the sign of ONE x element flipped at pixel (5, 29), the corner four tiles share.  The
+    result equals the reference of the flipped input, and the set of output elements that changed on the device is the
+    reference's: the 3 x 3 neighbourhood through all three stages, nothing else -- a halo that a neighbouring tile read stale,
+    or a tile that did not read it again, shows here."""
+    knobs(FOD_BNK_VERSION="4")
+    shape = (1, 12, 60)
+    p = FX.problem("s2", cin, shape)
+    k = int(p.ops["w1"].float()[0].abs().argmax())               # the input channel conv1's output channel 0 reads
+    flipped = dict(p.ops, x=p.ops["x"].clone())
+    flipped["x"][0, 5, 29, k] = -flipped["x"][0, 5, 29, k]
+    want_f = FX.rounded(FX.forward(flipped))
+    want_changed = want_f != p.want
+    where = want_changed.any(-1)[0].nonzero()
+    assert {tuple(t) for t in where.tolist()} == {(y, x) for y in (4, 5, 6) for x in (28, 29, 30)}        # all four tiles
+    base, buf0 = _bnk_launch({n: dev(t) for n, t in p.ops.items()}, shape)
+    got, buf1 = _bnk_launch({n: dev(t) for n, t in flipped.items()}, shape)
+    for t, want, what in ((base, p.want, "as in the table"), (got, want_f, "one x element flipped")):
+        msg = E.mismatch(t, want, f"bnk-s2-cin{cin} {what}")
+        assert msg is None, msg
+    assert torch.equal((got != base).cpu(), want_changed)
+    _guards_intact(buf0, "base"), _guards_intact(buf1, "flipped")
+
+
+@pytest.mark.parametrize("c", **FX.lan_params())
+def test_fused_linear_add_norm_sum_and_mean_are_exact(c):
+    """fod_linear_add_norm_fwd on +-1 operands with integer bias and x: the stored sum EQUALS a w^T + bias + x rounded once to
+    bf16, the row mean -- (a sum of 256 integers) * 2^-8 -- equals the float64 mean bit for bit; ragged first and last groups
+    of sixteen rows, with and without bias, plain and THEN form.  rstd, y and the THEN projection are not exact (rsqrt, Gaussian
+    gamma / beta / weights): they keep the bounds of test_fused_linear_add_norm_forward and
+    test_fused_linear_add_norm_then_next_projection, against the exact sum."""
+    import torch.nn.functional as F
+    from test_kernels_gpu import check
+    p = FX.lan_problem(c.M, c.bias)
+    o = {k: dev(t) for k, t in p.ops.items()}
+    res = ops.linear_add_norm_fwd(o["a"], o["w"], o["bias"], o["x"], o["gamma"], o["beta"],
+                                  **(dict(then_w=o["then_w"], then_bias=o["then_b"]) if c.then else {}))
+    y, s, mean, rstd = res[:4]
+    msg = E.mismatch(s, p.want_sum, f"{FX.lan_id(c)} sum")
+    assert msg is None, msg
+    msg = E.mismatch(mean, p.want_mean, f"{FX.lan_id(c)} mean")
+    assert msg is None, msg
+    assert torch.allclose(rstd.cpu(), (p.sum.var(-1, unbiased=False) + 1e-5).rsqrt().float(), rtol=1e-4)
+    ref = F.layer_norm(p.sum, (256,), p.ops["gamma"].double(), p.ops["beta"].double(), 1e-5)
+    check(y, ref.float(), torch.bfloat16, 4, FX.lan_id(c))
+    if c.then:
+        q_ref = ops.gemm_nt(y, o["then_w"], shift=o["then_b"])
+        assert float((res[4].float() - q_ref.float()).abs().max()) <= 2.0 ** -7 * float(q_ref.float().abs().max())
