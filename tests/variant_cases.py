@@ -1,6 +1,7 @@
 """The selectable kernel variants and the smallest shapes that reach them: ONE table, read by tests/test_dispatch_cpu.py
 (the route the library reports for every case, under the case's knobs, is held against the route written here -- no GPU
-needed) and by tests/test_variants_gpu.py (which runs every case against a high-precision torch reference).
+needed), by tests/test_variants_gpu.py (which runs every case against a high-precision torch reference) and, for the
+attention cases, by tests/attention_cases.py (operands that leave the float64 reference exact).
 
 A case records the knobs it sets (csrc/knobs.h), the call, the shape, the dtype and the route fields it expects.  Data
 and small helpers only: no fixtures, nothing is computed on a device here."""
@@ -230,6 +231,43 @@ for _dt in BOTH:
 _add("attn_strided", {}, "attn", (2, 2, 100, 100, 2), "bf16", _fam(LDS, LDS, LDS, 8, 0))
 _add("attn_strided", {}, "attn", (2, 2, 300, 300, 2), "bf16", dict(_fam(PLAIN, PLAIN, PREFETCH, 4, 1, 2), kchunk=256))
 _add("attn_strided", dict(FOD_ATTN_LDS=0), "attn", (2, 2, 100, 100, 2), "bf16", _fam(PLAIN, PLAIN, PREFETCH, 4, 0))
+
+# ---- attention on exactly representable operands (tests/attention_cases.py runs these together with every attn_family /
+# attn_ksplit / attn_strided case): the default routes of both dtypes at the shapes of test_attention_fwd_bwd, f32 where
+# the families above have bf16 only, dropout by default and with FOD_ATTN_PF=0, and the smallest shapes on the kernels'
+# edges.  The expected route restates route() of csrc/attention.hip for the default knobs (FOD_ATTN_LDS=8).
+def _attn_default(shape, dtype, drop=False, pf=True):
+    B, H, Tq, S, _ = shape
+    split = int(Tq <= 512 and S >= 128)
+    lds = dtype == "bf16" and not drop and not split
+    ks, kc = 1, S
+    if Tq <= 512 and S >= 256:
+        k = min(256 // (-(-Tq // 32) * H * B), 8, S // 128)
+        if k > 1:
+            kc = -(-(-(-S // k)) // 128) * 128
+            ks = -(-S // kc)
+    fwd = LDS if lds else PLAIN
+    dkv = LDS if lds else PREFETCH if dtype == "bf16" and pf else PLAIN
+    return dict(_fam(fwd, fwd, dkv, 8 if lds else 4, split, ks), kchunk=kc)
+
+
+ATTN_FWD_BWD_SHAPES = [(2, 4, 77, 150, 1), (1, 8, 128, 49, 2), (2, 2, 33, 1, 2), (1, 8, 200, 200, 1), (2, 8, 128, 1450, 2),
+                       (1, 2, 600, 333, 1), (1, 1, 40, 130, 2), (1, 2, 700, 650, 2), (2, 1, 513, 64, 1)]
+ATTN_EDGE_TQ = (32, 33, 128, 129, 256, 257)          # one wave's queries, a 4-wave and an 8-wave block, each plus one
+ATTN_EDGE_S = (1, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257)   # key tiles of 32 / 64, the two split thresholds
+ATTN_EDGE_SHAPES = ([(1, 2, _tq, _s, 1 + (_tq + _s) % 2) for _tq in ATTN_EDGE_TQ for _s in (65, 129)]       # S = 129: S % 128 == 1
+                    + [(1, 2, 33, _s, 1 + _s % 2) for _s in ATTN_EDGE_S if _s not in (65, 129)]
+                    + [(1, 1, 513, _s, 1 + _s % 2) for _s in ATTN_EDGE_S if _s != 1])      # the non-split kernels at every S
+ATTN_DROP_SHAPES = [(1, 2, 600, 333, 1), (2, 4, 77, 150, 1), (1, 4, 200, 300, 1), (1, 8, 128, 49, 2)]
+_seen = set()
+for _dt in BOTH:
+    for _s in ATTN_FWD_BWD_SHAPES + ATTN_LONG_SHAPES + ATTN_SPLIT_SHAPES + ATTN_EDGE_SHAPES:
+        if (_s, _dt) not in _seen:
+            _seen.add((_s, _dt))
+            _add("attn_exact", {}, "attn", _s, _dt, _attn_default(_s, _dt))
+    for _s in ATTN_DROP_SHAPES:
+        _add("attn_exact", {}, "attn", _s, _dt, _attn_default(_s, _dt, drop=True), drop=0.5)
+        _add("attn_exact", dict(FOD_ATTN_PF=0), "attn", _s, _dt, _attn_default(_s, _dt, drop=True, pf=False), drop=0.5)
 
 # ---- fp8 attention forward with two 64-key tiles per barrier (no route query: the knob is only read back)
 FP8_STAGE2_SHAPES = [(1, 2, 77, 150, 1), (2, 2, 33, 1, 2), (1, 1, 300, 64, 2), (1, 2, 600, 333, 1)]
