@@ -171,6 +171,15 @@ FOD_DEVINL void store_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC
 FOD_DEVINL float load_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 FOD_DEVINL void stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
+// 16-byte raw buffer load as R (uint4, Frag<__bf16>, ...): an offset past the descriptor's extent returns zeros
+template <typename R, typename RS>
+FOD_DEVINL R bload16(const RS& rs, unsigned off) {
+  const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
+  R u;
+  __builtin_memcpy(&u, &v, 16);
+  return u;
+}
+
 FOD_DEVINL int acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
 
 FOD_DEVINL float wave_sum(float v) {

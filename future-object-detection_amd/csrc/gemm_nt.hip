@@ -43,6 +43,7 @@ using namespace fodnt;
 template <typename T, int MODE, int NT, bool UTAP>
 FOD_DEVINL void gemm_nt_body(const NtParams& p) {
   constexpr int VEC = Elem<T>::VEC;
+  constexpr unsigned ESZ = sizeof(T);
   constexpr int BK = ROW_BYTES / (int)sizeof(T);
   constexpr int BN = 64 * NT;
   constexpr int KSTEPS = BK / 16;
@@ -56,42 +57,22 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   FOD_STAMP(0);
-  // XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (private L2 each), so block
-  // ids congruent mod 8 share an L2: give each XCD whole m-tiles (all of an m-tile's n-tiles re-read the
-  // same gathered A rows; neighbouring m-tiles share 3x3 halo rows) instead of striping n-tiles over XCDs.
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int nt_i = slot % p.gx;
-  const int mt_i = (slot / p.gx) * 8 + xcd;
-  if (mt_i >= p.gy) return;
-  const int n0 = nt_i * BN;
-  const int m0 = mt_i * BM;
+  const TileOrigin tile = tile_origin<BM, BN>(p);
+  if (!tile.ok) return;
+  const int m0 = tile.m0, n0 = tile.n0;
   const int cc = tid & 7;     // 16-byte chunk column handled by this thread
   const int r0 = tid >> 3;    // first tile row handled by this thread (then +32, +64, +96)
 
-  // Operands are read with raw buffer loads: an out-of-range chunk (row tail, k tail, conv padding) gets the
-  // byte offset OOB, which the hardware range check turns into zeros -- no branch and no select around
-  // the load, so hipcc keeps counted vmcnt waits and the staged tile stays in flight during the MFMAs.
-  constexpr unsigned OOB = 0xFFFFFFF0u;
+  // Operands are read with raw buffer loads (OOB, gemm_nt.h)
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, p.a_bytes, 0x00020000);
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, p.b_bytes, 0x00020000);
 
   // ---- per-row gather state (fixed over the k loop); offsets in BYTES
   // dense: a_base = byte offset of the row.  conv modes: byte offset of the image; with UTAP of source pixel
-  // (img, a_h, a_w), channel = this thread's chunk (modulo 2^32 when a_h / a_w are negative: only used after the
-  // bounds check), so that a tap adds or subtracts one uniform byte delta (tap_off below)
+  // (img, a_h, a_w), channel = this thread's chunk, so that a tap adds or subtracts one uniform byte delta
   unsigned a_base[4];
   int a_h[4], a_w[4];
-  // pixel (img, ph, pw) of this thread's first row by division, of the next three (+32 rows each) by stepping:
-  // eight 32-bit divisions per thread were ~0.5 us of every block's prologue
-  int px_img = 0, px_h = 0, px_w = 0;
-  if (MODE != MODE_DENSE) {
-    const int mfirst = m0 + r0;
-    const int hw = p.Hd * p.Wd;
-    px_img = mfirst / hw;
-    const int rem = mfirst - px_img * hw;
-    px_h = rem / p.Wd;
-    px_w = rem - px_h * p.Wd;
-  }
+  PixelWalk px(p, MODE != MODE_DENSE ? m0 + r0 : 0);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int m = m0 + r0 + 32 * i;
@@ -101,32 +82,16 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
       a_base[i] = valid ? (unsigned)((long)row * p.lda * (long)sizeof(T)) : OOB;
       a_h[i] = a_w[i] = 0;
     } else {
-      const int img = px_img, ph = px_h, pw = px_w;
-      px_w += 32;                                  // the next row of this thread
-      while (px_w >= p.Wd) {
-        px_w -= p.Wd;
-        if (++px_h == p.Hd) {
-          px_h = 0;
-          ++px_img;
-        }
-      }
-      a_base[i] = (unsigned)((long)img * p.Hs * p.Ws * p.Cs * (long)sizeof(T));
+      const PixelWalk here = px.template next<32>(p);   // then the next row of this thread
       if (MODE == MODE_STEM) {
         // byte offset of haloed pixel (img, 2 ho, 2 wo): the first tap of output pixel (ho, wo)
-        a_base[i] = valid ? a_base[i] + (unsigned)(((long)(2 * ph) * p.Ws + 2 * pw) * p.Cs * (long)sizeof(T)) : OOB;
+        a_base[i] = (unsigned)((long)here.img * p.Hs * p.Ws * p.Cs * (long)sizeof(T));
+        a_base[i] = valid ? a_base[i] + (unsigned)(((long)(2 * here.h) * p.Ws + 2 * here.w) * p.Cs * (long)sizeof(T)) : OOB;
         a_h[i] = a_w[i] = 0;
-      } else if (MODE == MODE_CONV) {
-        a_h[i] = valid ? ph * p.stride - p.pad : -(1 << 28);
-        a_w[i] = pw * p.stride - p.pad;
-      } else if (MODE == MODE_DGRAD_S2) {
-        a_h[i] = valid ? ph + p.off_h : -(1 << 28);
-        a_w[i] = pw + p.off_w;
       } else {
-        a_h[i] = valid ? ph + p.pad : -(1 << 28);
-        a_w[i] = pw + p.pad;
+        a_base[i] = row_origin<MODE, ESZ>(p, here, valid, a_h[i], a_w[i]);
+        if (UTAP) a_base[i] += origin_offset<ESZ>(p, a_h[i], a_w[i]);
       }
-      if (UTAP)
-        a_base[i] += ((unsigned)a_h[i] * (unsigned)p.Ws + (unsigned)a_w[i]) * (unsigned)p.Cs * (unsigned)sizeof(T);
     }
   }
   unsigned b_base[BROWS];
@@ -136,39 +101,24 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
     b_base[i] = (n < p.N) ? (unsigned)((long)n * p.ldb * (long)sizeof(T)) : OOB;
   }
 
-  auto bload = [](const auto& rs, unsigned off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
-    uint4 u;
-    __builtin_memcpy(&u, &v, 16);
-    return u;
-  };
-  constexpr unsigned ESZ = sizeof(T);
-  constexpr unsigned BKB = BK * ESZ;
   const int ccs = cc;
   const unsigned cc_off = (unsigned)(ccs * VEC) * ESZ;
-  const int tap_w = MODE == MODE_DGRAD_S2 ? p.n_s : p.kw;
-  const unsigned tap_row_skip = (unsigned)((p.Ws - tap_w) * p.Cs) * ESZ;
-  const unsigned kb_row_skip = (unsigned)((2 * p.kw - 2 * tap_w) * p.Cs) * ESZ;
-  const unsigned cs_b = (unsigned)p.Cs * ESZ;
   // Tap walk (r, s, c) of the tile being requested (tiles come in increasing order).
-  //   UTAP : c = the tile's first channel, the state is block-uniform (SGPRs, scalar updates).
-  //          tap_off = ((r * Ws + s) * Cs +- c) * ESZ is the source-side byte delta of (tap (r, s), channel c):
-  //          added to the row's base in the forward conv, subtracted (taps walk backwards, the channel still
-  //          counts up) in both dgrad modes.  tap_kb (MODE_DGRAD_S2) = byte offset of (full-kernel tap, c) in a
-  //          weight row.  Everything advances by adds.
-  //   else : per-thread walk of this thread's chunk; offsets by multiplication (stem, ragged channel counts).
-  int tap_r = 0, tap_s = 0, tap_c = UTAP ? 0 : ccs * VEC;
-  unsigned tap_off = 0, tap_kb = 0;
+  //   UTAP : the block-uniform walk of gemm_nt.h; the rows' bases take this thread's chunk.
+  //   else : per-thread walk of this thread's chunk; offsets by multiplication (ragged channel counts).
+  UniformTapWalk<MODE, ESZ> utap(p);
+  const int tap_w = MODE == MODE_DGRAD_S2 ? p.n_s : p.kw;
+  int tap_r = 0, tap_s = 0, tap_c = ccs * VEC;
   const unsigned stem_row_b = (unsigned)(p.Ws * p.Cs) * ESZ;   // MODE_STEM: bytes per source image row
   if (MODE != MODE_DENSE && MODE != MODE_STEM) {
-    const int tap = tap_c / p.Cs;
-    tap_c -= tap * p.Cs;
-    tap_r = tap / tap_w;
-    tap_s = tap - tap_r * tap_w;
     if (UTAP) {
-      if (MODE == MODE_DGRAD_S2) tap_kb = (unsigned)((p.r_first * p.kw + p.s_first) * p.Cs) * ESZ;
 #pragma unroll
       for (int i = 0; i < 4; ++i) a_base[i] += cc_off;
+    } else {
+      const int tap = tap_c / p.Cs;
+      tap_c -= tap * p.Cs;
+      tap_r = tap / tap_w;
+      tap_s = tap - tap_r * tap_w;
     }
   }
   // Register staging ring: tile t lives in ring[t % 3]; two tiles are in flight while a third is consumed
@@ -181,30 +131,22 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
   auto tile_offsets = [&](int kt, unsigned* offa, unsigned* offb) {
     const int k = kt * BK + ccs * VEC;
     const bool kin = UTAP ? true : k < p.K;          // UTAP: K is a multiple of BK
-    const int r = tap_r, s = tap_s, c = tap_c;
-    const unsigned toff = tap_off;
+    const int r = UTAP ? utap.r : tap_r, s = UTAP ? utap.s : tap_s, c = tap_c;
+    const unsigned toff = utap.off;
     unsigned kb = (unsigned)k * ESZ;                 // byte offset of this chunk inside a B row
     if (MODE == MODE_DGRAD_S2)
-      kb = UTAP ? tap_kb + cc_off
+      kb = UTAP ? utap.kb + cc_off
                 : (unsigned)(((p.r_first + 2 * r) * p.kw + p.s_first + 2 * s) * p.Cs + c) * ESZ;
     if (MODE != MODE_DENSE && MODE != MODE_STEM) {   // advance to the next tile's tap
-      tap_c += BK;
       if (UTAP) {
-        tap_off = MODE == MODE_CONV ? tap_off + BKB : tap_off - BKB;
-        tap_kb += BKB;
-      }
-      while (tap_c >= p.Cs) {                        // UTAP: at most once, uniform
-        tap_c -= p.Cs;
-        if (UTAP) {
-          if (MODE != MODE_CONV) tap_off += 2 * cs_b;   // (s+1)*Cs - (c-Cs) vs s*Cs - c; forward: the sum is unchanged
-          tap_kb += cs_b;                               // the full kernel advances by two taps
-        }
-        if (++tap_s == tap_w) {
-          tap_s = 0;
-          ++tap_r;
-          if (UTAP) {
-            tap_off += tap_row_skip;
-            tap_kb += kb_row_skip;
+        utap.template advance<BK>(p);
+      } else {
+        tap_c += BK;
+        while (tap_c >= p.Cs) {
+          tap_c -= p.Cs;
+          if (++tap_s == tap_w) {
+            tap_s = 0;
+            ++tap_r;
           }
         }
       }
@@ -217,10 +159,8 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
       } else if (MODE == MODE_STEM) {
         off = (kin && a_base[i] != OOB) ? a_base[i] + (unsigned)(k >> 5) * stem_row_b + (unsigned)(k & 31) * ESZ : OOB;
       } else {
-        // forward: source = (a_h + r, a_w + s); both dgrad modes walk the taps backwards
-        const int hs = MODE == MODE_CONV ? a_h[i] + r : a_h[i] - r;
-        const int ws = MODE == MODE_CONV ? a_w[i] + s : a_w[i] - s;
-        const bool ok = kin && (unsigned)hs < (unsigned)p.Hs && (unsigned)ws < (unsigned)p.Ws;
+        int hs, ws;
+        const bool ok = tap_source<MODE>(p, kin, a_h[i], a_w[i], r, s, hs, ws);
         if (UTAP) off = ok ? (MODE == MODE_CONV ? a_base[i] + toff : a_base[i] - toff) : OOB;
         else off = ok ? a_base[i] + (unsigned)((hs * p.Ws + ws) * p.Cs + c) * ESZ : OOB;
       }
@@ -233,9 +173,9 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
     unsigned offa[4], offb[BROWS];
     tile_offsets(kt, offa, offb);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) st.a[i] = bload(rsA, offa[i]);
+    for (int i = 0; i < 4; ++i) st.a[i] = bload16<uint4>(rsA, offa[i]);
 #pragma unroll
-    for (int i = 0; i < BROWS; ++i) st.b[i] = bload(rsB, offb[i]);
+    for (int i = 0; i < BROWS; ++i) st.b[i] = bload16<uint4>(rsB, offb[i]);
   };
   auto store_tile = [&](int buf, const Stage& st) {
 #pragma unroll
@@ -326,16 +266,6 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
 
   const T* __restrict__ Rp = reinterpret_cast<const T*>(p.res);
   const T* __restrict__ Mp = reinterpret_cast<const T*>(p.mask);
-  // row of C / residual / mask for tile row m (identity except for the parity-class launches)
-  auto out_row = [&](int m) -> long {
-    if (MODE != MODE_DGRAD_S2) return m;
-    const int hw = p.Hd * p.Wd;
-    const int img = m / hw;
-    const int rem = m - img * hw;
-    const int hq = rem / p.Wd;
-    const int wq = rem - hq * p.Wd;
-    return ((long)img * p.out_H + 2 * hq + p.par_h) * p.out_W + 2 * wq + p.par_w;
-  };
   if (p.vec_epi) {
     // ---- epilogue A: accumulators -> LDS (f32 tile, reusing the staging buffers; the k-loop ended on a
     // barrier) -> whole rows back out, 4 columns per lane: 32 (BN=128) or 16 lanes cover one row, so every
@@ -353,14 +283,8 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
     VT rres[PB], rmsk[PB];
     auto prefetch = [&](int base) {
 #pragma unroll
-      for (int ps = 0; ps < PB; ++ps) {
-        const long m = out_row(min(m0 + rq + (base + ps) * RPP, p.M - 1));
-        if (Rp) {
-          const long rm = p.res_row_mod > 0 ? (m % p.res_row_mod) : m;
-          rres[ps] = *reinterpret_cast<const VT*>(Rp + rm * p.ldr + nc);
-        }
-        if (Mp) rmsk[ps] = *reinterpret_cast<const VT*>(Mp + m * p.ldmask + nc);
-      }
+      for (int ps = 0; ps < PB; ++ps)
+        fetch_res_mask<MODE>(p, Rp, Mp, Rp != nullptr, Mp != nullptr, m0 + rq + (base + ps) * RPP, nc, rres[ps], rmsk[ps]);
     };
     prefetch(0);
     float* sC = reinterpret_cast<float*>(smem);
@@ -391,16 +315,9 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
         for (int ps = 0; ps < NPASS; ++ps) v[ps] = *reinterpret_cast<const f32x4*>(sC + (rq + ps * RPP) * BN + cq * 4);
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
-          f32x4 w = v[ps] * sc + sh;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if constexpr (decltype(has_res)::value) w[e] += (float)rres[ps][e];
-            if constexpr (decltype(do_relu)::value) w[e] = fmaxf(w[e], 0.f);
-            if constexpr (decltype(has_mask)::value) w[e] = ((float)rmsk[ps][e] > 0.f) ? w[e] : 0.f;
-          }
-          const long mo = out_row(m0 + rq + ps * RPP);
-          *reinterpret_cast<bf16x4_t*>(reinterpret_cast<__bf16*>(p.C) + mo * p.ldc + n) =
-              bf16x4_t{(__bf16)w[0], (__bf16)w[1], (__bf16)w[2], (__bf16)w[3]};
+          const f32x4 w = epilogue4<decltype(has_res)::value, decltype(do_relu)::value, decltype(has_mask)::value>(
+              v[ps], sc, sh, rres[ps], rmsk[ps]);
+          store4(p, false, out_row<MODE>(p, m0 + rq + ps * RPP), n, w);
         }
       };
       typedef std::true_type Y;
@@ -440,15 +357,7 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = ((float)rmsk[ps][e] > 0.f) ? v[e] : 0.f;
         }
-        if (m < p.M && n < p.N) {
-          const long mo = out_row(m);
-          if (p.c_is_f32 || sizeof(T) == 4) {
-            *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + mo * p.ldc + n) = v;
-          } else {
-            *reinterpret_cast<bf16x4_t*>(reinterpret_cast<__bf16*>(p.C) + mo * p.ldc + n) =
-                bf16x4_t{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-          }
-        }
+        if (m < p.M && n < p.N) store4(p, p.c_is_f32 || sizeof(T) == 4, out_row<MODE>(p, m), n, v);
       }
     }
     FOD_STAMP(4);
@@ -467,7 +376,7 @@ FOD_DEVINL void gemm_nt_body(const NtParams& p) {
       for (int r = 0; r < 16; ++r) {
         const int mt = m0 + wm * 64 + i * 32 + acc_row(r, lane);
         if (mt >= p.M) continue;
-        const long m = out_row(mt);
+        const long m = out_row<MODE>(p, mt);
         float v = acc[i][j][r] * sc + sh;
         if (Rp) {
           const long rm = p.res_row_mod > 0 ? (m % p.res_row_mod) : m;
@@ -534,7 +443,6 @@ __global__ __launch_bounds__(256) void gemm_nt_small_kernel(const NtParams p) {
   }
   const int n0 = blockIdx.x * 64, m0 = by * 64;
   FOD_STAMP(0);
-  constexpr unsigned OOB = 0xFFFFFFF0u;
   const T* pA = reinterpret_cast<const T*>(p.A) + bz * p.a_batch;
   const T* pB = reinterpret_cast<const T*>(p.B) + bz * p.b_batch;
   const float* pShift = p.shift ? p.shift + bz * p.shift_batch : nullptr;
@@ -542,12 +450,6 @@ __global__ __launch_bounds__(256) void gemm_nt_small_kernel(const NtParams p) {
   const T* pMask = p.mask ? reinterpret_cast<const T*>(p.mask) + bz * p.mask_batch : nullptr;
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(pA), 0, p.a_bytes, 0x00020000);
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(pB), 0, p.b_bytes, 0x00020000);
-  auto bload = [](const auto& rs, unsigned off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
-    Frag<T> f;
-    __builtin_memcpy(&f, &v, 16);
-    return f;
-  };
 
   // ---- epilogue operands of this thread's 4 output rows (row = tid/16 + 16*pass, 4 columns at (tid%16)*4)
   const int cq = tid & 15, rq = tid >> 4;
@@ -617,8 +519,8 @@ __global__ __launch_bounds__(256) void gemm_nt_small_kernel(const NtParams p) {
       const bool kin = u < ue && k < p.K;        // K % 8 == 0: a 16-byte chunk is all in or all out
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        f.a[ks][i] = bload(rsA, (kin && a_off[i] != OOB) ? a_off[i] + k * 2 + seg_extra : OOB);
-        f.b[ks][i] = bload(rsB, (kin && b_off[i] != OOB) ? b_off[i] + k * 2 : OOB);
+        f.a[ks][i] = bload16<Frag<T>>(rsA, (kin && a_off[i] != OOB) ? a_off[i] + k * 2 + seg_extra : OOB);
+        f.b[ks][i] = bload16<Frag<T>>(rsB, (kin && b_off[i] != OOB) ? b_off[i] + k * 2 : OOB);
       }
     }
     seg_k += 32;

@@ -51,15 +51,10 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware tile order (see gemm_nt.hip): block ids congruent mod 8 share an L2 and get whole m-tiles
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int nt_i = slot % p.gx;
-  const int mt_i = (slot / p.gx) * 8 + xcd;
-  if (mt_i >= p.gy) return;
-  const int n0 = nt_i * BNB;
-  const int m0 = mt_i * BMB;
+  const TileOrigin tile = tile_origin<BMB, BNB>(p);
+  if (!tile.ok) return;
+  const int m0 = tile.m0, n0 = tile.n0;
 
-  constexpr unsigned OOB = 0xFFFFFFF0u;
   const v4i rsA = make_rsrc(p.A, p.a_bytes), rsB = make_rsrc(p.B, p.b_bytes);
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)smem;      // LDS byte address of the ring
 
@@ -68,15 +63,7 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
   const int lrow = lane >> 3, lslot = lane & 7;
   unsigned a_base[A_DMA], a_cc[A_DMA];
   int a_h[A_DMA], a_w[A_DMA];
-  int px_img = 0, px_h = 0, px_w = 0;
-  if (MODE != MODE_DENSE) {
-    const int mfirst = m0 + 8 * wave + lrow;
-    const int hw = p.Hd * p.Wd;
-    px_img = mfirst / hw;
-    const int rem = mfirst - px_img * hw;
-    px_h = rem / p.Wd;
-    px_w = rem - px_h * p.Wd;
-  }
+  PixelWalk px(p, MODE != MODE_DENSE ? m0 + 8 * wave + lrow : 0);
 #pragma unroll
   for (int i = 0; i < A_DMA; ++i) {
     const int row = 8 * (8 * i + wave) + lrow;
@@ -88,29 +75,10 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
       a_base[i] = valid ? (unsigned)((long)r * p.lda * (long)ESZ) + a_cc[i] : OOB;
       a_h[i] = a_w[i] = 0;
     } else {
-      const int img = px_img, ph = px_h, pw = px_w;
-      px_w += 64;                                  // this lane's next row is 64 tile rows on
-      while (px_w >= p.Wd) {
-        px_w -= p.Wd;
-        if (++px_h == p.Hd) {
-          px_h = 0;
-          ++px_img;
-        }
-      }
-      a_base[i] = (unsigned)((long)img * p.Hs * p.Ws * p.Cs * (long)ESZ);
-      if (MODE == MODE_CONV) {
-        a_h[i] = valid ? ph * p.stride - p.pad : -(1 << 28);
-        a_w[i] = pw * p.stride - p.pad;
-      } else if (MODE == MODE_DGRAD_S2) {
-        a_h[i] = valid ? ph + p.off_h : -(1 << 28);
-        a_w[i] = pw + p.off_w;
-      } else {
-        a_h[i] = valid ? ph + p.pad : -(1 << 28);
-        a_w[i] = pw + p.pad;
-      }
-      // byte offset of source pixel (img, a_h, a_w), this lane's chunk (modulo 2^32 for negative coordinates: only
-      // used after the bounds check); a tap then adds or subtracts one block-uniform delta
-      a_base[i] += ((unsigned)a_h[i] * (unsigned)p.Ws + (unsigned)a_w[i]) * (unsigned)p.Cs * ESZ + a_cc[i];
+      const PixelWalk here = px.template next<64>(p);   // this lane's next row is 64 tile rows on
+      // byte offset of source pixel (img, a_h, a_w), this lane's chunk
+      a_base[i] = row_origin<MODE, ESZ>(p, here, valid, a_h[i], a_w[i]);
+      a_base[i] += origin_offset<ESZ>(p, a_h[i], a_w[i]) + a_cc[i];
     }
   }
   unsigned b_base[B_DMA], b_cc[B_DMA];
@@ -122,14 +90,7 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
     b_base[i] = (n < p.N) ? (unsigned)((long)n * p.ldb * (long)ESZ) + b_cc[i] : OOB;
   }
 
-  // block-uniform tap walk of the tile being requested (tiles come in increasing order); see gemm_nt.hip UTAP
-  const int tap_w = MODE == MODE_DGRAD_S2 ? p.n_s : p.kw;
-  const unsigned tap_row_skip = (unsigned)((p.Ws - tap_w) * p.Cs) * ESZ;
-  const unsigned kb_row_skip = (unsigned)((2 * p.kw - 2 * tap_w) * p.Cs) * ESZ;
-  const unsigned cs_b = (unsigned)p.Cs * ESZ;
-  int tap_r = 0, tap_s = 0, tap_c = 0;
-  unsigned tap_off = 0, tap_kb = 0;
-  if (MODE == MODE_DGRAD_S2) tap_kb = (unsigned)((p.r_first * p.kw + p.s_first) * p.Cs) * ESZ;
+  UniformTapWalk<MODE, ESZ> tap(p);                  // of the tile being requested (gemm_nt.h)
   int next_kt = 0;                                   // tile the walk stands at
 
   struct TileCtx {
@@ -141,26 +102,11 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
   auto begin_tile = [&](int stage) {
     const int kt = next_kt++;
     const unsigned kbyte = (unsigned)kt * BKB;       // byte offset of the tile inside a dense row
-    const int r = tap_r, s = tap_s;
-    const unsigned toff = tap_off;
+    const int r = tap.r, s = tap.s;
+    const unsigned toff = tap.off;
     unsigned kb = kbyte;
-    if (MODE == MODE_DGRAD_S2) kb = tap_kb;
-    if (MODE != MODE_DENSE) {                        // advance the walk to the next tile
-      tap_c += BKB_EL;
-      tap_off = MODE == MODE_CONV ? tap_off + BKB : tap_off - BKB;
-      tap_kb += BKB;
-      if (tap_c >= p.Cs) {
-        tap_c -= p.Cs;
-        if (MODE != MODE_CONV) tap_off += 2 * cs_b;
-        tap_kb += cs_b;
-        if (++tap_s == tap_w) {
-          tap_s = 0;
-          ++tap_r;
-          tap_off += tap_row_skip;
-          tap_kb += kb_row_skip;
-        }
-      }
-    }
+    if (MODE == MODE_DGRAD_S2) kb = tap.kb;
+    if (MODE != MODE_DENSE) tap.template advance<BKB_EL>(p);   // to the next tile
     const unsigned sA = lds0 + (unsigned)(stage * STAGE_BYTES + wave * 1024);
     const unsigned sB = sA + BMB * ROW_BYTES;
     const bool tile_in = kt * BKB_EL < p.K;
@@ -177,6 +123,7 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
         const bool kin = (int)(c.kt * BKB_EL + (a_cc[i] >> 1)) < p.K;
         off = (kin && a_base[i] != OOB) ? a_base[i] + c.kbyte : OOB;
       } else {
+        // the test of tap_source (gemm_nt.h) written out: through the function this loop measured 0.06 ms per step slower
         const int hs = MODE == MODE_CONV ? a_h[i] + c.r : a_h[i] - c.r;
         const int ws = MODE == MODE_CONV ? a_w[i] + c.s : a_w[i] - c.s;
         const bool ok = c.tile_in && (unsigned)hs < (unsigned)p.Hs && (unsigned)ws < (unsigned)p.Ws;
@@ -292,15 +239,6 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
   // ---- epilogue: accumulators -> LDS (f32 tile over the ring) -> whole rows out, 4 columns per lane
   const T* __restrict__ Rp = reinterpret_cast<const T*>(p.res);
   const T* __restrict__ Mp = reinterpret_cast<const T*>(p.mask);
-  auto out_row = [&](int m) -> long {
-    if (MODE != MODE_DGRAD_S2) return m;
-    const int hw = p.Hd * p.Wd;
-    const int img = m / hw;
-    const int rem = m - img * hw;
-    const int hq = rem / p.Wd;
-    const int wq = rem - hq * p.Wd;
-    return ((long)img * p.out_H + 2 * hq + p.par_h) * p.out_W + 2 * wq + p.par_w;
-  };
   // The f32 tile goes over the ring in HALVES row halves (the 256 x 256 tile is 256 KiB, its ring 128)
   constexpr int HALVES = (BMB * BNB * 4 > NSTAGE * STAGE_BYTES) ? 2 : 1;
   constexpr int ROWS_H = BMB / HALVES;       // rows per half
@@ -318,42 +256,25 @@ __global__ __launch_bounds__(512) void nt_big_kernel(const NtParams p) {
   const bool full = m0 + BMB <= p.M && n0 + BNB <= p.N && !p.c_is_f32;
   int mh = 0;                                // first tile row of the half in LDS
   auto rows_out = [&](auto has_res, auto do_relu, auto has_mask, auto is_full) {
+    constexpr bool HAS_RES = decltype(has_res)::value, HAS_MASK = decltype(has_mask)::value;
 #pragma unroll
     for (int base = 0; base < NPASS; base += PB) {
       bf16x4_t rres[PB], rmsk[PB];
       f32x4 v[PB];
 #pragma unroll
-      for (int ps = 0; ps < PB; ++ps) {
-        const long m = out_row(min(m0 + mh + rq + (base + ps) * RPP, p.M - 1));
-        if constexpr (decltype(has_res)::value) {
-          const long rm = p.res_row_mod > 0 ? (m % p.res_row_mod) : m;
-          rres[ps] = *reinterpret_cast<const bf16x4_t*>(Rp + rm * p.ldr + nc);
-        }
-        if constexpr (decltype(has_mask)::value) rmsk[ps] = *reinterpret_cast<const bf16x4_t*>(Mp + m * p.ldmask + nc);
-      }
+      for (int ps = 0; ps < PB; ++ps)
+        fetch_res_mask<MODE>(p, Rp, Mp, HAS_RES, HAS_MASK, m0 + mh + rq + (base + ps) * RPP, nc, rres[ps], rmsk[ps]);
 #pragma unroll
       for (int ps = 0; ps < PB; ++ps)
         v[ps] = *reinterpret_cast<const f32x4*>(sC + (rq + (base + ps) * RPP) * BNB + cq * 4);
 #pragma unroll
       for (int ps = 0; ps < PB; ++ps) {
-        f32x4 w = v[ps] * sc + sh;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if constexpr (decltype(has_res)::value) w[e] += (float)rres[ps][e];
-          if constexpr (decltype(do_relu)::value) w[e] = fmaxf(w[e], 0.f);
-          if constexpr (decltype(has_mask)::value) w[e] = ((float)rmsk[ps][e] > 0.f) ? w[e] : 0.f;
-        }
+        const f32x4 w = epilogue4<HAS_RES, decltype(do_relu)::value, HAS_MASK>(v[ps], sc, sh, rres[ps], rmsk[ps]);
         const int mt = m0 + mh + rq + (base + ps) * RPP;
         if constexpr (!decltype(is_full)::value) {
           if (mt >= p.M || n >= p.N) continue;
         }
-        const long mo = out_row(mt);
-        if (decltype(is_full)::value || !p.c_is_f32) {
-          *reinterpret_cast<bf16x4_t*>(reinterpret_cast<__bf16*>(p.C) + mo * p.ldc + n) =
-              bf16x4_t{(__bf16)w[0], (__bf16)w[1], (__bf16)w[2], (__bf16)w[3]};
-        } else {
-          *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + mo * p.ldc + n) = w;
-        }
+        store4(p, !decltype(is_full)::value && p.c_is_f32, out_row<MODE>(p, mt), n, w);
       }
     }
   };

@@ -114,12 +114,6 @@ FOD_DEVINL void gemm_tn_body(const TnParams& p, const int bid_x, const int bid_y
   constexpr unsigned OOB = 0xFFFFFFF0u;
   const auto rsG = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.G), 0, p.g_bytes, 0x00020000);
   const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.X), 0, p.x_bytes, 0x00020000);
-  auto bload = [](const auto& rs, unsigned off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
-    uint4 u;
-    __builtin_memcpy(&u, &v, 16);
-    return u;
-  };
   struct Stage {
     uint4 g[PASSES];
     uint4 x[PASSES];
@@ -187,8 +181,8 @@ FOD_DEVINL void gemm_tn_body(const TnParams& p, const int bid_x, const int bid_y
       row_m[ps] += MSTEP;
       off_g[ps] += step_g;
       if (MODE == MODE_DENSE) off_x[ps] += step_x;
-      st.g[ps] = bload(rsG, og);
-      st.x[ps] = bload(rsX, ox);
+      st.g[ps] = bload16<uint4>(rsG, og);
+      st.x[ps] = bload16<uint4>(rsX, ox);
     }
   };
   float csum[VEC];
