@@ -16,6 +16,10 @@ Plannable is: crops (a rectangle inside a rectangle composes exactly), then at m
 `JointHorizontalFlip`, with `SizeFilter` / no-ops anywhere; `RandomSelect` plans the branch it draws.  Anything else
 would need a second resampling: `plan` raises ValueError naming the step, it never approximates.
 
+`JointResize(..., antialias=True)` is opt-in (the reference's pinned torchvision does not antialias tensors; current
+torchvision does by default): the CPU form passes `antialias=True` to `F.interpolate`, the plan carries the flag
+(`Plan.antialias`) and the device half runs `fod_clip_crop_resize_aa`.  Geometry, annotations and draws do not change.
+
 `JointPhotometricDistortion` is the colour half: per-pixel work, which commutes exactly with crops and flips but not
 with resampling.  A plan carries at most one row of it (`Plan.photo`), drawn once per clip, and a `JointResize` may not
 follow it; `fod_clip_crop_resize_photo` applies the row to the resampled pixels in the same pass.
@@ -135,6 +139,7 @@ class Plan:
         self.flip = False
         self.steps = []
         self.photo = None                     # (delta, alpha, sat, hue, first) of a JointPhotometricDistortion, if any
+        self.antialias = False                # the JointResize's flag: the image half is the antialiased pass
         self._resized = self._flip_seen = False
 
     def row(self):
@@ -205,14 +210,23 @@ class JointCompose(JointTransform):
 
 
 class JointResize(JointTransform):
-    def __init__(self, size: Tuple[int, int], interpolation: str = "bilinear"):
+    """`antialias=True` (bilinear only; the default stays the reference's False) averages the whole source footprint of
+    an output pixel, `F.interpolate(..., antialias=True)`: what the device pass does as `fod_clip_crop_resize_aa`."""
+
+    def __init__(self, size: Tuple[int, int], interpolation: str = "bilinear", antialias: bool = False):
         self._size = [int(v) for v in size]
         self._interpolation = getattr(interpolation, "value", interpolation)
+        self._antialias = bool(antialias)
+        if self._antialias and self._interpolation != "bilinear":
+            raise ValueError(f"JointResize(interpolation={self._interpolation!r}, antialias=True): only the bilinear "
+                             "resize has an antialiased form")
 
     def __call__(self, images, boxes, classes):
         old_h, old_w = images.shape[-2:]
         new_h, new_w = self._size
         kw = {"align_corners": False} if self._interpolation in ("bilinear", "bicubic") else {}
+        if self._antialias:
+            kw["antialias"] = True
         images = F.interpolate(images, size=(new_h, new_w), mode=self._interpolation, **kw)
         boxes, classes = annotate(("resize", old_w, old_h, new_w, new_h), boxes, classes)
         return images, boxes, classes
@@ -230,6 +244,7 @@ class JointResize(JointTransform):
         old_h, old_w = plan.size
         plan.size = (self._size[0], self._size[1])
         plan._resized = True
+        plan.antialias = self._antialias
         plan.steps.append(("resize", old_w, old_h, self._size[1], self._size[0]))
 
 
@@ -415,11 +430,32 @@ class JointPhotometricDistortion(JointTransform):
         plan.photo = self._draw(rng)
 
 
+def _inner(transform):
+    """The transforms directly inside a JointCompose or a RandomSelect; nothing for any other step."""
+    return list(getattr(transform, "transforms", ())) if isinstance(transform, JointCompose) else \
+        [transform.transforms1, transform.transforms2] if isinstance(transform, RandomSelect) else []
+
+
 def has_photometric(transform):
     """Whether a JointPhotometricDistortion stands anywhere in `transform` (inside JointCompose / RandomSelect too): then
     its plans may carry a row, and the device half takes the `photo` operand."""
     if isinstance(transform, JointPhotometricDistortion):
         return True
-    inner = list(getattr(transform, "transforms", ())) if isinstance(transform, JointCompose) else \
-        [transform.transforms1, transform.transforms2] if isinstance(transform, RandomSelect) else []
-    return any(has_photometric(t) for t in inner)
+    return any(has_photometric(t) for t in _inner(transform))
+
+
+def _resizes(transform):
+    if isinstance(transform, JointResize):
+        return [transform]
+    return [r for t in _inner(transform) for r in _resizes(t)]
+
+
+def uses_antialias(transform):
+    """Whether the JointResize steps of `transform` (inside JointCompose / RandomSelect too) antialias: then the device
+    half runs `fod_clip_crop_resize_aa`.  One tree makes one choice -- the device half reads it once, and a RandomSelect
+    must not make it per sample: steps that disagree raise ValueError.  A tree without a JointResize does not."""
+    flags = {r._antialias for r in _resizes(transform)}
+    if len(flags) > 1:
+        raise ValueError("the JointResize steps of one transform disagree on antialias: the device pass is chosen once "
+                         "per transform, not per sample (give every JointResize the same flag)")
+    return bool(flags) and flags.pop()

@@ -402,7 +402,7 @@ def clip_to_stem_layout(video, dtype, mean=None, std=None):
     return out
 
 
-def _clip_crop_resize(who, video_u8, plans, size, mean, std, photo=None):
+def _clip_crop_resize(who, video_u8, plans, size, mean, std, photo=None, antialias=False):
     if not isinstance(video_u8, torch.Tensor) or not video_u8.is_cuda or video_u8.dtype != torch.uint8 \
             or video_u8.dim() != 5:
         raise L.FodError(f"{who}: video must be a uint8 device tensor [B, L, C, H0, W0] "
@@ -420,6 +420,10 @@ def _clip_crop_resize(who, video_u8, plans, size, mean, std, photo=None):
     h, w = (int(v) for v in size)
     if photo is None:
         out = torch.empty((b, l, c, h, w), dtype=torch.float32, device=video_u8.device)
+        if antialias:
+            call("fod_clip_crop_resize_aa", ptr(video_u8), ptr(out), b, l, c, h0, w0, h, w, sb, sl, ptr(plans),
+                 ptr(mean), ptr(std), None, stream())
+            return out
         call("fod_clip_crop_resize", ptr(video_u8), ptr(out), b, l, c, h0, w0, h, w, sb, sl, ptr(plans), ptr(mean),
              ptr(std), stream())
         return out
@@ -432,8 +436,8 @@ def _clip_crop_resize(who, video_u8, plans, size, mean, std, photo=None):
     if c != 3:
         raise L.FodError(f"{who}: the photometric map mixes three planes, got C = {c}")
     out = torch.empty((b, l, c, h, w), dtype=torch.float32, device=video_u8.device)
-    call("fod_clip_crop_resize_photo", ptr(video_u8), ptr(out), b, l, c, h0, w0, h, w, sb, sl, ptr(plans), ptr(mean),
-         ptr(std), ptr(photo), stream())
+    call("fod_clip_crop_resize_aa" if antialias else "fod_clip_crop_resize_photo", ptr(video_u8), ptr(out), b, l, c, h0,
+         w0, h, w, sb, sl, ptr(plans), ptr(mean), ptr(std), ptr(photo), stream())
     return out
 
 
@@ -452,6 +456,15 @@ def clip_crop_resize_photo(video_u8, plans, size, mean, std, photo):
     if photo is None:
         raise L.FodError("clip_crop_resize_photo: photo must be an f32 device tensor [B, 5]")
     return _clip_crop_resize("clip_crop_resize_photo", video_u8, plans, size, mean, std, photo)
+
+
+def clip_crop_resize_aa(video_u8, plans, size, mean, std, photo=None):
+    """clip_crop_resize with antialiased resampling (`F.interpolate(..., mode="bilinear", antialias=True)` on the crop
+    rectangle; include/fod_ext.h, fod_clip_crop_resize_aa, states the weights): one separable pass through LDS.  `photo`:
+    None, or f32 [B,5] rows as clip_crop_resize_photo takes them (C must then be 3), applied to the antialiased sample
+    in the same launch; a neutral row gives the bits of None.  A frame more than 4 times the output on an axis is
+    refused before any launch.  There is no CPU fallback."""
+    return _clip_crop_resize("clip_crop_resize_aa", video_u8, plans, size, mean, std, photo, antialias=True)
 
 
 def render_boxes(video, boxes, labels, *, frame_idx=None, mean=None, std=None, palette, thickness=3, out=None):

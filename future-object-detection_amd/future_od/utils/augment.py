@@ -11,6 +11,10 @@ upload, which is a quarter of the bytes a float clip would take over PCIe.
 With a `JointPhotometricDistortion` in the joint transform the plans also carry one photometric row per clip: `host`
 adds `photo` f32 [B, 5], and `device` runs `ops.clip_crop_resize_photo` -- the same single launch -- instead.
 
+With `JointResize(..., antialias=True)` in the joint transform (`uses_antialias`, read once) `device` runs
+`ops.clip_crop_resize_aa` instead -- the antialiased pass, which takes the `photo` rows too.  Plans, annotations, draws
+and batch keys are the same with and without it.
+
 `DevicePrefetcher` calls the two halves for a loader that carries a `device_transform` attribute.  The batch that
 reaches the model has the usual keys, shapes and dtypes, so a captured step is captured once and replayed.
 There is no CPU fallback for the kernel."""
@@ -18,7 +22,7 @@ import random
 
 import torch
 
-from future_od.datasets.transforms import has_photometric
+from future_od.datasets.transforms import has_photometric, uses_antialias
 from future_od.utils.recursive_functions import HOST_ANNOTATIONS
 
 PLANS, PLAN_SIZE, PHOTO = "plans", "_plan_size", "photo"
@@ -29,6 +33,7 @@ class DeviceJointTransform:
         self.joint_transform = joint_transform
         self.seed, self.rank = int(seed), int(rank)
         self.photometric = has_photometric(joint_transform)      # then every batch carries `photo`
+        self.antialias = uses_antialias(joint_transform)         # then the device half is the antialiased pass
         self._index = 0                       # batches planned so far
         self._norm = {}                       # device -> (mean, std)
 
@@ -134,6 +139,11 @@ class DeviceJointTransform:
         if norm is None:
             norm = self._norm[video.device] = tuple(torch.tensor(v, dtype=torch.float32, device=video.device)
                                                     for v in (ResNetBody.PIXEL_MEAN, ResNetBody.PIXEL_STD))
+        if self.antialias:
+            out = {k: v for k, v in batch.items() if k not in (PLANS, PLAN_SIZE, PHOTO)}
+            out["video"] = ops.clip_crop_resize_aa(video, batch[PLANS], batch[PLAN_SIZE], *norm,
+                                                   batch[PHOTO] if self.photometric else None)
+            return out
         if not self.photometric:
             out = {k: v for k, v in batch.items() if k not in (PLANS, PLAN_SIZE)}
             out["video"] = ops.clip_crop_resize(video, batch[PLANS], batch[PLAN_SIZE], *norm)

@@ -16,7 +16,10 @@ source: normalised float clips at `img_size`, no transform.
 
 `photometric` (a `T.JointPhotometricDistortion`; the reference has no colour augmentation) is appended to the training
 transform, after the resize: `JointCompose([random_aug, JointResize(img_size), photometric])`.  Its row is drawn once per
-clip and applied by the same device pass.  The validation transform stays as it is."""
+clip and applied by the same device pass.  The validation transform stays as it is.
+
+`antialias=True` builds the training resize as `JointResize(img_size, antialias=True)`: the device pass becomes the
+antialiased one (`fod_clip_crop_resize_aa`).  The validation transform, a centre crop, resamples nothing."""
 import torch
 
 import future_od.datasets.transforms as T
@@ -76,14 +79,16 @@ class SyntheticLoader:
 
 def get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_aug=None,
                      val_annotated_frame_override=None, filter_offsets=None, val_batch_size=None, steps_per_epoch=None,
-                     val_steps=None, raw_size=None, photometric=None):
+                     val_steps=None, raw_size=None, antialias=False, photometric=None):
     """-> (train_loader, {"val": val_loader}); `train_batch_size` is GLOBAL (reference :110-112).  `offsets` may be a
     dict {"train": ..., "val": ...} (reference :64-68).  `random_aug`: a joint transform (the reference's default is
     `T.RandomSizedCrop(0.5, 1.0)`) switches both loaders to raw uint8 frames of `raw_size` (default: the camera's
     `nu_scenes.ORIGINAL_IMSIZE`) plus the reference's transforms, applied by `DevicePrefetcher`; None (the default
     here) keeps the plain source.  `photometric`: a `T.JointPhotometricDistortion` appended to the training transform
-    (it needs a `random_aug`: the plain source has no device pass to apply it in).  The filter arguments exist for call compatibility; the synthetic source has no
-    offsets to filter."""
+    (it needs a `random_aug`: the plain source has no device pass to apply it in).  `antialias`: the training
+    `JointResize` antialiases (it needs a `random_aug` for the same reason); it is a bool and nothing else, so a
+    photometric step passed by position -- `antialias` stands where that used to land -- raises instead of being read
+    as a flag.  The filter arguments exist for call compatibility; the synthetic source has no offsets to filter."""
     size = img_size
     if isinstance(offsets, dict):
         assert "train" in offsets and "val" in offsets
@@ -100,9 +105,14 @@ def get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_a
     if photometric is not None and random_aug is None:
         raise ValueError("photometric needs a random_aug: without one the loaders yield the plain source, which no "
                          "device transform touches")
+    if not isinstance(antialias, bool):       # it stands in front of `photometric`: a step passed by position lands here
+        raise TypeError(f"antialias is True or False, got {type(antialias).__name__} (pass photometric= by keyword)")
+    if antialias and random_aug is None:
+        raise ValueError("antialias needs a random_aug: without one the loaders yield the plain source, which no "
+                         "device transform resizes")
     if random_aug is not None:
         raw_size = tuple(raw_size) if raw_size is not None else nu_scenes.ORIGINAL_IMSIZE
-        train_tf = T.JointCompose([random_aug, T.JointResize(size=img_size)]
+        train_tf = T.JointCompose([random_aug, T.JointResize(size=img_size, antialias=bool(antialias))]
                                   + ([photometric] if photometric is not None else []))
         val_tf = T.JointCompose([T.JointCenterCrop(size=img_size)])
     train = SyntheticLoader(size, offsets, per_gpu, steps, rank, world, seed=1234, raw_size=raw_size,
@@ -113,8 +123,8 @@ def get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_a
 
 
 def get_nuim_loaders(img_size, offsets, args, config, train_batch_size, random_aug=None,
-                     val_annotated_frame_override=None, *, photometric=None, **kw):
+                     val_annotated_frame_override=None, *, antialias=False, photometric=None, **kw):
     """Reference runs/_loader.py:10-50: NuImages clips are addressed by FRAME INDEX offsets around the annotated frame
     (`nu_images.ANNOTATED_FRAME + offset`); only their count matters to the synthetic source."""
     return get_nusc_loaders(img_size, offsets, args, config, train_batch_size, random_aug,
-                            val_annotated_frame_override, photometric=photometric, **kw)
+                            val_annotated_frame_override, antialias=antialias, photometric=photometric, **kw)

@@ -14,6 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import future_od.datasets.transforms as T  # noqa: E402
 from future_od.models.st_detr import SpatioTemporalDETRArgs  # noqa: E402
 from future_od.utils.distributed import init_distributed_and_device_  # noqa: E402
 from runs._helper import build_base_parser, get_lr_func, get_trainer, setup_optimizer  # noqa: E402
@@ -32,7 +33,10 @@ def train(model, args, detr_args, config):
     until = (int(args.epochs * 0.60), args.epochs)
     trainer = None
     for k, ((size, global_batch), last_epoch) in enumerate(zip(stages, until)):
-        loaders = get_nusc_loaders(size, offsets=OFFSETS, config=config, args=args, train_batch_size=global_batch)
+        aug = {}
+        if getattr(args, "antialias", False):   # raw camera frames, the reference's crop, the antialiased device resize
+            aug = dict(random_aug=T.RandomSizedCrop(0.5, 1.0), antialias=True)
+        loaders = get_nusc_loaders(size, offsets=OFFSETS, config=config, args=args, train_batch_size=global_batch, **aug)
         if trainer is None:
             trainer = get_trainer(args, config, detr_args, schedule, model, optimizer, *loaders)
         else:
@@ -57,6 +61,9 @@ def build_parser():
     parser.add_argument("--accumulate", default=1, type=int,
                         help="gradient accumulation: one optimizer update per this many batches (each normalised by "
                              "its own number of boxes); default: 1, none")
+    parser.add_argument("--antialias", action="store_true",
+                        help="train on raw camera frames through the reference's RandomSizedCrop(0.5, 1.0) and an "
+                             "ANTIALIASED device resize (JointResize(..., antialias=True)); default: the plain source")
     return parser
 
 

@@ -79,6 +79,33 @@ int fod_multi_accum(const long* pairs, const long* numel, const int* blk_tensor,
 int fod_clip_crop_resize_photo(const unsigned char* src, float* dst, int B, int L, int C, int H0, int W0, int H, int W,
                                long src_stride_b, long src_stride_l, const int* plans, const float* mean,
                                const float* std, const float* photo, fod_stream_t stream);
+/* fod_clip_crop_resize with ANTIALIASED resampling: where the crop rectangle is larger than the output, every output
+ * value averages the whole source footprint under a triangle filter instead of sampling two taps per axis (which at a
+ * ratio of 2 never reads half of the source).  The definition is
+ *   torch.nn.functional.interpolate(crop, size=(H, W), mode="bilinear", align_corners=False, antialias=True)
+ * on the (clamped) crop rectangle of the raw 0..255 values, then the pixel pipeline of fod_clip_crop_resize.  Per axis,
+ * with n_in the rectangle's extent and n_out the output's:
+ *   scale = n_in / n_out,   sup = max(scale, 1)
+ *   for output index i:   c = scale * (i + 0.5),   lo = max(0, int(c - sup + 0.5)),   hi = min(n_in, int(c + sup + 0.5))
+ *   w_j = max(0, 1 - |(j - c + 0.5) / sup|)  for j in [lo, hi),  each divided by their sum
+ * (int() truncates towards zero).  The horizontal pass runs first, the vertical pass second, both in f32 on the 0..255
+ * values; then ((v / 255) - mean[c]) / std[c].  Taps are clamped to the crop rectangle, never to the frame: no pixel
+ * outside the rectangle reaches the output.  flip mirrors the output columns.  A rectangle of the output's size comes
+ * out bit-equal to fod_clip_crop_resize (the weights are 1 and 0); an enlarged axis has the weights of plain bilinear.
+ * (The kernel forms x / sup and w / sum as products with one reciprocal per axis and output: within an ulp of the
+ * quotient, exact where sup or the sum is 1.)
+ * Arguments, the plan rows (read from device memory and clamped into the frame), the checks and the 16-byte alignment
+ * are fod_clip_crop_resize's, plus
+ *   photo: NULL, or DEVICE f32 [B][5] as fod_clip_crop_resize_photo takes it: steps 1-5 of that map are then applied to
+ *   the antialiased sample / 255 before it is normalised (C must then be 3; anything else is FOD_ERR_ARG).  The row is
+ *   sanitised as there; a neutral row gives the bits of a NULL photo.
+ * The footprint follows the clamped rectangle, per clip and per axis, at run time.  What is accepted is decided from
+ * (H0, W0, H, W) alone, before any launch and never from plan contents: H0 <= 4 * H and W0 <= 4 * W (a rectangle lies
+ * inside its frame, so no axis is reduced by more than 4); a larger frame is FOD_ERR_ARG and nothing is written.
+ * Not this: torchvision's uint8 path with integer weights (this is the float path's definition), bicubic. */
+int fod_clip_crop_resize_aa(const unsigned char* src, float* dst, int B, int L, int C, int H0, int W0, int H, int W,
+                            long src_stride_b, long src_stride_l, const int* plans, const float* mean,
+                            const float* std, const float* photo, fod_stream_t stream);
 /* Visualisation: one frame of each sample of a clip as an 8-bit RGB picture with box outlines painted on it, in ONE
  * launch (the reference's revert_imagenet_normalization + draw_boxes + `* 255` + `.byte()`, which it runs on the host
  * after copying the whole f32 clip there).  future_od/utils/visualization.py (draw_boxes, render) is the CPU form.
