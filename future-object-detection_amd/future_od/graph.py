@@ -628,13 +628,17 @@ class GraphedPredict(_GraphedInference):
     the batch carries (labels, say) is ignored and never staged.  Returns the dict of `predict` as the graph's static
     outputs, valid until the next call; nothing is read back.  Parameters are read when the graph runs (GraphedForward)."""
 
-    def __init__(self, model, top_k=100, score_threshold=0.0, per_query=False, warmup=1, attention=False):
+    def __init__(self, model, top_k=100, score_threshold=0.0, per_query=False, warmup=1, attention=False, *, nms=None,
+                 nms_class_agnostic=False):
         super().__init__(model, warmup)
         self.top_k, self.score_threshold, self.per_query = int(top_k), float(score_threshold), bool(per_query)
         self.attention = bool(attention)     # predict's option: the attention-map launch is part of the captured graph
+        # predict's duplicate suppression: its launch is a node of the captured graph as well, nothing is read back
+        self.nms, self.nms_class_agnostic = (None if nms is None else float(nms)), bool(nms_class_agnostic)
 
     def _run(self, data):
-        return self.model.predict(data, self.top_k, self.score_threshold, self.per_query, attention=self.attention)
+        return self.model.predict(data, self.top_k, self.score_threshold, self.per_query, attention=self.attention,
+                                  nms=self.nms, nms_class_agnostic=self.nms_class_agnostic)
 
     def _inputs(self, data):
         return self.model.predict_inputs(data)

@@ -146,7 +146,8 @@ class SpatioTemporalDETR(nn.Module):
         return {k: data[k] for k in keys}
 
     @torch.no_grad()
-    def predict(self, data, top_k=100, score_threshold=0.0, per_query=False, box_map=None, attention=False):
+    def predict(self, data, top_k=100, score_threshold=0.0, per_query=False, box_map=None, attention=False, *,
+                nms=None, nms_class_agnostic=False):
         """Detections for frames WITHOUT annotations: the core exactly as `forward` calls it, then one launch
         (ops.detect_select) in place of the reference's post-processing chain (st_detr.py:190-234, ConditionalDETR's
         PostProcess, demo.ipynb:171-172,245) -- no targets, no matcher, no loss, no AP bookkeeping, no host sync.
@@ -160,7 +161,14 @@ class SpatioTemporalDETR(nn.Module):
         grid) -- and "attention_frames" i32 [J], the clip frame of each image.  ONE more launch (ops.attn_maps with
         `query` as its index table; padding rows are zeros), nothing read back.  'attend one at a time': a map sums to 1
         per image; 'attend all at once': the ONE memory's keys are returned split into its frames, and a map sums to 1
-        over all of them.  Off (the default) nothing is tapped and no launch, key or number changes."""
+        over all of them.  Off (the default) nothing is tapped and no launch, key or number changes.
+        `nms` (None: off, and no launch, key or bit differs): an IoU threshold in [0, 1] -- ONE more launch
+        (ops.detect_nms) right after the selection, in place on its outputs and before the attention launch: greedy
+        hard suppression in row order, a row dropped iff a kept earlier row of its class (`nms_class_agnostic`: of any
+        class) overlaps it with inter > nms * union.  The survivors move to the front, `count` becomes their number, and
+        the dict gains "source" i32 [B,K], the row of the unsuppressed result each row came from (-1 for padding);
+        "attention" then holds the maps of the surviving rows in their new order.  `top_k` is the number of CANDIDATES
+        that enter suppression: nothing is re-filled from beyond it, so fewer than `top_k` rows may come back."""
         if self.training:
             raise RuntimeError("predict: evaluation only (model.eval()); dropout would make the detections random")
         images = data["video"]
@@ -184,6 +192,9 @@ class SpatioTemporalDETR(nn.Module):
             outputs["pred_logits"].detach().float().contiguous(), outputs["pred_boxes"].detach().float().contiguous(),
             H, W, top_k, score_threshold, per_query, box_map)
         out = {"scores": scores, "labels": labels, "boxes": boxes, "query": query, "count": count}
+        if nms is not None:
+            out["source"] = ops.detect_nms(scores, labels, boxes, query, count, nms, nms_class_agnostic,
+                                           out=(scores, labels, boxes, query, count, torch.empty_like(labels)))[5]
         if tap is not None:
             out["attention"] = tap.maps(self._model.detector.decoder.layers[-1].self_attend.Nhead, query)
             first, step = tap.frames[0], (tap.frames[1] - tap.frames[0] if len(tap.frames) > 1 else 1)

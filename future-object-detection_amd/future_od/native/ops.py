@@ -1397,6 +1397,81 @@ def detect_select(logits, boxes, img_h, img_w, top_k=100, score_threshold=0.0, p
     return scores, labels, boxes_px, query, count
 
 
+def _detect_nms_cpu(scores, labels, boxes, query, count, thr, class_agnostic):
+    """The definition of fod_detect_nms (include/fod_ext.h) on host tensors, sample by sample: f32 tensor operations,
+    each rounded once; a row's test against all later rows is one vector expression."""
+    B, K = scores.shape
+    out = (torch.zeros_like(scores), torch.full_like(labels, -1), torch.zeros_like(boxes), torch.full_like(query, -1),
+           torch.zeros_like(count), torch.full_like(labels, -1))
+    thr = torch.tensor(thr, dtype=torch.float32)
+    zero = torch.zeros((), dtype=torch.float32)
+    for b in range(B):
+        n = min(max(int(count[b]), 0), K)
+        bx, lb = boxes[b, :n], labels[b, :n]
+        finite = torch.isfinite(bx).all(dim=1)
+        x0, y0, x1, y1 = bx.unbind(dim=1)
+        area = torch.maximum(x1 - x0, zero) * torch.maximum(y1 - y0, zero)
+        gone = torch.zeros(n, dtype=torch.bool)
+        for i in range(n):
+            if gone[i] or not finite[i]:
+                continue
+            iw = torch.maximum(torch.minimum(x1[i], x1[i + 1:]) - torch.maximum(x0[i], x0[i + 1:]), zero)
+            ih = torch.maximum(torch.minimum(y1[i], y1[i + 1:]) - torch.maximum(y0[i], y0[i + 1:]), zero)
+            inter = iw * ih
+            uni = (area[i] + area[i + 1:]) - inter
+            hit = (inter > thr * uni) & finite[i + 1:]
+            if not class_agnostic:
+                hit &= lb[i + 1:] == lb[i]
+            gone[i + 1:] |= hit
+        src = torch.nonzero(~gone).flatten()
+        m = src.numel()
+        for o, t in zip(out[:4], (scores, labels, boxes, query)):
+            o[b, :m] = t[b, src]
+        out[4][b] = m
+        out[5][b, :m] = src.to(torch.int32)
+    return out
+
+
+def detect_nms(scores, labels, boxes, query, count, iou_threshold=0.5, class_agnostic=False, out=None):
+    """Greedy hard NMS over the five tensors of detect_select, one launch (fod_detect_nms in include/fod_ext.h has the
+    exact semantics): per sample the rows below `count` in row order, a row dropped iff a kept earlier row of its class
+    (`class_agnostic`: of any class) has inter > iou_threshold * union with it.
+    -> (scores, labels, boxes, query, count, source): the survivors at the front, padding behind them, `source` i32 [B,K]
+    the input row of every output row (-1 for padding).  `out`: six tensors of those shapes to write into instead of new
+    ones; the first five may be the inputs themselves (in place).  CPU tensors run the plain per-sample form of the same
+    definition (same bits); device tensors run the kernel."""
+    if scores.dim() != 2:
+        raise L.FodError(f"detect_nms: scores [B,K] expected, got {tuple(scores.shape)}")
+    (B, K), dev = scores.shape, scores.device
+    shapes = (("scores", torch.float32, (B, K)), ("labels", torch.int32, (B, K)), ("boxes", torch.float32, (B, K, 4)),
+              ("query", torch.int32, (B, K)), ("count", torch.int32, (B,)))
+    for t, (name, dtype, shape) in zip((scores, labels, boxes, query, count), shapes):
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise L.FodError(f"detect_nms: contiguous {name} {dtype} {list(shape)} on {dev} expected, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    thr = float(iou_threshold)
+    if not (math.isfinite(thr) and 0.0 <= thr <= 1.0):
+        raise L.FodError(f"detect_nms: iou_threshold={thr} is outside [0, 1]")
+    if B < 1 or not 1 <= K <= 1024:
+        raise L.FodError(f"detect_nms: B={B} (at least 1) and K={K} (1..1024) expected")
+    if out is None:
+        out = tuple(torch.empty_like(t) for t in (scores, labels, boxes, query, count, labels))
+    if len(out) != 6:
+        raise L.FodError("detect_nms: out is (scores, labels, boxes, query, count, source)")
+    for t, (name, dtype, shape) in zip(out, shapes + (("source", torch.int32, (B, K)),)):
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise L.FodError(f"detect_nms: contiguous out {name} {dtype} {list(shape)} on {dev} expected, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    if not scores.is_cuda:
+        res = _detect_nms_cpu(scores, labels, boxes, query, count, thr, bool(class_agnostic))
+        for o, r in zip(out, res):                         # everything was read before anything is written
+            o.copy_(r)
+        return tuple(out)
+    call("fod_detect_nms", ptr(scores), ptr(labels), ptr(boxes), ptr(query), ptr(count), B, K, thr,
+         int(bool(class_agnostic)), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(out[4]), ptr(out[5]), stream())
+    return tuple(out)
+
+
 def od_map(scores, boxes_px, anno_boxes, anno_classes, anno_active, imsize, T=10):
     _chk(scores, "scores", torch.float32); _chk(boxes_px, "boxes", torch.float32)
     _chk(anno_boxes, "anno_boxes", torch.float32)

@@ -232,6 +232,37 @@ int fod_render_labels(unsigned char* pictures, int B, int H, int W, const float*
                       const int* idents, const float* scores, const unsigned char* names, int n_names, int name_stride,
                       const unsigned char* palette, int P, const unsigned char* font, int font_first, int G, int FW,
                       int FH, int scale, int thickness, fod_stream_t stream);
+/* Duplicate suppression behind fod_detect_select: greedy hard NMS over the rows that function wrote, per sample, in ONE
+ * launch (the reference has none; torchvision.ops.nms / batched_nms is the usual host-side form).  One workgroup per
+ * sample, wave64, no scratch, no atomics, nothing between workgroups: two launches give equal bits, and the launch can
+ * be captured.  ops.detect_nms on CPU tensors is the plain form of the same definition.
+ *   scores f32 [B][K], labels i32 [B][K], boxes f32 [B][K][4] xyxy, query i32 [B][K], count i32 [B]: the five tensors
+ *        of fod_detect_select, dense.  Nothing but 4-byte alignment is required of any pointer.
+ * Candidates and order: rows j < n = min(max(count[b], 0), K) of sample b, in ROW order -- the order fod_detect_select
+ * left them in: score descending, ties by flat index.  Scores are never read for ordering; rows at or beyond count[b]
+ * are never read at all.  Row j is KEPT iff no kept row i < j suppresses it.
+ * Row i SUPPRESSES row j iff
+ *   (class_agnostic != 0  or  labels[i] == labels[j])   and   inter > iou_threshold * uni
+ * with, all in f32, every operation rounded once, no fused multiply-add:
+ *   w = max(x1 - x0, 0),  h = max(y1 - y0, 0),  area = w * h                       (inverted corners: area 0)
+ *   iw = max(min(x1_i, x1_j) - max(x0_i, x0_j), 0),  ih likewise in y,  inter = iw * ih
+ *   uni = (area_i + area_j) - inter
+ * There is no division: iou_threshold = 0.5 on boxes with small-integer corners is decided exactly, an IoU EQUAL to the
+ * threshold does not suppress, and two zero-area boxes never suppress each other (0 > 0 is false).
+ * A row with a NaN or infinite coordinate is kept and suppresses nothing: this is tested explicitly, before any min /
+ * max sees the value.
+ * Output: the survivors at the front of out_scores / out_labels / out_boxes / out_query in their original order, each
+ * row copied bit for bit; out_count[b] = their number; out_source i32 [B][K] (may be NULL) = the input row each output row
+ * came from.  Rows from out_count[b] on are the padding of fod_detect_select: score 0, label -1, query -1, box 0, and
+ * source -1.  Every one of the B * K output rows is written, by exactly one thread.
+ * Every output may alias its input (in place): the workgroup holds all rows of its sample before it writes any.
+ * class_agnostic = 0 compares labels; anything else compares boxes only.
+ * FOD_ERR_ARG before any launch: K outside 1..1024 (the limit of fod_detect_select: every result of it is accepted);
+ * B < 1; an iou_threshold that is not finite or outside [0, 1]; a NULL operand other than out_source.
+ * Not this: soft-NMS, a division-based `inter / uni > thr` where the two round differently, suppression across samples. */
+int fod_detect_nms(const float* scores, const int* labels, const float* boxes, const int* query, const int* count, int B,
+                   int K, float iou_threshold, int class_agnostic, float* out_scores, int* out_labels, float* out_boxes,
+                   int* out_query, int* out_count, int* out_source, fod_stream_t stream);
 
 #ifdef __cplusplus
 }

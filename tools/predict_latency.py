@@ -7,7 +7,10 @@ forward's.
 
     python tools/predict_latency.py --out profiles/predict_latency.json
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/predict_latency.py --predict-only --replays 5
-        (a run of its own: the duration of detect_select_kernel is read from DIR's kernel statistics)"""
+        (a run of its own: the duration of detect_select_kernel is read from DIR's kernel statistics)
+    ... --predict-only --replays 5 --nms 0.5 [--top-k 300]
+        (duplicate suppression as one more node of the graph: detect_nms_kernel stands beside detect_select_kernel in
+        the same statistics; tools/measure_nms.py measures the two on rows whose suppressed share is set)"""
 import argparse
 import json
 import os
@@ -28,6 +31,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--top-k", type=int, default=100)
     ap.add_argument("--size", type=int, nargs=4, default=[2, 6, 900, 1600], metavar=("B", "T", "H", "W"))
+    ap.add_argument("--nms", type=float, default=None, metavar="THR",
+                    help="predict(nms=THR): one fod_detect_nms launch behind the selection, inside the graph")
+    ap.add_argument("--nms-class-agnostic", action="store_true")
     ap.add_argument("--predict-only", action="store_true", help="replay GraphedPredict alone (for a kernel trace)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -47,7 +53,7 @@ def main():
                                                      pretrained_backbone=False))
     model.eval()
     data = make_batch(B, T, H, W, seed=1234, device=dev)
-    passes = {"predict": GraphedPredict(model, top_k=a.top_k)}
+    passes = {"predict": GraphedPredict(model, top_k=a.top_k, nms=a.nms, nms_class_agnostic=a.nms_class_agnostic)}
     if not a.predict_only:
         passes["forward"] = GraphedForward(model)
     for _ in range(a.warmup + 1):                    # the first call captures
@@ -68,6 +74,8 @@ def main():
             "extent": {"B": B, "T": T, "H": H, "W": W, "dtype": "bf16", "num_images": T - 1, "top_k": a.top_k},
             "replays_each": a.replays, "device": torch.cuda.get_device_name(0),
             "detections": [int(c) for c in det["count"].tolist()]}
+    if a.nms is not None:
+        line["nms"] = {"iou_threshold": a.nms, "class_agnostic": a.nms_class_agnostic}
     for k, ts in times.items():
         line[f"{k}_ms_median"] = round(statistics.median(ts), 4)
         line[f"{k}_ms_min"] = round(min(ts), 4)
