@@ -1491,6 +1491,119 @@ def od_map(scores, boxes_px, anno_boxes, anno_classes, anno_active, imsize, T=10
     return confs, is_pos, sizes, num_annos
 
 
+def _detect_od_map_cpu(scores, labels, boxes, query, count, anno_boxes, anno_classes, anno_active, H, W, C, P, T):
+    """The definition of fod_detect_od_map (include/fod_ext.h) on host tensors, sample by sample: f32 tensor operations,
+    each rounded once; a sample's IoU table is one vector expression, the greedy walk is a loop."""
+    (B, K), N, C1 = scores.shape, anno_boxes.shape[1], C + 1
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    zero, eps = f32(0.0), f32(1e-7)
+    s0, s1 = f32((1.0 / 24) * (1.0 / 64) * float(H) * float(W)), f32((1.0 / 4) * (1.0 / 12) * float(H) * float(W))
+    confs = torch.zeros((T, C1, B * P), dtype=torch.float32)
+    is_pos = torch.zeros((T, C1, B * P), dtype=torch.bool)
+    sizes = torch.zeros((C1, 4, B * P), dtype=torch.bool)
+    num_annos = torch.zeros((C1, 4), dtype=torch.int64)
+
+    def flags(bx, finite):                               # [R,4]: column 0 always, 1..3 from the unclamped area
+        area = (bx[:, 2] - bx[:, 0]) * (bx[:, 3] - bx[:, 1])
+        return torch.stack([torch.ones_like(finite), finite & (area <= s0), finite & (s0 < area) & (area <= s1),
+                            finite & (s1 < area)], dim=1)
+
+    def clamped_area(bx):
+        return torch.maximum(bx[:, 2] - bx[:, 0], zero) * torch.maximum(bx[:, 3] - bx[:, 1], zero)
+
+    for b in range(B):
+        n = min(max(int(count[b]), 0), K)
+        a_fin = torch.isfinite(anno_boxes[b]).all(dim=1)
+        a_flags = flags(anno_boxes[b], a_fin)
+        ab = torch.where(a_fin[:, None], anno_boxes[b], zero)
+        a_area = clamped_area(ab)
+        for c in range(C1):
+            counted = (anno_active[b] == 1) & ((anno_classes[b] == c) if c < C else torch.ones(N, dtype=torch.bool))
+            num_annos[c] += (counted[:, None] & a_flags).sum(dim=0)
+            if c < C:
+                rows = torch.nonzero(labels[b, :n] == c).flatten()[:P]
+            else:
+                seen, first = set(), []
+                for j, q in enumerate(query[b, :n].tolist()):
+                    if q not in seen:
+                        seen.add(q)
+                        first.append(j)
+                rows = torch.tensor(first[:P], dtype=torch.int64)
+            m = rows.numel()
+            if m == 0:
+                continue
+            pb = boxes[b, rows]
+            p_fin = torch.isfinite(pb).all(dim=1)
+            at = slice(b * P, b * P + m)
+            confs[:, c, at] = scores[b, rows]
+            sizes[c, :, at] = flags(pb, p_fin).T
+            inter = torch.maximum(torch.minimum(pb[:, None, 2], ab[None, :, 2]) - torch.maximum(pb[:, None, 0], ab[None, :, 0]), zero) * \
+                torch.maximum(torch.minimum(pb[:, None, 3], ab[None, :, 3]) - torch.maximum(pb[:, None, 1], ab[None, :, 1]), zero)
+            iou = (inter + eps) / (((clamped_area(pb)[:, None] + a_area[None]) - inter) + eps)
+            iou = torch.where(iou == iou, iou, zero)       # a NaN never wins the comparison `iou > best`
+            for t in range(T):
+                thr = f32(0.5 + t * 0.05)
+                free = counted & a_fin
+                for k in range(m):
+                    if not p_fin[k]:
+                        continue
+                    cand = torch.where(free, iou[k], zero)
+                    best = int(cand.argmax())                # the first of equal maxima: the lowest index
+                    if cand[best] >= thr:
+                        is_pos[t, c, b * P + k] = True
+                        free[best] = False
+    return confs, is_pos, sizes, num_annos
+
+
+def detect_od_map(scores, labels, boxes, query, count, anno_boxes, anno_classes, anno_active, imsize, num_classes,
+                  per_class=50, T=10, out=None):
+    """The AP bookkeeping of `od_map` over detection ROWS, one launch (fod_detect_od_map in include/fod_ext.h has the
+    exact semantics): the five tensors of detect_select / detect_nms plus the dense annotations of od_map (boxes f32
+    [B,N,4], classes i64 [B,N], active i64 [B,N]) -> (confs f32 [T,C1,B*P], is_positive bool [T,C1,B*P], size_categories
+    bool [C1,4,B*P], num_annos i64 [C1,4]) with C1 = num_classes + 1 and P = min(per_class, K) slots per sample and
+    class.  Row order is the ranking; the generic class sees each query's first row.  `out`: four tensors of those shapes
+    (bool or uint8 for the two flag tensors) to write into instead of new ones.  CPU tensors run the plain per-sample form
+    of the same definition (same bytes); device tensors run the kernel."""
+    if scores.dim() != 2 or anno_classes.dim() != 2:
+        raise L.FodError(f"detect_od_map: scores [B,K] and anno_classes [B,N] expected, got {tuple(scores.shape)} and "
+                         f"{tuple(anno_classes.shape)}")
+    (B, K), N, dev = scores.shape, anno_classes.shape[1], scores.device
+    shapes = (("scores", torch.float32, (B, K)), ("labels", torch.int32, (B, K)), ("boxes", torch.float32, (B, K, 4)),
+              ("query", torch.int32, (B, K)), ("count", torch.int32, (B,)), ("anno_boxes", torch.float32, (B, N, 4)),
+              ("anno_classes", torch.int64, (B, N)), ("anno_active", torch.int64, (B, N)))
+    for t, (name, dtype, shape) in zip((scores, labels, boxes, query, count, anno_boxes, anno_classes, anno_active), shapes):
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise L.FodError(f"detect_od_map: contiguous {name} {dtype} {list(shape)} on {dev} expected, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    C, T, per_class = int(num_classes), int(T), int(per_class)
+    if B < 1 or not 1 <= K <= 1024 or not 1 <= N <= 1024:
+        raise L.FodError(f"detect_od_map: B={B} (at least 1), K={K} (1..1024) and N={N} (1..1024) expected")
+    if C < 1 or per_class < 1 or not 1 <= T <= 16:
+        raise L.FodError(f"detect_od_map: num_classes={C} (at least 1), per_class={per_class} (at least 1) and T={T} "
+                         f"(1..16) expected")
+    H, W = float(imsize[0]), float(imsize[1])
+    C1, P = C + 1, min(per_class, K)
+    shapes = (("confs", (torch.float32,), (T, C1, B * P)), ("is_positive", (torch.bool, torch.uint8), (T, C1, B * P)),
+              ("size_categories", (torch.bool, torch.uint8), (C1, 4, B * P)), ("num_annos", (torch.int64,), (C1, 4)))
+    if out is None:
+        out = tuple(torch.empty(shape, dtype=dtypes[0], device=dev) for _name, dtypes, shape in shapes)
+    if len(out) != 4:
+        raise L.FodError("detect_od_map: out is (confs, is_positive, size_categories, num_annos)")
+    for t, (name, dtypes, shape) in zip(out, shapes):
+        if tuple(t.shape) != shape or t.dtype not in dtypes or t.device != dev or not t.is_contiguous():
+            raise L.FodError(f"detect_od_map: contiguous out {name} {dtypes[0]} {list(shape)} on {dev} expected, got "
+                             f"{t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    if not scores.is_cuda:
+        res = _detect_od_map_cpu(scores, labels, boxes, query, count, anno_boxes, anno_classes, anno_active, H, W, C, P, T)
+        for o, r in zip(out, res):
+            o.copy_(r)
+        return tuple(out)
+    call("fod_detect_od_map", ptr(scores), ptr(labels), ptr(boxes), ptr(query), ptr(count), ptr(anno_boxes),
+         ptr(anno_classes), ptr(anno_active), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), B, K, N, C, P, T, H, W,
+         stream())
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------------------------ tracker baseline
 TRACKER_MODES = {None: 0, "linear": 1, "percentual": 2, "average": 3}
 

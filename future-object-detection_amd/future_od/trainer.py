@@ -159,6 +159,72 @@ class Trainer:
             self._model.to(self._device)
         self._run_eval()
 
+    @torch.no_grad()
+    def evaluate_detections(self, top_k=100, score_threshold=0.0, per_query=False, nms=None, nms_class_agnostic=False,
+                            per_class=50):
+        """The AP, precision and recall of what `predict` RETURNS with these options, over every validation loader: the
+        detection rows (the survivors of the suppression with `nms=`) go through the AP bookkeeping in their order, one
+        more launch per batch (future_od.utils.od_map.DetectionEvaluator), instead of the dense scores `_run_epoch` reads.
+        Evaluation mode, under the weight EMA when one is attached, through a captured `GraphedPredict` where the
+        evaluation pass would be captured and eager `predict` otherwise, capped at ~10k images as `_run_epoch` is.
+        Prints `_run_epoch`'s AP lines and a precision / recall line; -> {loader name: the evaluator's dict}.  Trains
+        nothing and leaves the model in the mode it was in.  One process only: nothing is gathered between ranks.
+        (A method, not a constructor keyword: the constructor is the reference's plus `ema`.)"""
+        if self._distributed and distrib.is_initialized() and distrib.get_world_size() > 1:
+            raise NotImplementedError("Trainer.evaluate_detections: detections are not gathered between ranks; "
+                                      "evaluate in one process")
+        from future_od.graph import GraphedPredict
+        from future_od.utils.od_map import DetectionEvaluator
+        model = self._model_no_ddp
+        if not self._distributed:
+            self._model.to(self._device)
+        was_training, drop_mode = model.training, getattr(model._model, "drop_mode", None)
+        model.train(False)
+        options = dict(top_k=top_k, score_threshold=score_threshold, per_query=per_query, nms=nms,
+                       nms_class_agnostic=nms_class_agnostic)
+        graphed = GraphedPredict(model, **options) if self._eval_graph_allowed() else None
+        results = {}
+        try:
+            with self._ema.applied() if self._ema is not None else contextlib.nullcontext():
+                for name, loader in self._val_loaders.items():
+                    if hasattr(model._model, "drop_mode"):
+                        model._model.drop_mode = name
+                    batch_size = getattr(loader, "batch_size", 1) or 1
+                    evaluator = DetectionEvaluator(model._criterion.num_classes, per_class)
+                    for i, data in enumerate(DevicePrefetcher(loader, self._device)):
+                        if EXIT.is_set() or i * batch_size >= 10000:         # the cap of the AP bookkeeping
+                            break
+                        det = None
+                        if graphed is not None:
+                            try:
+                                det = graphed(data)
+                            except CaptureError as e:
+                                print(f"[fod] captured predict unavailable ({e}); launching eagerly")
+                                graphed = None
+                        if det is None:
+                            det = model.predict(data, **options)
+                        evaluator.update(det, data)
+                    if not len(evaluator):
+                        continue
+                    ap = results[name] = evaluator.aggregate(self._device)
+                    fmt = lambda xs: " ".join(f"{float(e):.3f}" for e in xs)
+                    print(f"[{name}] detections of predict({', '.join(f'{k}={v}' for k, v in options.items())}), "
+                          f"per_class={per_class}:")
+                    print("AP50 for epoch is:", fmt(ap["all"][0, :, 0]))
+                    print("MAP for epoch is:", fmt(ap["threshavg"][:, 0]))
+                    print("MAP for small objects is:", fmt(ap["threshavg"][:, 1]))
+                    print("MAP for medium objects is:", fmt(ap["threshavg"][:, 2]))
+                    print("MAP for large objects is:", fmt(ap["threshavg"][:, 3]))
+                    op = ap["operating_point"]
+                    print("Precision / recall at IoU 0.5 (generic class):", f"{float(op['precision'][-1]):.3f} /",
+                          f"{float(op['recall'][-1]):.3f}  ({int(op['true_positives'][-1])} of "
+                          f"{int(op['detections'][-1])} detections, {int(op['annotations'][-1])} annotations)")
+        finally:
+            model.train(was_training)
+            if drop_mode is not None:
+                model._model.drop_mode = drop_mode
+        return results
+
     # ------------------------------------------------------------------ internals
     def _setup_wandb(self, tags):
         c = self._wandb_config
@@ -202,6 +268,13 @@ class Trainer:
                                             accumulate=self._accumulate)
         return g
 
+    def _eval_graph_allowed(self):
+        """Whether an evaluation pass is captured here (`_graphed_forward`, `evaluate_detections`)."""
+        from future_od.models.set_criterion import device_matching_enabled
+        dev = torch.device(self._device)
+        return bool(SW.FOD_GRAPH_EVAL and not self._distributed and dev.type == "cuda"
+                    and device_matching_enabled(dev) and not torch.is_grad_enabled())
+
     def _graphed_forward(self):
         """The evaluation pass as one captured hipGraph (future_od/graph.py: GraphedForward), same conditions as the
         captured training step; FOD_GRAPH_EVAL=0 keeps the eager loop."""
@@ -209,11 +282,7 @@ class Trainer:
         if g is False:
             return None
         if g is None:
-            from future_od.models.set_criterion import device_matching_enabled
-            dev = torch.device(self._device)
-            ok = (SW.FOD_GRAPH_EVAL and not self._distributed and dev.type == "cuda"
-                  and device_matching_enabled(dev) and not torch.is_grad_enabled())
-            if not ok:
+            if not self._eval_graph_allowed():
                 self._graphed_eval = False
                 return None
             from future_od.graph import GraphedForward

@@ -1,6 +1,10 @@
 """AP bookkeeping (reference future_od/utils/od_map.py): the per-batch greedy TP/FP assignment runs
 as one HIP kernel (fod_od_map, one wave per sample x class x IoU threshold) instead of the
-reference's 50-step tensor loop; the end-of-epoch aggregation is small host math."""
+reference's 50-step tensor loop; the end-of-epoch aggregation is small host math.
+
+The same bookkeeping over the detection ROWS `predict` returns (fod_detect_od_map, one launch): prepare_od_map_detections,
+DetectionEvaluator and operating_point -- what top_k, score_threshold, per_query and the duplicate suppression do to AP,
+precision and recall.  Nothing of it runs unless it is called."""
 import numpy as np
 import torch
 
@@ -51,3 +55,82 @@ def aggregate_mean_average_precision(confs, is_positive, size_categories, num_an
         "generic": ap[:, -1, :],
         "generic threshavg": np.nanmean(ap[:, -1, :].numpy(), axis=0),
     }
+
+
+DETECTION_KEYS = ("scores", "labels", "boxes", "query", "count")
+
+
+@torch.no_grad()
+def prepare_od_map_detections(det, anno_boxes, anno_classes, anno_active, imsize, num_classes, per_class=50):
+    """`prepare_od_map_stuffs` for the dict of `predict` / `GraphedPredict` (suppressed by `nms=` or not) instead of dense
+    scores: the rows below `count` in their order are the ranking, class c's candidates are its first `per_class` rows,
+    the generic class's are the first row of every query (ops.detect_od_map; fod_detect_od_map in include/fod_ext.h has
+    the exact semantics).  -> confs (T,C,B*P) f32, is_positive (T,C,B*P) bool, size_categories (C,4,B*P) bool, num_annos
+    (C,4) i64 with C = num_classes + 1 and P = min(per_class, K).  One launch, nothing read back.  With every pair
+    selected (top_k = M * num_classes, threshold 0) this is `prepare_od_map_stuffs` on the same predictions, bit for bit.
+    The boxes must be in the annotations' frame: a `det` that carries a `box_map` (the batch's, or the one handed to
+    `predict`) holds boxes in the camera's frame and is refused."""
+    if det.get("box_map") is not None:
+        raise ValueError("prepare_od_map_detections: these detections went through a box_map (boxes in the camera's "
+                         "frame); the annotations are in the network's input frame")
+    B, N = anno_classes.shape[0], anno_classes.shape[-1]
+    return ops.detect_od_map(*(det[k] for k in DETECTION_KEYS), anno_boxes.reshape(B, N, 4).float().contiguous(),
+                             anno_classes.reshape(B, N).contiguous(), anno_active.reshape(B, N).contiguous(), imsize,
+                             num_classes, per_class, T=NUM_THRESHOLDS)
+
+
+def operating_point(confs, is_positive, size_categories, num_annos, t=0):
+    """What the returned rows ARE at IoU threshold `t` (0: IoU 0.5), with no ranking involved: per class, the generic
+    class last, "detections" (the filled slots: column 0 of size_categories), "true_positives", "annotations" (i64 [C])
+    and "precision" = TP / detections, "recall" = TP / annotations, "f1" = 2 TP / (detections + annotations) (f64 [C],
+    NaN where the denominator is 0), plus "iou".  Takes one batch's four tensors or the concatenated ones (num_annos
+    (C,4) or (C,4,iterations))."""
+    filled = size_categories[:, 0].bool()
+    det = filled.sum(dim=1).cpu()
+    tp = (is_positive[t].bool() & filled).sum(dim=1).cpu()
+    anno = (num_annos[:, 0] if num_annos.dim() == 2 else num_annos[:, 0].sum(dim=1)).cpu()
+    ratio = lambda a, b: torch.where(b > 0, a.double() / b.double().clamp(min=1), torch.full_like(a, float("nan"), dtype=torch.float64))
+    return {"iou": 0.5 + 0.05 * t, "detections": det, "true_positives": tp, "annotations": anno,
+            "precision": ratio(tp, det), "recall": ratio(tp, anno), "f1": ratio(2 * tp, det + anno)}
+
+
+class DetectionEvaluator:
+    """ev = DetectionEvaluator(num_classes); for batch: ev.update(model.predict(batch, ...), batch); ev.aggregate()
+
+    The AP of what `predict` RETURNS over a set of labelled batches: `update` makes one launch and keeps its four device
+    tensors (nothing is read back), `aggregate` concatenates them as the trainer's epoch does and returns
+    `aggregate_mean_average_precision`'s dict plus "operating_point"."""
+
+    def __init__(self, num_classes, per_class=50):
+        self.num_classes, self.per_class = int(num_classes), int(per_class)
+        self.reset()
+
+    def reset(self):
+        self._od = [[], [], [], []]
+
+    def __len__(self):
+        return len(self._od[0])
+
+    def update(self, det, data):
+        """`det`: the dict of `predict(data, ...)`; `data`: the batch with `boxes`, `classes`, `active` and `video`."""
+        if data.get("box_map") is not None and det.get("box_map") is None:
+            det = dict(det, box_map=data["box_map"])       # predict applied the batch's map
+        od = prepare_od_map_detections(det, data["boxes"], data["classes"], data["active"], data["video"].shape[-2:],
+                                       self.num_classes, self.per_class)
+        for kept, t in zip(self._od, od):
+            kept.append(t)
+        return od
+
+    def tensors(self):
+        """The concatenated intermediaries: confs, is_positive, size_categories (slots of all updates) and num_annos
+        (C,4,updates)."""
+        if not len(self):
+            raise RuntimeError("DetectionEvaluator: no update yet")
+        return (torch.cat(self._od[0], dim=2), torch.cat(self._od[1], dim=2), torch.cat(self._od[2], dim=2),
+                torch.stack(self._od[3], dim=2))
+
+    def aggregate(self, device=None):
+        od = self.tensors()
+        ap = aggregate_mean_average_precision(*od, od[0].device if device is None else device)
+        ap["operating_point"] = operating_point(*od)
+        return ap

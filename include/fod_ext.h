@@ -264,6 +264,49 @@ int fod_detect_nms(const float* scores, const int* labels, const float* boxes, c
                    int K, float iou_threshold, int class_agnostic, float* out_scores, int* out_labels, float* out_boxes,
                    int* out_query, int* out_count, int* out_source, fod_stream_t stream);
 
+/* AP bookkeeping over DETECTION ROWS: fod_od_map's greedy true / false-positive assignment (fod.h; reference
+ * utils/od_map.py:214-287), with the ranked candidates taken from the rows of fod_detect_select / fod_detect_nms instead
+ * of from dense scores, so that top_k, score_threshold, per_query and the suppression show in the AP.  ONE launch, one
+ * workgroup per (class, sample) with T waves of 64, one IoU threshold each; no scratch, no atomics, nothing between
+ * workgroups: two launches give equal bits, and the launch can be captured.  ops.detect_od_map on CPU tensors is the
+ * plain form of the same definition.
+ *   scores f32 [B][K], labels i32 [B][K], boxes f32 [B][K][4] xyxy, query i32 [B][K], count i32 [B]: the five tensors of
+ *        fod_detect_select / fod_detect_nms, dense.  Boxes in the frame of the annotations (no box_map).
+ *   anno_boxes f32 [B][N][4] xyxy, anno_classes i64 [B][N], anno_active i64 [B][N]: the dense annotations of fod_od_map.
+ *   C real classes, C1 = C + 1 (class C is the generic class); P candidate slots per sample and class; T thresholds.
+ * Outputs, fod_od_map's layout with P in place of min(50, M):
+ *   confs f32 [T][C1][B*P], is_positive u8 [T][C1][B*P], size_categories u8 [C1][4][B*P], num_annos i64 [C1][4].
+ * Per sample b, n = min(max(count[b], 0), K); rows at or beyond n are never read.
+ * Candidates of class c < C: the rows j < n with labels[j] == c, in row order.  Candidates of the generic class c == C:
+ * the rows j < n for which no earlier row i < j has query[i] == query[j] (each query's best surviving row; with per_query
+ * rows: every row).  In both cases only the first P candidates count, and ROW ORDER IS THE RANKING: scores are never
+ * compared.
+ * Slot b*P + k holds candidate k: confs = its score for every t; size flags as fod_od_map's: column 0 is 1, columns 1..3
+ * are  area <= s0,  s0 < area <= s1,  s1 < area  with the UNCLAMPED area (x1 - x0) * (y1 - y0) and
+ * s0 = (float)(1/24 * 1/64 * img_h * img_w), s1 = (float)(1/4 * 1/12 * img_h * img_w) formed in double.
+ * Slots k >= the number of candidates are padding: confs 0, is_positive 0, all four flags 0 (they add to no cumulative
+ * sum of the AP).
+ * Assignment, for threshold t with thr = (float)(0.5 + t * 0.05) (fod_od_map's): walk the candidates in order; each
+ * claims the still-free annotation of greatest IoU, ties to the lowest index; it is positive iff that IoU >= thr, and the
+ * annotation is then taken.  Free at the start: active == 1, and for c < C also class == c.  The IoU is fod_od_map's,
+ * in f32, every operation rounded once, no fused multiply-add:
+ *   area = max(x1 - x0, 0) * max(y1 - y0, 0),  inter = max(min(x1, X1) - max(x0, X0), 0) * (likewise in y)
+ *   iou = (inter + 1e-7f) / (((area_p + area_a) - inter) + 1e-7f)            (two zero-area boxes: IoU 1)
+ * num_annos[c][s] = the annotations of all samples that are free at the start for c, by the same size flags; written by
+ * this launch, it needs no zeroing.  Every element of every output is written exactly once.
+ * Non-finite input, tested explicitly before any min / max: a row with a NaN or infinite coordinate keeps its slot and
+ * its score, gets flags (1, 0, 0, 0), is never positive and claims nothing; an active annotation with such a coordinate
+ * counts in column 0 of num_annos only and can never be claimed.
+ * With every (query, class) pair selected (K = M * C, threshold 0) and P = min(50, M) the four outputs equal fod_od_map's
+ * on the same predictions, element for element.
+ * FOD_ERR_ARG before any launch: B < 1; K outside 1..1024; N outside 1..1024; P outside 1..K; T outside 1..16; C < 1;
+ * a NULL operand.
+ * Not this: COCO's 101-point interpolation, detections in another frame than the annotations, more than 1024 rows. */
+int fod_detect_od_map(const float* scores, const int* labels, const float* boxes, const int* query, const int* count,
+                      const float* anno_boxes, const int64_t* anno_classes, const int64_t* anno_active, float* confs,
+                      uint8_t* is_positive, uint8_t* size_categories, int64_t* num_annos, int B, int K, int N, int C,
+                      int P, int T, float img_h, float img_w, fod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
