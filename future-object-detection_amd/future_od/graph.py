@@ -645,3 +645,28 @@ class GraphedPredict(_GraphedInference):
 
     def _signature(self, data):
         return GraphedStep._signature(self._inputs(data))
+
+
+class GraphedTrackedPredict(GraphedPredict):
+    """det = GraphedTrackedPredict(model, tracker, top_k=100)(data): GraphedPredict followed by `tracker.update`
+    (future_od/utils/tracking.py) -- the track launch is one more node of the graph, and the dict gains "track" and
+    "track_hits".  The graph updates the tracker's state tensors in place, so the state persists from replay to replay
+    and every graph of this object (one per signature) advances the same tracker; `tracker.reset`, `load_state_dict` and
+    `restore` write into those tensors and stay valid between calls.  A capture runs the pass eagerly before it
+    records it: the tracker is put back afterwards, so the call that captures advances the state once, like any other."""
+
+    def __init__(self, model, tracker, top_k=100, score_threshold=0.0, per_query=False, warmup=1, attention=False, *,
+                 nms=None, nms_class_agnostic=False):
+        super().__init__(model, top_k, score_threshold, per_query, warmup, attention, nms=nms,
+                         nms_class_agnostic=nms_class_agnostic)
+        self.tracker = tracker
+
+    def _run(self, data):
+        return self.tracker.update(super()._run(data))
+
+    def _capture(self, data):
+        self.tracker.to_device(data["video"].device)         # the state must exist before anything is recorded
+        snap = self.tracker.snapshot()
+        g = super()._capture(data)
+        self.tracker.restore(snap)                            # the warm-up passes advanced it; the first replay starts here
+        return g

@@ -1604,6 +1604,123 @@ def detect_od_map(scores, labels, boxes, query, count, anno_boxes, anno_classes,
     return tuple(out)
 
 
+def _track_update_cpu(scores, labels, boxes, count, state, thr, birth, max_misses, class_agnostic, motion):
+    """The definition of fod_track_update (include/fod_ext.h) on host tensors, sample by sample, the state updated in
+    place: f32 tensor operations, each rounded once; a row's IoU with every slot is one vector expression."""
+    tb, tv, tm, ts, next_id = state
+    B, K = scores.shape
+    out_track, out_hits, out_slot = torch.full_like(labels, -1), torch.zeros_like(labels), torch.full_like(labels, -1)
+    thr, birth = torch.tensor(thr, dtype=torch.float32), torch.tensor(birth, dtype=torch.float32)
+    zero = torch.zeros((), dtype=torch.float32)
+    for b in range(B):
+        n = min(max(int(count[b]), 0), K)
+        meta, bx, lb, sc = tm[b], boxes[b, :n], labels[b, :n], scores[b, :n]
+        live = meta[:, 0] >= 0
+        gap = torch.where(live, meta[:, 3] + 1, torch.ones_like(meta[:, 3])).to(torch.float32)[:, None]
+        pred = tb[b] + tv[b] * gap if motion else tb[b].clone()
+        free_to_claim = live & torch.isfinite(pred).all(dim=1)
+        pred = torch.where(free_to_claim[:, None], pred, zero)
+        X0, Y0, X1, Y1 = pred.unbind(dim=1)
+        parea = torch.maximum(X1 - X0, zero) * torch.maximum(Y1 - Y0, zero)
+        finite = torch.isfinite(bx).all(dim=1)
+        slot_row = torch.full((tb.shape[1],), -1, dtype=torch.int64)
+        row_slot = torch.full((n,), -1, dtype=torch.int64)
+        for j in range(n):
+            if not finite[j]:
+                continue
+            seen = free_to_claim if class_agnostic else free_to_claim & (meta[:, 1] == lb[j])
+            if not seen.any():
+                continue
+            x0, y0, x1, y1 = bx[j].unbind()
+            area = torch.maximum(x1 - x0, zero) * torch.maximum(y1 - y0, zero)
+            inter = (torch.maximum(torch.minimum(x1, X1) - torch.maximum(x0, X0), zero) *
+                     torch.maximum(torch.minimum(y1, Y1) - torch.maximum(y0, Y0), zero))
+            uni = (area + parea) - inter
+            iou = torch.where(uni > 0, inter / torch.where(uni > 0, uni, torch.ones_like(uni)), zero)
+            iou = torch.where(seen, iou, torch.full_like(iou, -1.0))
+            s = int(torch.nonzero(iou == iou.max())[0])   # the greatest IoU, ties to the lowest slot
+            if inter[s] > 0 and iou[s] >= thr:
+                free_to_claim = free_to_claim.clone()
+                free_to_claim[s] = False
+                slot_row[s], row_slot[j] = j, s
+        ms = torch.nonzero(slot_row >= 0).flatten()
+        mj = slot_row[ms]
+        new = bx[mj]
+        tv[b, ms] = (new - tb[b, ms]) / gap[ms] if motion else torch.zeros_like(new)
+        tb[b, ms], ts[b, ms] = new, sc[mj]
+        meta[ms, 1], meta[ms, 2], meta[ms, 3] = lb[mj], meta[ms, 2] + 1, 0
+        out_track[b, mj], out_hits[b, mj], out_slot[b, mj] = meta[ms, 0], meta[ms, 2], ms.to(torch.int32)
+        aged = live & (slot_row < 0)
+        meta[aged, 3] += 1
+        dead = aged & (meta[:, 3] > max_misses)
+        meta[dead] = torch.tensor([-1, -1, 0, 0], dtype=torch.int32)
+        tb[b, dead], tv[b, dead], ts[b, dead] = 0.0, 0.0, 0.0
+        free = torch.nonzero(meta[:, 0] < 0).flatten()
+        cand = torch.nonzero(finite & (row_slot < 0) & (sc >= birth)).flatten()
+        r = min(free.numel(), cand.numel())
+        free, cand = free[:r], cand[:r]
+        ids = int(next_id[b]) + torch.arange(r, dtype=torch.int32)
+        tb[b, free], tv[b, free], ts[b, free] = bx[cand], 0.0, sc[cand]
+        meta[free, 0], meta[free, 1], meta[free, 2], meta[free, 3] = ids, lb[cand], 1, 0
+        out_track[b, cand], out_hits[b, cand], out_slot[b, cand] = ids, 1, free.to(torch.int32)
+        next_id[b] += r
+    return out_track, out_hits, out_slot
+
+
+def track_update(scores, labels, boxes, count, state, *, iou_threshold, birth_score, max_misses, class_agnostic, motion,
+                 out=None):
+    """One call of the tracker, one launch (fod_track_update in include/fod_ext.h has the exact semantics): the rows of
+    detect_select / detect_nms (scores f32 [B,K], labels i32 [B,K], boxes f32 [B,K,4], count i32 [B]; `query` is not
+    needed) claim the tracks of `state` = (boxes f32 [B,S,4], vel f32 [B,S,4], meta i32 [B,S,4] = (id, label, hits,
+    misses), scores f32 [B,S], next_id i32 [B]), which is updated IN PLACE.  -> (track i32 [B,K], hits i32 [B,K], slot
+    i32 [B,K]): the identity of every row (-1: none), how often it has been seen, and the slot that holds it.  `out`:
+    (track, hits) or (track, hits, slot) to write into instead of new tensors; a slot of None is not written, and comes
+    back as None.  CPU tensors run the plain per-sample form of the same definition (same bytes); device tensors run the
+    kernel."""
+    if scores.dim() != 2 or len(state) != 5 or state[0].dim() != 3:
+        raise L.FodError("track_update: scores [B,K] and state = (boxes [B,S,4], vel, meta, scores, next_id) expected")
+    (B, K), S, dev = scores.shape, state[0].shape[1], scores.device
+    shapes = (("scores", torch.float32, (B, K)), ("labels", torch.int32, (B, K)), ("boxes", torch.float32, (B, K, 4)),
+              ("count", torch.int32, (B,)), ("state boxes", torch.float32, (B, S, 4)), ("state vel", torch.float32, (B, S, 4)),
+              ("state meta", torch.int32, (B, S, 4)), ("state scores", torch.float32, (B, S)),
+              ("state next_id", torch.int32, (B,)))
+    for t, (name, dtype, shape) in zip((scores, labels, boxes, count) + tuple(state), shapes):
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise L.FodError(f"track_update: contiguous {name} {dtype} {list(shape)} on {dev} expected, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    thr, birth, max_misses = float(iou_threshold), float(birth_score), int(max_misses)
+    if not (math.isfinite(thr) and 0.0 <= thr <= 1.0):
+        raise L.FodError(f"track_update: iou_threshold={thr} is outside [0, 1]")
+    if B < 1 or not 1 <= K <= 1024 or not 1 <= S <= 1024 or max_misses < 0:
+        raise L.FodError(f"track_update: B={B} (at least 1), K={K} (1..1024), S={S} (1..1024) and max_misses={max_misses} "
+                         f"(not negative) expected")
+    if out is None:
+        out = tuple(torch.empty_like(labels) for _ in range(3))
+    if len(out) == 2:
+        out = tuple(out) + (None,)
+    if len(out) != 3 or out[0] is None or out[1] is None:
+        raise L.FodError("track_update: out is (track, hits) or (track, hits, slot)")
+    for t, name in zip(out, ("track", "hits", "slot")):
+        if t is not None and (tuple(t.shape) != (B, K) or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous()):
+            raise L.FodError(f"track_update: contiguous out {name} {torch.int32} {[B, K]} on {dev} expected, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    # the state is written while the detections are read: no tensor may serve twice
+    ptrs = [t.data_ptr() for t in (scores, labels, boxes, count) + tuple(state) + tuple(out) if t is not None]
+    if len(set(ptrs)) != len(ptrs):
+        raise L.FodError("track_update: the detections, the five state tensors and the outputs must be distinct tensors")
+    if not scores.is_cuda:
+        res = _track_update_cpu(scores, labels, boxes, count, state, thr, birth, max_misses, bool(class_agnostic),
+                                bool(motion))
+        for o, r in zip(out, res):
+            if o is not None:
+                o.copy_(r)
+        return tuple(out)
+    call("fod_track_update", ptr(scores), ptr(labels), ptr(boxes), ptr(count), B, K, ptr(state[0]), ptr(state[1]),
+         ptr(state[2]), ptr(state[3]), ptr(state[4]), S, thr, birth, max_misses, int(bool(class_agnostic)),
+         int(bool(motion)), ptr(out[0]), ptr(out[1]), ptr(out[2]), stream())
+    return tuple(out)
+
+
 # ------------------------------------------------------------------------------------------------ tracker baseline
 TRACKER_MODES = {None: 0, "linear": 1, "percentual": 2, "average": 3}
 

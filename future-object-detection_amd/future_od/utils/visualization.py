@@ -401,6 +401,28 @@ def render_detections(video, det, min_score=0.5, frame_idx=None, thickness=3, pa
     return _render(video, det["boxes"], labels.masked_fill(hidden, -1), frame_idx, thickness, palette, captions, det)
 
 
+def track_colour_index(det, min_hits=1, palette=COLOURS):
+    """What `render_tracks` hands `render` as labels, i32 [B, K]: track % len(palette) for the rows that carry an
+    identity seen at least `min_hits` times, -1 (not drawn) for every other row."""
+    track, hits = det["track"], det["track_hits"]
+    return torch.where((track >= 0) & (hits >= min_hits), track % palette.shape[0], torch.full_like(track, -1))
+
+
+def render_tracks(video, det, min_hits=1, frame_idx=None, thickness=3, palette=COLOURS, captions=None):
+    """`render` of what `DetectionTracker.update` returns: the rows with an identity (track >= 0) that has been seen in
+    at least `min_hits` calls, in the colour palette[track % len(palette)] -- the colour follows the OBJECT from picture
+    to picture, not the class.  It is `render` with `track_colour_index` as the labels: no launch of its own, and CPU
+    tensors give the same bytes.  With `captions` the number on a box is its identity (ident = det["track"], whatever the
+    Captions' own `ident` says); scores=True prints det["scores"].  A Captions with `names` is refused: names go by the
+    label, which here is the colour index."""
+    if captions is not None:
+        if captions.names is not None:
+            raise ValueError("render_tracks: captions with names would print the name of the colour index, not of the class")
+        captions = captions.replace(det["track"], captions.scores)
+    return _render(video, det["boxes"], track_colour_index(det, min_hits, palette), frame_idx, thickness, palette,
+                   captions, det)
+
+
 # uint8 [256, 3], a diverging blue - white - red ramp by an integer rule: entry i is (2i, 2i, 255) for i <= 127 and
 # (255, 2(255 - i), 2(255 - i)) for i >= 128 -- blue at 0, (254, 254, 255) | (255, 254, 254) in the middle, red at 255.
 # (Not matplotlib's `coolwarm`, which the reference's notebook uses: same idea, other numbers.)

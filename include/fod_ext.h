@@ -307,6 +307,60 @@ int fod_detect_od_map(const float* scores, const int* labels, const float* boxes
                       uint8_t* is_positive, uint8_t* size_categories, int64_t* num_annos, int B, int K, int N, int C,
                       int P, int T, float img_h, float img_w, fod_stream_t stream);
 
+/* Identities across calls: associate the detection rows of ONE call with the tracks the caller keeps from the calls
+ * before it, age and retire the tracks nobody claimed, and start new ones -- per sample, in ONE launch (the reference
+ * has none; fod_tracker_cost / fod_tracker_extrapolate are its prediction baseline, inside one forward, and keep no
+ * state).  One workgroup per sample, wave64, no scratch, no atomics, nothing between workgroups: two launches from
+ * equal states give equal bits, and the launch can be captured.  ops.track_update on CPU tensors is the plain form of
+ * the same definition.
+ *   scores f32 [B][K], labels i32 [B][K], boxes f32 [B][K][4] xyxy, count i32 [B]: read only, the dense tensors of
+ *        fod_detect_select / fod_detect_nms (their `query` is not needed).
+ *   Track state, S slots per sample, owned by the caller and updated IN PLACE:
+ *        trk_boxes f32 [B][S][4] the last associated box; trk_vel f32 [B][S][4] the displacement of every corner per
+ *        call; trk_meta i32 [B][S][4] = (id, label, hits, misses); trk_scores f32 [B][S]; next_id i32 [B].
+ *        A slot is LIVE iff id >= 0.  The other fields of a free slot are never read, and never written unless a track
+ *        is born there.  No state tensor may alias a detection tensor or an output.
+ *   out_track i32 [B][K], out_hits i32 [B][K], out_slot i32 [B][K] (may be NULL).
+ *   Nothing but 4-byte alignment is required of any pointer.
+ * Per sample b, n = min(max(count[b], 0), K); rows at or beyond n are never read.  All arithmetic is f32, every
+ * operation rounded once, no fused multiply-add.
+ * 1. Prediction.  A live slot has gap = (float)(misses + 1) and the predicted box  box + vel * gap  per corner (one
+ *    multiplication, one addition) if motion != 0, and  box  otherwise.  A live slot whose predicted box has a NaN or
+ *    infinite corner cannot be claimed; it ages like any unclaimed slot (4).
+ * 2. Claims -- fod_detect_od_map's procedure with tracks in place of annotations.  The rows j < n are walked in ROW
+ *    order; scores are never compared.  A row with a NaN or infinite corner (tested explicitly, before any min / max
+ *    sees the value) claims nothing and is never born.  Any other row looks at the live, claimable slots that no
+ *    earlier row has claimed -- with class_agnostic == 0 only at those with label == labels[j] -- and CHOOSES the one of
+ *    greatest IoU with the predicted box, ties to the lowest slot index (no such slot: no match).  With the row's box
+ *    (x0, y0, x1, y1) and the predicted box (X0, Y0, X1, Y1):
+ *      area = max(x1 - x0, 0) * max(y1 - y0, 0)                                       (inverted corners: area 0)
+ *      inter = max(min(x1, X1) - max(x0, X0), 0) * max(min(y1, Y1) - max(y0, Y0), 0)
+ *      uni = (area_row + area_slot) - inter,   iou = uni > 0 ? inter / uni : 0        (uni NaN: 0)
+ *    One division, no smoothing term: zero-area boxes match nothing.  The row is MATCHED iff, for the CHOSEN slot,
+ *    inter > 0 and iou >= iou_threshold; the slot is then claimed.  Otherwise it stays free for later rows.
+ * 3. A slot s matched by row j:  vel = (row_box - box) / gap per corner (one subtraction, one division; 0 if
+ *    motion == 0), then box = row_box, score = scores[j], label = labels[j], hits += 1, misses = 0;
+ *    out_track[j] = id, out_hits[j] = the new hits, out_slot[j] = s.
+ * 4. A live slot nobody claimed: misses += 1; if misses > max_misses the slot is cleared: meta (-1, -1, 0, 0), box,
+ *    vel and score 0.
+ * 5. Births.  The candidates are the unmatched rows j < n of finite corners with scores[j] >= birth_score (a NaN
+ *    score never qualifies), in row order.  The r-th candidate (r = 0, 1, ...) takes the r-th free slot in ascending
+ *    slot order, free as judged AFTER step 4: id = next_id[b] + r, the row's box, score and label, vel 0, hits 1,
+ *    misses 0; out_track = that id, out_hits = 1, out_slot = the slot.  Candidates beyond the free slots stay
+ *    untracked.  next_id[b] grows by the number born.
+ * 6. Every other row, rows at or beyond n included: out_track -1, out_hits 0, out_slot -1.  Each of the B * K output
+ *    rows has exactly one writer.
+ * class_agnostic = 0 compares labels; anything else compares boxes only.
+ * FOD_ERR_ARG before any launch: K or S outside 1..1024; B < 1; an iou_threshold that is not finite or outside [0, 1];
+ * max_misses < 0; a NULL operand other than out_slot.
+ * The launch reads 24 B per row below count and up to 52 B per slot, and writes 12 B per row and up to 52 B per slot.
+ * Not this: Hungarian association, Kalman filters, appearance features, identities across samples, ids that wrap
+ * beyond 2^31 - 1, more than 1024 rows or slots. */
+int fod_track_update(const float* scores, const int* labels, const float* boxes, const int* count, int B, int K,
+                     float* trk_boxes, float* trk_vel, int* trk_meta, float* trk_scores, int* next_id, int S,
+                     float iou_threshold, float birth_score, int max_misses, int class_agnostic, int motion,
+                     int* out_track, int* out_hits, int* out_slot, fod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
