@@ -1721,6 +1721,135 @@ def track_update(scores, labels, boxes, count, state, *, iou_threshold, birth_sc
     return tuple(out)
 
 
+# ------------------------------------------------------------------------------------------------ streaming AP
+AP_HIST_BINS = 0x3F81                                    # bf16 patterns 0 .. 0x3F80 (1.0)
+AP_HIST_POINTS = 101
+
+
+def ap_hist_keys(scores):
+    """The bin of every f32 score (fod_ap_hist_accum in include/fod_ext.h): 0 for NaN and s <= 0, else the score's bf16
+    truncation `bits >> 16`, at most 0x3F80.  -> i64, integer arithmetic only."""
+    s = scores.contiguous()
+    key = (s.view(torch.int32).to(torch.int64) >> 16).clamp(max=AP_HIST_BINS - 1)
+    return torch.where(s > 0, key, torch.zeros_like(key))
+
+
+def ap_hist_state(T, C1, device):
+    """The zeroed state of the streaming AP: (hist_tp i32 [T,C1,4,NB], hist_seen i32 [C1,4,NB], anno_total i64 [C1,4])
+    with NB = 16257 score bins.  Its size does not depend on the data; states of several processes combine by adding."""
+    T, C1 = int(T), int(C1)
+    if not 1 <= T <= 16 or C1 < 2:
+        raise L.FodError(f"ap_hist_state: T={T} (1..16) and C1={C1} (at least 2) expected")
+    return (torch.zeros((T, C1, 4, AP_HIST_BINS), dtype=torch.int32, device=device),
+            torch.zeros((C1, 4, AP_HIST_BINS), dtype=torch.int32, device=device),
+            torch.zeros((C1, 4), dtype=torch.int64, device=device))
+
+
+def _ap_hist_check_state(state, who):
+    if len(state) != 3 or state[0].dim() != 4:
+        raise L.FodError(f"{who}: state is (hist_tp [T,C1,4,NB], hist_seen [C1,4,NB], anno_total [C1,4])")
+    T, C1, dev = state[0].shape[0], state[0].shape[1], state[0].device
+    shapes = (("hist_tp", torch.int32, (T, C1, 4, AP_HIST_BINS)), ("hist_seen", torch.int32, (C1, 4, AP_HIST_BINS)),
+              ("anno_total", torch.int64, (C1, 4)))
+    for t, (name, dtype, shape) in zip(state, shapes):
+        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+            raise L.FodError(f"{who}: contiguous state {name} {dtype} {list(shape)} on {dev} expected, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    if not 1 <= T <= 16 or C1 < 2:
+        raise L.FodError(f"{who}: T={T} (1..16) and C1={C1} (at least 2) expected")
+    return T, C1, dev
+
+
+def ap_hist_accum(od, state):
+    """Fold one batch of the AP bookkeeping into the streaming state, one launch (fod_ap_hist_accum in include/fod_ext.h
+    has the exact semantics): `od` = (confs f32 [T,C1,P], is_positive bool|u8 [T,C1,P], size_categories bool|u8 [C1,4,P],
+    num_annos i64 [C1,4]) as `od_map` / `detect_od_map` (prepare_od_map_stuffs / prepare_od_map_detections) return them,
+    `state` from `ap_hist_state`, updated IN PLACE and returned.  The bin of a slot is that of its score at t = 0; padding
+    slots add nothing.  Integer sums: the state does not depend on the order of the slots or of the batches.  CPU tensors
+    run the plain form of the same definition (same bytes); device tensors run the kernel."""
+    T, C1, dev = _ap_hist_check_state(state, "ap_hist_accum")
+    if len(od) != 4 or od[0].dim() != 3:
+        raise L.FodError("ap_hist_accum: od is (confs [T,C1,P], is_positive, size_categories, num_annos)")
+    P = od[0].shape[2]
+    flag = (torch.bool, torch.uint8)
+    shapes = (("confs", (torch.float32,), (T, C1, P)), ("is_positive", flag, (T, C1, P)),
+              ("size_categories", flag, (C1, 4, P)), ("num_annos", (torch.int64,), (C1, 4)))
+    for t, (name, dtypes, shape) in zip(od, shapes):
+        if tuple(t.shape) != shape or t.dtype not in dtypes or t.device != dev or not t.is_contiguous():
+            raise L.FodError(f"ap_hist_accum: contiguous {name} {dtypes[0]} {list(shape)} on {dev} expected, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    if P < 1:
+        raise L.FodError("ap_hist_accum: at least one slot expected")
+    confs, is_pos, sizes, num_annos = od
+    hist_tp, hist_seen, anno_total = state
+    if not dev.type == "cuda":
+        rows = (torch.arange(C1, dtype=torch.int64)[:, None] * 4) * AP_HIST_BINS + ap_hist_keys(confs[0])      # [C1,P]
+        for s in range(4):
+            f = sizes[:, s] != 0
+            at = (rows + s * AP_HIST_BINS).flatten()
+            hist_seen.view(-1).index_add_(0, at, f.flatten().to(torch.int32))
+            hist_tp.view(T, -1).index_add_(1, at, ((is_pos != 0) & f[None]).reshape(T, -1).to(torch.int32))
+        anno_total += num_annos
+        return state
+    call("fod_ap_hist_accum", ptr(confs), ptr(is_pos), ptr(sizes), ptr(num_annos), T, C1, P, ptr(hist_tp), ptr(hist_seen),
+         ptr(anno_total), stream())
+    return state
+
+
+def _ap_hist_finalize_cpu(hist_tp, hist_seen, anno_total, T, C1):
+    """The definition of fod_ap_hist_finalize on host tensors: per (class, size) row only the non-empty bins are visited
+    (an empty bin changes no sum and answers no recall point); integers in i64, everything after them in f64."""
+    nan = float("nan")
+    ap = torch.full((T, C1, 4), nan, dtype=torch.float64)
+    ap101, pr = ap.clone(), torch.full((T, C1, 4, AP_HIST_POINTS), nan, dtype=torch.float64)
+    score = torch.full((T, C1, 4, AP_HIST_POINTS), nan, dtype=torch.float32)
+    totals = torch.stack([hist_tp.sum(dim=3, dtype=torch.int64),
+                          hist_seen.sum(dim=2, dtype=torch.int64)[None].expand(T, -1, -1)], dim=3).contiguous()
+    steps = torch.arange(AP_HIST_POINTS, dtype=torch.int64)
+    above = lambda x: x.flip(-1).cumsum(-1).flip(-1)                      # inclusive sums over the bins of key >= b
+    for c in range(C1):
+        for s in range(4):
+            A = int(anno_total[c, s])
+            if A <= 0:
+                continue
+            bins = torch.nonzero(hist_seen[c, s] > 0).flatten()          # ascending
+            tp, se = hist_tp[:, c, s, bins].to(torch.int64), hist_seen[c, s, bins].to(torch.int64)
+            TP, SE = above(tp), above(se)[None]
+            ap[:, c, s] = (tp.double() * (TP.double() / (SE.double() + 1e-5))).sum(dim=1) / float(A)
+            if not bins.numel():
+                pr[:, c, s], score[:, c, s], ap101[:, c, s] = 0.0, 0.0, 0.0
+                continue
+            env = (TP.double() / SE.double()).cummax(dim=1).values
+            # TP falls with the bin: the bins that reach recall point i are the first `reach` ones
+            reach = (TP[:, None, :] * 100 >= (steps * A)[None, :, None]).sum(dim=2)            # [T,101]
+            at = (reach - 1).clamp(min=0)
+            edges = (bins << 16).to(torch.int32).view(torch.float32)
+            pr[:, c, s] = torch.where(reach > 0, env.gather(1, at), torch.zeros((), dtype=torch.float64))
+            score[:, c, s] = torch.where(reach > 0, edges[at], torch.zeros((), dtype=torch.float32))
+            total = torch.zeros(T, dtype=torch.float64)
+            for i in range(AP_HIST_POINTS):                               # ascending, as the contract says
+                total = total + pr[:, c, s, i]
+            ap101[:, c, s] = total / 101.0
+    return ap, ap101, pr, score, totals
+
+
+def ap_hist_finalize(state):
+    """The streaming state -> (ap f64 [T,C1,4], ap101 f64 [T,C1,4], pr f64 [T,C1,4,101], pr_score f32 [T,C1,4,101],
+    totals i64 [T,C1,4,2]), one launch (fod_ap_hist_finalize in include/fod_ext.h has the exact semantics): the
+    reference's AP taken on score bins, COCO's 101-point interpolated AP, the precision envelope and the score's lower
+    edge at recall i / 100, and (true positives, candidates) per row.  NaN where a row has no annotation.  The state is
+    read only.  CPU tensors run the plain form of the same definition; device tensors run the kernel."""
+    T, C1, dev = _ap_hist_check_state(state, "ap_hist_finalize")
+    if not dev.type == "cuda":
+        return _ap_hist_finalize_cpu(*state, T, C1)
+    out = (torch.empty((T, C1, 4), dtype=torch.float64, device=dev), torch.empty((T, C1, 4), dtype=torch.float64, device=dev),
+           torch.empty((T, C1, 4, AP_HIST_POINTS), dtype=torch.float64, device=dev),
+           torch.empty((T, C1, 4, AP_HIST_POINTS), dtype=torch.float32, device=dev),
+           torch.empty((T, C1, 4, 2), dtype=torch.int64, device=dev))
+    call("fod_ap_hist_finalize", ptr(state[0]), ptr(state[1]), ptr(state[2]), T, C1, *(ptr(o) for o in out), stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ tracker baseline
 TRACKER_MODES = {None: 0, "linear": 1, "percentual": 2, "average": 3}
 

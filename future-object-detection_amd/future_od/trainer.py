@@ -80,6 +80,15 @@ class Trainer:
         self._captions = V.Captions(names=self._category_dict) if flag else None
         return self
 
+    def set_streaming_evaluation(self, flag=True):
+        """`evaluate_detections` through integer histograms over score bins (od_map.StreamingDetectionEvaluator) instead
+        of every batch's tensors: constant memory, so the ~10k-image cap is lifted; every rank evaluates its own shard and
+        one all_reduce of the histograms gives every rank the AP of the whole set, so more than one rank is accepted; the
+        result gains "coco" (101-point interpolated AP) and "pr_curve", and one "COCO AP" line is printed.  Off (the
+        default): nothing changes.  (A method, not a keyword of `evaluate_detections`: its signature is kept as it is.)"""
+        self._streaming_eval = bool(flag)
+        return self
+
     def set_accumulate(self, n):
         """One optimizer update per `n` loader items (micro-batches), each normalised by its own number of boxes: the
         update is the mean of their gradients (future_od/graph.py: GraphedStep(accumulate=n); the eager loop accumulates
@@ -169,12 +178,15 @@ class Trainer:
         evaluation pass would be captured and eager `predict` otherwise, capped at ~10k images as `_run_epoch` is.
         Prints `_run_epoch`'s AP lines and a precision / recall line; -> {loader name: the evaluator's dict}.  Trains
         nothing and leaves the model in the mode it was in.  One process only: nothing is gathered between ranks.
+        After `set_streaming_evaluation()`: no cap, any number of ranks (each its own shard), and the COCO AP as well.
         (A method, not a constructor keyword: the constructor is the reference's plus `ema`.)"""
-        if self._distributed and distrib.is_initialized() and distrib.get_world_size() > 1:
+        streaming = getattr(self, "_streaming_eval", False)
+        ranks = distrib.get_world_size() if self._distributed and distrib.is_initialized() else 1
+        if ranks > 1 and not streaming:
             raise NotImplementedError("Trainer.evaluate_detections: detections are not gathered between ranks; "
                                       "evaluate in one process")
         from future_od.graph import GraphedPredict
-        from future_od.utils.od_map import DetectionEvaluator
+        from future_od.utils.od_map import DetectionEvaluator, StreamingDetectionEvaluator
         model = self._model_no_ddp
         if not self._distributed:
             self._model.to(self._device)
@@ -190,9 +202,10 @@ class Trainer:
                     if hasattr(model._model, "drop_mode"):
                         model._model.drop_mode = name
                     batch_size = getattr(loader, "batch_size", 1) or 1
-                    evaluator = DetectionEvaluator(model._criterion.num_classes, per_class)
+                    evaluator = (StreamingDetectionEvaluator if streaming else DetectionEvaluator)(
+                        model._criterion.num_classes, per_class)
                     for i, data in enumerate(DevicePrefetcher(loader, self._device)):
-                        if EXIT.is_set() or i * batch_size >= 10000:         # the cap of the AP bookkeeping
+                        if EXIT.is_set() or (not streaming and i * batch_size >= 10000):   # the cap of the kept tensors
                             break
                         det = None
                         if graphed is not None:
@@ -204,7 +217,7 @@ class Trainer:
                         if det is None:
                             det = model.predict(data, **options)
                         evaluator.update(det, data)
-                    if not len(evaluator):
+                    if not len(evaluator) and ranks == 1:             # (with more ranks every one joins the all_reduce)
                         continue
                     ap = results[name] = evaluator.aggregate(self._device)
                     fmt = lambda xs: " ".join(f"{float(e):.3f}" for e in xs)
@@ -215,6 +228,9 @@ class Trainer:
                     print("MAP for small objects is:", fmt(ap["threshavg"][:, 1]))
                     print("MAP for medium objects is:", fmt(ap["threshavg"][:, 2]))
                     print("MAP for large objects is:", fmt(ap["threshavg"][:, 3]))
+                    if streaming:
+                        print("COCO AP (101-point, IoU 0.50:0.95 / 0.50) is:", fmt(ap["coco"]["threshavg"][:, 0]), "/",
+                              fmt(ap["coco"]["all"][0, :, 0]))
                     op = ap["operating_point"]
                     print("Precision / recall at IoU 0.5 (generic class):", f"{float(op['precision'][-1]):.3f} /",
                           f"{float(op['recall'][-1]):.3f}  ({int(op['true_positives'][-1])} of "

@@ -4,7 +4,10 @@ reference's 50-step tensor loop; the end-of-epoch aggregation is small host math
 
 The same bookkeeping over the detection ROWS `predict` returns (fod_detect_od_map, one launch): prepare_od_map_detections,
 DetectionEvaluator and operating_point -- what top_k, score_threshold, per_query and the duplicate suppression do to AP,
-precision and recall.  Nothing of it runs unless it is called."""
+precision and recall.  Nothing of it runs unless it is called.
+
+StreamingDetectionEvaluator keeps integer histograms over score bins instead of every batch's tensors (fod_ap_hist_accum /
+fod_ap_hist_finalize): constant memory, one all_reduce between ranks, COCO's 101-point AP and a precision / recall curve."""
 import numpy as np
 import torch
 
@@ -46,6 +49,11 @@ def aggregate_mean_average_precision(confs, is_positive, size_categories, num_an
                                   num_annos.to(device)) for t in range(T)]).cpu()
     print("Number of annos for each class and size category is:")
     print(num_annos.sum(dim=2))
+    return _ap_tables(ap)
+
+
+def _ap_tables(ap):
+    """AP (T,C,S) on the host, the generic class last -> the tables every aggregation returns."""
     per_class = ap[:, 0:-1, :].numpy()
     return {
         "all": ap[:, 0:-1, :],
@@ -89,6 +97,10 @@ def operating_point(confs, is_positive, size_categories, num_annos, t=0):
     det = filled.sum(dim=1).cpu()
     tp = (is_positive[t].bool() & filled).sum(dim=1).cpu()
     anno = (num_annos[:, 0] if num_annos.dim() == 2 else num_annos[:, 0].sum(dim=1)).cpu()
+    return _operating_point(det, tp, anno, t)
+
+
+def _operating_point(det, tp, anno, t):
     ratio = lambda a, b: torch.where(b > 0, a.double() / b.double().clamp(min=1), torch.full_like(a, float("nan"), dtype=torch.float64))
     return {"iou": 0.5 + 0.05 * t, "detections": det, "true_positives": tp, "annotations": anno,
             "precision": ratio(tp, det), "recall": ratio(tp, anno), "f1": ratio(2 * tp, det + anno)}
@@ -134,3 +146,86 @@ class DetectionEvaluator:
         ap = aggregate_mean_average_precision(*od, od[0].device if device is None else device)
         ap["operating_point"] = operating_point(*od)
         return ap
+
+
+class StreamingDetectionEvaluator(DetectionEvaluator):
+    """ev = StreamingDetectionEvaluator(num_classes); for batch: ev.update(model.predict(batch, ...), batch); ev.aggregate()
+
+    DetectionEvaluator in constant memory: `update` runs the bookkeeping launch into buffers it reuses and folds them into
+    integer histograms over 16257 score bins (ops.ap_hist_accum: one more launch, nothing read back, nothing kept per
+    batch), so a set of any size can be scored and `tensors()` has nothing to return.  `aggregate` adds the states of
+    all ranks with one all_reduce(SUM) per tensor when a process group with more than one rank is initialised (exact
+    integers: every rank returns the bytes one process that saw all batches returns), finalises in one launch
+    (ops.ap_hist_finalize) and returns `aggregate_mean_average_precision`'s tables from the AP taken on bins, plus
+    "coco" (the same tables from the 101-point interpolated AP), "pr_curve" ("precision" f64 and "score" f32
+    [T,C,4,101], "recall" = i / 100) and "operating_point" with DetectionEvaluator's fields.  Where no two candidates of a
+    (class, size) row share a bin the AP is the sorted one up to f64 rounding; otherwise a bin's candidates are counted
+    together.  `update_od` takes the four tensors directly, e.g. `prepare_od_map_stuffs`' of the dense path.
+    (A class of its own, not a keyword of DetectionEvaluator: that constructor is kept as it is.)"""
+
+    def reset(self):
+        self._updates = 0
+        if getattr(self, "_state", None) is not None:
+            for t in self._state:
+                t.zero_()
+        else:
+            self._state, self._bufs = None, {}
+
+    def __len__(self):
+        return self._updates
+
+    def update_od(self, od):
+        """One batch's (confs, is_positive, size_categories, num_annos) into the state."""
+        if self._state is None:
+            self._state = ops.ap_hist_state(od[0].shape[0], self.num_classes + 1, od[0].device)
+        ops.ap_hist_accum(od, self._state)
+        self._updates += 1
+        return od
+
+    def update(self, det, data):
+        if data.get("box_map") is not None or det.get("box_map") is not None:
+            raise ValueError("StreamingDetectionEvaluator: these detections went through a box_map (boxes in the camera's "
+                             "frame); the annotations are in the network's input frame")
+        B, N = data["classes"].shape[0], data["classes"].shape[-1]
+        (_, K), dev = det["scores"].shape, det["scores"].device
+        C1, P = self.num_classes + 1, min(self.per_class, K)
+        out = self._bufs.get((B, P, dev))
+        if out is None:                                     # reused by every later batch of this shape
+            out = self._bufs[(B, P, dev)] = (
+                torch.empty((NUM_THRESHOLDS, C1, B * P), dtype=torch.float32, device=dev),
+                torch.empty((NUM_THRESHOLDS, C1, B * P), dtype=torch.bool, device=dev),
+                torch.empty((C1, 4, B * P), dtype=torch.bool, device=dev), torch.empty((C1, 4), dtype=torch.int64, device=dev))
+        od = ops.detect_od_map(*(det[k] for k in DETECTION_KEYS), data["boxes"].reshape(B, N, 4).float().contiguous(),
+                               data["classes"].reshape(B, N).contiguous(), data["active"].reshape(B, N).contiguous(),
+                               data["video"].shape[-2:], self.num_classes, self.per_class, T=NUM_THRESHOLDS, out=out)
+        return self.update_od(od)
+
+    def tensors(self):
+        raise RuntimeError("StreamingDetectionEvaluator keeps no per-batch tensors: only the histograms (state())")
+
+    def state(self):
+        """(hist_tp, hist_seen, anno_total) as accumulated here; None before the first update."""
+        return self._state
+
+    def aggregate(self, device=None):
+        import torch.distributed as distrib
+        ranks = distrib.get_world_size() if distrib.is_available() and distrib.is_initialized() else 1
+        if self._state is None:
+            if ranks == 1:
+                raise RuntimeError("StreamingDetectionEvaluator: no update yet")
+            self._state = ops.ap_hist_state(NUM_THRESHOLDS, self.num_classes + 1, "cpu" if device is None else device)
+        state = self._state
+        if ranks > 1:                                       # the local state stays what this rank saw
+            state = tuple(t.clone() for t in state)
+            for t in state:
+                distrib.all_reduce(t, op=distrib.ReduceOp.SUM)
+        ap, ap101, pr, score, totals = (t.cpu() for t in ops.ap_hist_finalize(state))
+        anno = state[2].cpu()
+        print("Number of annos for each class and size category is:")
+        print(anno)
+        res = _ap_tables(ap)
+        res["coco"] = _ap_tables(ap101)
+        res["pr_curve"] = {"precision": pr, "score": score,
+                           "recall": torch.arange(101, dtype=torch.float64) / 100}
+        res["operating_point"] = _operating_point(totals[0, :, 0, 1], totals[0, :, 0, 0], anno[:, 0], 0)
+        return res

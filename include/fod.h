@@ -45,7 +45,7 @@ enum { FOD_OK = 0, FOD_ERR_ARG = 1, FOD_ERR_LAUNCH = 2, FOD_ERR_RUNTIME = 3 };
 size_t fod_last_error(char* buf, size_t cap);
 /* ABI version of this header; the loader refuses a library that disagrees. */
 int fod_abi_version(void);
-#define FOD_ABI_VERSION 19
+#define FOD_ABI_VERSION 20
 
 /* Kernel-selection knobs: the FOD_* variables the library looks at (listed with their values and defaults in
  * csrc/knobs.h) live in one process-wide host table that is filled from the environment ONCE, at its first use; a

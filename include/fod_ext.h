@@ -361,6 +361,54 @@ int fod_track_update(const float* scores, const int* labels, const float* boxes,
                      float iou_threshold, float birth_score, int max_misses, int class_agnostic, int motion,
                      int* out_track, int* out_hits, int* out_slot, fod_stream_t stream);
 
+/* Streaming AP: the four tensors of the AP bookkeeping (fod_od_map or fod_detect_od_map) are folded, batch after batch,
+ * into INTEGER histograms over score bins; one finalising launch turns them into the reference's AP, COCO's 101-point
+ * interpolated AP, a precision / recall curve and the operating point.  The state has a constant size, its sums are
+ * exact and independent of order (two runs give equal bits although the adds are atomic), and several processes combine
+ * theirs by adding the three tensors element-wise.  Both launches can be captured.  ops.ap_hist_accum / ap_hist_finalize
+ * on CPU tensors are the plain form of the same definition.
+ * Bins: NB = 0x3F81 = 16257.  A score s has key 0 if s is NaN or s <= 0, and min(bits(s) >> 16, 0x3F80) otherwise, where
+ * bits is the f32 pattern: the score truncated to bf16, everything from 1.0 on (+inf included) in the last bin.  The
+ * lower edge of bin k is the f32 of pattern k << 16.  Integer arithmetic only; 2^-7 relative resolution everywhere.
+ * State, owned by the caller and zeroed by the caller ONCE:
+ *   hist_tp i32 [T][C1][4][NB], hist_seen i32 [C1][4][NB], anno_total i64 [C1][4].
+ *
+ * fod_ap_hist_accum: ONE launch over
+ *   confs f32 [T][C1][P_total], is_positive u8 [T][C1][P_total], size_categories u8 [C1][4][P_total] (flags 0 or 1),
+ *   num_annos i64 [C1][4]
+ * for any P_total >= 1.  For slot p of class c the key is that of confs[0][c][p]: both producers write one score for
+ * every t, and only t = 0 is read.  With f_s = size_categories[c][s][p]:
+ *   hist_seen[c][s][key] += f_s;   hist_tp[t][c][s][key] += is_positive[t][c][p] & f_s;   anno_total[c][s] += num_annos[c][s].
+ * A slot whose four flags are 0 (the producers' padding) adds nothing and reads nothing beyond its flags.  The adds are
+ * integer atomics on global memory; no float atomics, no scratch.  A bin that would pass 2^31 - 1 is not claimed.
+ * FOD_ERR_ARG before any launch: T outside 1..16; C1 < 2; P_total < 1; C1 * ceil(P_total / 256) beyond 2^31 - 1; a NULL
+ * operand.
+ *
+ * fod_ap_hist_finalize: ONE launch, one workgroup per (t, c, s) row, the NB bins walked from the low-score end in chunks
+ * with wave-level scans; the state is read only.  Everything from the integers on is f64, each operation rounded once.
+ * With A = anno_total[c][s], tp_b = hist_tp[t][c][s][b], se_b = hist_seen[c][s][b] (tp_b <= se_b, as the accumulation
+ * leaves them), TP_b / SE_b their sums over the bins of key >= b, and a bin NON-EMPTY iff se_b > 0:
+ *   totals i64 [T][C1][4][2] = (TP_0, SE_0): the true positives and the candidates of the row.
+ *   ap f64 [T][C1][4] = (sum over b of tp_b * (TP_b / (SE_b + 1e-5))) / A: the reference's mean precision at the true
+ *        positives (utils/od_map.py:290-314) taken on bins -- every candidate of a bin is counted before the bin's
+ *        precision is taken.  The order of the sum is the kernel's own: within (n + 3) * 2^-53 of any other, n non-empty
+ *        bins.
+ *   p_b = TP_b / SE_b on non-empty bins (one division); env_b = the maximum of p_b' over the non-empty bins b' <= b.
+ *   pr f64 [T][C1][4][101], pr_score f32 [T][C1][4][101]: for i = 0..100, with b the HIGHEST non-empty bin for which
+ *        TP_b * 100 >= i * A (compared in i64: no recall is rounded), pr[i] = env_b and pr_score[i] = the lower edge of b;
+ *        no such bin: both 0.
+ *   ap101 f64 [T][C1][4] = (pr[0] + pr[1] + ... + pr[100]) / 101, summed in that order.
+ * A <= 0: ap, ap101, pr and pr_score of the row are NaN (the reference's 0 / 0); totals is still written.
+ * Every output element has exactly one writer.
+ * FOD_ERR_ARG before any launch: T outside 1..16; C1 < 2; a NULL operand.
+ * Not this: equality with the sorted AP where two candidates of a (class, size) row share a bin; COCO's area ranges or
+ * maxDets; tracking metrics. */
+int fod_ap_hist_accum(const float* confs, const uint8_t* is_positive, const uint8_t* size_categories,
+                      const int64_t* num_annos, int T, int C1, long P_total, int* hist_tp, int* hist_seen,
+                      int64_t* anno_total, fod_stream_t stream);
+int fod_ap_hist_finalize(const int* hist_tp, const int* hist_seen, const int64_t* anno_total, int T, int C1, double* ap,
+                         double* ap101, double* pr, float* pr_score, int64_t* totals, fod_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
