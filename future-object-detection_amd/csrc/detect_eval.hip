@@ -14,16 +14,9 @@
 //   5. the workgroups of sample 0 count their class's annotations over ALL samples: one writer per num_annos row.
 // Every output element has exactly one writer, nothing is accumulated in memory, no scratch, no atomics, nothing between
 // workgroups: the outputs need no initialisation and two launches give equal bits.
-#include "common.h"
+#include "det_rows.h"   // fp contract(off) from here on (explained there): the IoU is od_map_kernel's, operation for operation
 
-// The IoU is od_map_kernel's, operation for operation and each rounded once (the header): nothing here may contract.
-#pragma clang fp contract(off)
-
-constexpr int DE_MAX_K = 1024, DE_MAX_N = 1024, DE_MAX_T = 16;   // rows (fod_detect_select's limit), annotation slots, waves
-
-FOD_DEVINL bool de_finite(const float4 b) { return isfinite(b.x) && isfinite(b.y) && isfinite(b.z) && isfinite(b.w); }
-FOD_DEVINL float4 de_box(const float* p) { return make_float4(p[0], p[1], p[2], p[3]); }   // (4-byte alignment only)
-FOD_DEVINL float de_area(const float4 b) { return fmaxf(b.z - b.x, 0.f) * fmaxf(b.w - b.y, 0.f); }
+constexpr int DE_MAX_T = 16;                           // waves; rows and annotation slots: ROWS_MAX
 
 __global__ __launch_bounds__(1024) void detect_od_map_kernel(
     const float* __restrict__ scores, const int32_t* __restrict__ labels, const float* __restrict__ boxes,
@@ -31,22 +24,22 @@ __global__ __launch_bounds__(1024) void detect_od_map_kernel(
     const int64_t* __restrict__ ac, const int64_t* __restrict__ aa, float* __restrict__ confs,
     uint8_t* __restrict__ is_pos, uint8_t* __restrict__ sizes, long long* __restrict__ num_annos, int B, int K, int N,
     int C1, int P, float H, float W) {
-  __shared__ float4 s_abox[DE_MAX_N];                   // annotations: zeros where the box is not finite
-  __shared__ float4 s_cbox[DE_MAX_K];                   // candidates, in rank order
-  __shared__ float s_aarea[DE_MAX_N];
-  __shared__ float s_carea[DE_MAX_K];
-  __shared__ float s_cscore[DE_MAX_K];
-  __shared__ int s_key[DE_MAX_K];                       // per row: the label, for the generic class the query
+  __shared__ float4 s_abox[ROWS_MAX];                   // annotations: zeros where the box is not finite
+  __shared__ float4 s_cbox[ROWS_MAX];                   // candidates, in rank order
+  __shared__ float s_aarea[ROWS_MAX];
+  __shared__ float s_carea[ROWS_MAX];
+  __shared__ float s_cscore[ROWS_MAX];
+  __shared__ int s_key[ROWS_MAX];                       // per row: the label, for the generic class the query
   __shared__ unsigned s_free[DE_MAX_T * 64];            // per wave and lane: bit r = annotation lane + 64 r is free
-  __shared__ unsigned short s_cand[DE_MAX_K];           // candidate k's row
-  __shared__ unsigned char s_avail[DE_MAX_N];           // free at the start
-  __shared__ unsigned char s_cfin[DE_MAX_K];            // candidate k's box is finite
+  __shared__ unsigned short s_cand[ROWS_MAX];           // candidate k's row
+  __shared__ unsigned char s_avail[ROWS_MAX];           // free at the start
+  __shared__ unsigned char s_cfin[ROWS_MAX];            // candidate k's box is finite
   __shared__ int s_wcnt[DE_MAX_T];
   __shared__ long long s_cnt[DE_MAX_T][4];
   const int c = blockIdx.x % C1, b = blockIdx.x / C1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x, T = nthreads >> 6;
   const bool generic = c == C1 - 1;
-  const int n = min(max(count[b], 0), K);               // rows at or beyond n are never read
+  const int n = row_count(count, b, K);
   const float s0 = (float)((1.0 / 24) * (1.0 / 64) * (double)H * (double)W);     // od_map_kernel's delimiters
   const float s1 = (float)((1.0 / 4) * (1.0 / 12) * (double)H * (double)W);
   const long slots = (long)B * P;
@@ -54,11 +47,11 @@ __global__ __launch_bounds__(1024) void detect_od_map_kernel(
   // ---- 1. annotations and keys
   for (int a = tid; a < N; a += nthreads) {
     const long i = (long)b * N + a;
-    const float4 box = de_box(ab + i * 4);
-    const bool fin = de_finite(box);                     // tested before any min / max sees the value
+    const float4 box = row_box(ab + i * 4);
+    const bool fin = row_finite(box);                    // tested before any min / max sees the value
     const float4 tb = fin ? box : make_float4(0.f, 0.f, 0.f, 0.f);
     s_abox[a] = tb;
-    s_aarea[a] = de_area(tb);
+    s_aarea[a] = row_area(tb);
     s_avail[a] = fin && aa[i] == 1 && (generic || ac[i] == c);
   }
   for (int j = tid; j < n; j += nthreads) s_key[j] = generic ? query[(long)b * K + j] : labels[(long)b * K + j];
@@ -100,10 +93,10 @@ __global__ __launch_bounds__(1024) void detect_od_map_kernel(
     unsigned char f1 = 0, f2 = 0, f3 = 0;
     if (k < ncand) {
       const long row = (long)b * K + s_cand[k];
-      const float4 box = de_box(boxes + row * 4);
-      const bool fin = de_finite(box);
+      const float4 box = row_box(boxes + row * 4);
+      const bool fin = row_finite(box);
       s_cbox[k] = box;
-      s_carea[k] = de_area(box);
+      s_carea[k] = row_area(box);
       s_cscore[k] = scores[row];
       s_cfin[k] = fin;
       if (fin) {
@@ -146,6 +139,7 @@ __global__ __launch_bounds__(1024) void detect_od_map_kernel(
           float iou = 0.f;
           if (a < N && ((freem >> r) & 1u)) {
             const float4 q = s_abox[a];
+            // row_inter(p, q), spelled out: through the helper the compiler allocates this loop's registers differently
             const float inter = fmaxf(fminf(p.z, q.z) - fmaxf(p.x, q.x), 0.f) * fmaxf(fminf(p.w, q.w) - fmaxf(p.y, q.y), 0.f);
             iou = (inter + 1e-7f) / (area1 + s_aarea[a] - inter + 1e-7f);
           }
@@ -177,9 +171,9 @@ __global__ __launch_bounds__(1024) void detect_od_map_kernel(
     long long cnt[4] = {0, 0, 0, 0};
     for (long i = tid; i < (long)B * N; i += nthreads) {
       if (aa[i] != 1 || !(generic || ac[i] == c)) continue;
-      const float4 box = de_box(ab + i * 4);
+      const float4 box = row_box(ab + i * 4);
       cnt[0] += 1;
-      if (de_finite(box)) {                              // a non-finite annotation counts in column 0 only
+      if (row_finite(box)) {                             // a non-finite annotation counts in column 0 only
         const float area = (box.z - box.x) * (box.w - box.y);
         cnt[1] += area <= s0;
         cnt[2] += (s0 < area) && (area <= s1);
@@ -208,8 +202,8 @@ extern "C" int fod_detect_od_map(const float* scores, const int* labels, const f
                                  uint8_t* size_categories, int64_t* num_annos, int B, int K, int N, int C, int P, int T,
                                  float img_h, float img_w, hipStream_t stream) {
   FOD_REQUIRE(B >= 1, "detect_od_map: B=%d samples, at least 1 expected", B);
-  FOD_REQUIRE(K >= 1 && K <= DE_MAX_K, "detect_od_map: K=%d is outside 1..%d", K, DE_MAX_K);
-  FOD_REQUIRE(N >= 1 && N <= DE_MAX_N, "detect_od_map: N=%d is outside 1..%d", N, DE_MAX_N);
+  FOD_REQUIRE(K >= 1 && K <= ROWS_MAX, "detect_od_map: K=%d is outside 1..%d", K, ROWS_MAX);
+  FOD_REQUIRE(N >= 1 && N <= ROWS_MAX, "detect_od_map: N=%d is outside 1..%d", N, ROWS_MAX);
   FOD_REQUIRE(P >= 1 && P <= K, "detect_od_map: P=%d is outside 1..K=%d", P, K);
   FOD_REQUIRE(T >= 1 && T <= DE_MAX_T, "detect_od_map: T=%d is outside 1..%d", T, DE_MAX_T);
   FOD_REQUIRE(C >= 1, "detect_od_map: C=%d classes, at least 1 expected", C);

@@ -17,15 +17,7 @@
 // Every access is lane l to row base + l: 16 bytes to consecutive slots or 4 bytes to consecutive dwords, no bank
 // conflict.  Inside the loops a row comes out of a lane's registers (v_readlane), not out of LDS.
 // No scratch, no atomics, nothing between workgroups; the order of every decision is fixed: deterministic.
-#include "common.h"
-
-// The suppression test is defined in single roundings (the header): nothing in this file may contract a * b + c.  The
-// arithmetic is written with plain operators for that reason: the pragma governs the operations of THIS file, while
-// __fmul_rn / __fsub_rn are inline functions of the HIP headers, compiled under the default (contracting) mode -- with
-// them `(area_i + area_j) - iw * ih` came out as one v_fma_f32.
-#pragma clang fp contract(off)
-
-constexpr int NMS_MAX_K = 1024;                        // = DET_MAX_K of fod_detect_select (csrc/loss.hip)
+#include "det_rows.h"   // fp contract(off) from here on (explained there): the suppression test rounds every operation once
 
 // min / max of a wave-uniform value and a lane's own as ONE instruction.  fminf / fmaxf on a value that came through
 // v_readlane cost a second one each (v_max_f32 s, s: the compiler re-quiets a possible signalling NaN); the corners
@@ -50,31 +42,16 @@ FOD_DEVINL bool nms_overlaps(const float4 a, const float area_a, const float4 b,
   return inter > thr * uni;
 }
 
-FOD_DEVINL unsigned long long nms_uniform64(unsigned long long v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
-// the value lane `i` holds, for a wave-uniform i: v_readlane_b32 into scalar registers, no LDS round trip
-FOD_DEVINL int nms_lane(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
-FOD_DEVINL float nms_lane(float v, int i) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i)); }
-FOD_DEVINL float4 nms_lane(float4 v, int i) {
-  return make_float4(nms_lane(v.x, i), nms_lane(v.y, i), nms_lane(v.z, i), nms_lane(v.w, i));
-}
-FOD_DEVINL unsigned long long nms_lane(unsigned long long v, int i) {
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, i), hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), i);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(1024) void detect_nms_kernel(
     const float* in_scores, const int32_t* in_labels, const float* in_boxes, const int32_t* in_query,
     const int32_t* in_count, int K, float thr, int class_agnostic, float* out_scores, int32_t* out_labels,
     float* out_boxes, int32_t* out_query, int32_t* out_count, int32_t* out_source) {   // (no __restrict__: they may alias)
-  __shared__ float4 s_box[NMS_MAX_K];                   // the box the test reads: zeros for a row that takes no part
-  __shared__ float s_area[NMS_MAX_K];
-  __shared__ int s_cls[NMS_MAX_K];
-  __shared__ unsigned long long s_kept[NMS_MAX_K / 64];
+  __shared__ float4 s_box[ROWS_MAX];                    // the box the test reads: zeros for a row that takes no part
+  __shared__ float s_area[ROWS_MAX];
+  __shared__ int s_cls[ROWS_MAX];
+  __shared__ unsigned long long s_kept[ROWS_MAX / 64];
   const int b = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
-  const int n = min(max(in_count[b], 0), K);            // rows at or beyond n are never read
+  const int n = row_count(in_count, b, K);
   const int nblk = (n + 63) >> 6;
   const long row = (long)b * K + j;
 
@@ -87,16 +64,17 @@ __global__ __launch_bounds__(1024) void detect_nms_kernel(
     score = in_scores[row];
     label = in_labels[row];
     query = in_query[row];
-    box = make_float4(in_boxes[row * 4], in_boxes[row * 4 + 1], in_boxes[row * 4 + 2], in_boxes[row * 4 + 3]);
+    box = row_box(in_boxes + row * 4);
   }
   // a row with a non-finite coordinate is kept and suppresses nothing: tested here, once, and the test then sees a
   // zero box in its place -- against any box of finite corners that gives inter = 0, and 0 > thr * uni never holds
   // (thr * uni is >= 0 or NaN).  Rows beyond n are zero boxes as well; they are never candidates.
+  // (row_finite(box), spelled out: through the helper the two subtractions of the area below stop being one v_pk_add_f32)
   const bool finite = isfinite(box.x) && isfinite(box.y) && isfinite(box.z) && isfinite(box.w);
   const float4 tb = finite ? box : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float area = fmaxf(tb.z - tb.x, 0.f) * fmaxf(tb.w - tb.y, 0.f);
+  const float area = row_area(tb);
   const int cls = class_agnostic ? 0 : label;
-  s_box[j] = tb;                                          // (the launch has at most NMS_MAX_K threads)
+  s_box[j] = tb;                                          // (the launch has at most ROWS_MAX threads)
   s_area[j] = area;
   s_cls[j] = cls;
   __syncthreads();
@@ -108,8 +86,8 @@ __global__ __launch_bounds__(1024) void detect_nms_kernel(
     const unsigned long long live = __ballot(valid);
     for (int i = 0; i + 1 < last; ++i) {
       // (two ballots and scalar ands: one `&&` of the two tests cost a v_cndmask and a second compare per step)
-      const unsigned long long w = __ballot(cls == nms_lane(cls, i)) &
-                                   __ballot(nms_overlaps(nms_lane(tb, i), nms_lane(area, i), tb, area, thr)) &
+      const unsigned long long w = __ballot(cls == row_lane(cls, i)) &
+                                   __ballot(nms_overlaps(row_lane(tb, i), row_lane(area, i), tb, area, thr)) &
                                    live & ~((2ull << i) - 1ull);                      // rows above i only
       if (lane == i) word = w;
     }
@@ -124,7 +102,7 @@ __global__ __launch_bounds__(1024) void detect_nms_kernel(
       unsigned long long standing = __ballot(valid && !suppressed), todo = __ballot(word != 0ull);
       while (standing & todo) {
         const int i = __builtin_ctzll(standing & todo);
-        standing &= ~nms_lane(word, i);                    // bits above i only: row i itself stays
+        standing &= ~row_lane(word, i);                    // bits above i only: row i itself stays
         todo &= ~((2ull << i) - 1ull);
       }
       if (lane == 0) s_kept[blk] = standing;
@@ -136,12 +114,12 @@ __global__ __launch_bounds__(1024) void detect_nms_kernel(
       const float4 ob = s_box[blk * 64 + lane];
       const float oa = s_area[blk * 64 + lane];
       const int oc = s_cls[blk * 64 + lane];
-      unsigned long long m = nms_uniform64(s_kept[blk]), struck = 0ull;
+      unsigned long long m = row_uniform64(s_kept[blk]), struck = 0ull;
       if (__ballot(valid && !suppressed) == 0ull) m = 0ull;               // nobody left to strike in this wave
       while (m) {
         const int i = __builtin_ctzll(m);
         m &= m - 1;
-        struck |= __ballot(cls == nms_lane(oc, i)) & __ballot(nms_overlaps(nms_lane(ob, i), nms_lane(oa, i), tb, area, thr));
+        struck |= __ballot(cls == row_lane(oc, i)) & __ballot(nms_overlaps(row_lane(ob, i), row_lane(oa, i), tb, area, thr));
       }
       suppressed |= (struck >> lane) & 1ull;
     }
@@ -160,17 +138,14 @@ __global__ __launch_bounds__(1024) void detect_nms_kernel(
     out_scores[o] = score;
     out_labels[o] = label;
     out_query[o] = query;
-    out_boxes[o * 4 + 0] = box.x;
-    out_boxes[o * 4 + 1] = box.y;
-    out_boxes[o * 4 + 2] = box.z;
-    out_boxes[o * 4 + 3] = box.w;
+    row_put(out_boxes + o * 4, box);
     if (out_source) out_source[o] = j;
   }
   if (j >= total && j < K) {
     out_scores[row] = 0.f;
     out_labels[row] = -1;
     out_query[row] = -1;
-    for (int k = 0; k < 4; ++k) out_boxes[row * 4 + k] = 0.f;
+    row_put(out_boxes + row * 4, make_float4(0.f, 0.f, 0.f, 0.f));
     if (out_source) out_source[row] = -1;
   }
   if (j == 0) out_count[b] = total;
@@ -180,7 +155,7 @@ extern "C" int fod_detect_nms(const float* scores, const int* labels, const floa
                               const int* count, int B, int K, float iou_threshold, int class_agnostic,
                               float* out_scores, int* out_labels, float* out_boxes, int* out_query, int* out_count,
                               int* out_source, hipStream_t stream) {
-  FOD_REQUIRE(K >= 1 && K <= NMS_MAX_K, "detect_nms: K=%d is outside 1..%d", K, NMS_MAX_K);
+  FOD_REQUIRE(K >= 1 && K <= ROWS_MAX, "detect_nms: K=%d is outside 1..%d", K, ROWS_MAX);
   FOD_REQUIRE(B >= 1, "detect_nms: B=%d samples, at least 1 expected", B);
   FOD_REQUIRE(iou_threshold >= 0.f && iou_threshold <= 1.f, "detect_nms: iou_threshold=%g is outside [0, 1]",
               (double)iou_threshold);

@@ -16,24 +16,14 @@
 //      it is born in.  A slot that was cleared and is born in again in the same call is written by the newborn row only:
 //      every element has exactly one writer.
 // No scratch, no atomics, nothing between workgroups; the order of every decision is fixed: deterministic.
-#include "common.h"
+#include "det_rows.h"   // fp contract(off) from here on (explained there): `box + vel * gap` would become one v_fma_f32
 
-// The prediction, the IoU and the velocity are defined in single roundings (the header): nothing in this file may
-// contract a * b + c -- `box + vel * gap` would become one v_fma_f32.  Plain operators, not __fmul_rn: see detect_nms.hip.
-#pragma clang fp contract(off)
-
-constexpr int TRK_MAX = 1024;                          // rows (= DET_MAX_K of fod_detect_select) and slots
-
-FOD_DEVINL bool trk_finite(const float4 b) { return isfinite(b.x) && isfinite(b.y) && isfinite(b.z) && isfinite(b.w); }
-FOD_DEVINL float4 trk_box(const float* p) { return make_float4(p[0], p[1], p[2], p[3]); }     // (4-byte alignment only)
-FOD_DEVINL void trk_put(float* p, const float4 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
-FOD_DEVINL float trk_area(const float4 b) { return fmaxf(b.z - b.x, 0.f) * fmaxf(b.w - b.y, 0.f); }
 // the header's IoU of a row `a` and a predicted box `q`; `inter` comes back as well (the match needs inter > 0).
 // To be called by all lanes of a wave together.  The correctly rounded division is most of the work, and most pairs do not
 // overlap: where inter is +0 (or NaN, and uni with it) the header's expression is +0 whatever uni is, so a wave in which no
 // lane has inter > 0 skips the division -- the same bits, a wave-uniform branch.
 FOD_DEVINL float trk_iou(const float4 a, const float area_a, const float4 q, const float area_q, float& inter) {
-  inter = fmaxf(fminf(a.z, q.z) - fmaxf(a.x, q.x), 0.f) * fmaxf(fminf(a.w, q.w) - fmaxf(a.y, q.y), 0.f);
+  inter = row_inter(a, q);
   float iou = 0.f;
   if (__ballot(inter > 0.f) != 0ull) {
     const float uni = (area_a + area_q) - inter;
@@ -42,36 +32,25 @@ FOD_DEVINL float trk_iou(const float4 a, const float area_a, const float4 q, con
   return iou;
 }
 
-FOD_DEVINL unsigned long long trk_uniform64(unsigned long long v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
-// the value lane `i` holds, for a wave-uniform i: v_readlane_b32, no LDS round trip
-FOD_DEVINL int trk_lane(int v, int i) { return __builtin_amdgcn_readlane(v, i); }
-FOD_DEVINL float trk_lane(float v, int i) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i)); }
-FOD_DEVINL float4 trk_lane(float4 v, int i) {
-  return make_float4(trk_lane(v.x, i), trk_lane(v.y, i), trk_lane(v.z, i), trk_lane(v.w, i));
-}
-
 __global__ __launch_bounds__(1024) void track_update_kernel(
     const float* __restrict__ scores, const int32_t* __restrict__ labels, const float* __restrict__ boxes,
     const int32_t* __restrict__ count, float* __restrict__ trk_boxes, float* __restrict__ trk_vel,
     int32_t* __restrict__ trk_meta, float* __restrict__ trk_scores, int32_t* __restrict__ next_id,
     int32_t* __restrict__ out_track, int32_t* __restrict__ out_hits, int32_t* __restrict__ out_slot, int K, int S,
     float thr, float birth_score, int max_misses, int class_agnostic, int motion) {
-  __shared__ float4 s_pbox[TRK_MAX];                    // slots: the predicted box, zeros where it cannot be claimed
-  __shared__ float4 s_rbox[TRK_MAX];                    // rows: the box, zeros where it is not finite or beyond n
-  __shared__ float s_parea[TRK_MAX];
-  __shared__ int s_pcls[TRK_MAX];
-  __shared__ int s_rcls[TRK_MAX];
-  __shared__ int s_rbest[TRK_MAX];                      // rows: A leaves best slot | matched << 16 (or -1), B the claimed slot (or -1)
-  __shared__ int s_smatch[TRK_MAX];                     // slots: the row that claimed it, or -1
-  __shared__ int s_list[TRK_MAX];                       // the r-th free slot
-  __shared__ unsigned long long s_availw[TRK_MAX / 64]; // per 64 slots: claimable
-  __shared__ unsigned long long s_candw[TRK_MAX / 64];  // per 64 rows: takes part in B
-  __shared__ int s_fcnt[TRK_MAX / 64], s_bcnt[TRK_MAX / 64];
+  __shared__ float4 s_pbox[ROWS_MAX];                   // slots: the predicted box, zeros where it cannot be claimed
+  __shared__ float4 s_rbox[ROWS_MAX];                   // rows: the box, zeros where it is not finite or beyond n
+  __shared__ float s_parea[ROWS_MAX];
+  __shared__ int s_pcls[ROWS_MAX];
+  __shared__ int s_rcls[ROWS_MAX];
+  __shared__ int s_rbest[ROWS_MAX];                     // rows: A leaves best slot | matched << 16 (or -1), B the claimed slot (or -1)
+  __shared__ int s_smatch[ROWS_MAX];                    // slots: the row that claimed it, or -1
+  __shared__ int s_list[ROWS_MAX];                      // the r-th free slot
+  __shared__ unsigned long long s_availw[ROWS_MAX / 64];   // per 64 slots: claimable
+  __shared__ unsigned long long s_candw[ROWS_MAX / 64];    // per 64 rows: takes part in B
+  __shared__ int s_fcnt[ROWS_MAX / 64], s_bcnt[ROWS_MAX / 64];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = blockDim.x >> 6;
-  const int n = min(max(count[b], 0), K);               // rows at or beyond n are never read
+  const int n = row_count(count, b, K);
   const int first_id = next_id[b];                       // (read by every thread before the first barrier; written after the last)
   const int nsblk = (S + 63) >> 6, nrblk = (n + 63) >> 6;
   const long row = (long)b * K + tid, slot = (long)b * S + tid;
@@ -88,16 +67,16 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
     slabel = trk_meta[slot * 4 + 1];
     hits = trk_meta[slot * 4 + 2];
     misses = trk_meta[slot * 4 + 3];
-    sbox = trk_box(trk_boxes + slot * 4);
-    svel = trk_box(trk_vel + slot * 4);
+    sbox = row_box(trk_boxes + slot * 4);
+    svel = row_box(trk_vel + slot * 4);
     gap = (float)(misses + 1);
     pbox = motion ? make_float4(sbox.x + svel.x * gap, sbox.y + svel.y * gap, sbox.z + svel.z * gap, sbox.w + svel.w * gap)
                   : sbox;
-    claimable = trk_finite(pbox);
+    claimable = row_finite(pbox);
   }
   if (!claimable) pbox = zero4;
-  s_pbox[tid] = pbox;                                    // (the launch has at most TRK_MAX threads)
-  s_parea[tid] = trk_area(pbox);
+  s_pbox[tid] = pbox;                                    // (the launch has at most ROWS_MAX threads)
+  s_parea[tid] = row_area(pbox);
   s_pcls[tid] = class_agnostic ? 0 : slabel;
   s_smatch[tid] = -1;
   {
@@ -110,11 +89,11 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
   if (tid < n) {
     score = scores[row];
     label = labels[row];
-    box = trk_box(boxes + row * 4);
+    box = row_box(boxes + row * 4);
   }
-  const bool fin = tid < n && trk_finite(box);           // tested here, once: a row that fails it takes no part at all
+  const bool fin = tid < n && row_finite(box);          // tested here, once: a row that fails it takes no part at all
   const float4 rb = fin ? box : zero4;
-  const float rarea = trk_area(rb);
+  const float rarea = row_area(rb);
   const int rcls = class_agnostic ? 0 : label;
   s_rbox[tid] = rb;
   s_rcls[tid] = rcls;
@@ -126,7 +105,7 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
     int bslot = -1;
     if (__ballot(fin) != 0ull) {
       for (int blk = 0; blk < nsblk; ++blk) {
-        unsigned long long m = trk_uniform64(s_availw[blk]);
+        unsigned long long m = row_uniform64(s_availw[blk]);
         if (m == 0ull) continue;
         const float4 ob = s_pbox[blk * 64 + lane];
         const float oa = s_parea[blk * 64 + lane];
@@ -135,8 +114,8 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
           const int i = __builtin_ctzll(m);
           m &= m - 1;
           float inter;
-          const float iou = trk_iou(rb, rarea, trk_lane(ob, i), trk_lane(oa, i), inter);
-          if (rcls == trk_lane(oc, i) && iou > best) {   // ascending slots, strictly greater: ties stay with the lowest
+          const float iou = trk_iou(rb, rarea, row_lane(ob, i), row_lane(oa, i), inter);
+          if (rcls == row_lane(oc, i) && iou > best) {   // ascending slots, strictly greater: ties stay with the lowest
             best = iou;
             binter = inter;
             bslot = blk * 64 + i;
@@ -156,7 +135,7 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
   if (wave == 0) {
     unsigned claimed = 0u;                               // bit r: slot lane + 64 r is claimed
     for (int w = 0; w < nrblk; ++w) {
-      unsigned long long m = trk_uniform64(s_candw[w]);
+      unsigned long long m = row_uniform64(s_candw[w]);
       if (m == 0ull) continue;
       const int packed = s_rbest[w * 64 + lane];
       const float4 qb = s_rbox[w * 64 + lane];
@@ -165,14 +144,14 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
       while (m) {
         const int i = __builtin_ctzll(m);
         m &= m - 1;
-        const int p = trk_lane(packed, i), bs = p & 0xffff;
+        const int p = row_lane(packed, i), bs = p & 0xffff;
         int got = -1;
-        if (((trk_lane((int)claimed, bs & 63) >> (bs >> 6)) & 1) == 0) {
+        if (((row_lane((int)claimed, bs & 63) >> (bs >> 6)) & 1) == 0) {
           if (p >> 16) got = bs;                          // its best of A stands: also the best of what is left
         } else {
-          const float4 q = trk_lane(qb, i);
-          const float qarea = trk_area(q);
-          const int cls = trk_lane(qc, i);
+          const float4 q = row_lane(qb, i);
+          const float qarea = row_area(q);
+          const int cls = row_lane(qc, i);
           float best = -1.f, binter = 0.f;
           int bslot = 0x7fffffff;
           for (int r = 0; r < nsblk; ++r) {
@@ -259,8 +238,8 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
 
   // ---- D. writes: every element by exactly one thread
   if (dirty && !(is_free && frank < nborn)) {            // (a cleared slot that is born in again: the newborn row writes it)
-    trk_put(trk_boxes + slot * 4, sbox);
-    trk_put(trk_vel + slot * 4, svel);
+    row_put(trk_boxes + slot * 4, sbox);
+    row_put(trk_vel + slot * 4, svel);
     trk_meta[slot * 4 + 0] = id;
     trk_meta[slot * 4 + 1] = slabel;
     trk_meta[slot * 4 + 2] = hits;
@@ -280,8 +259,8 @@ __global__ __launch_bounds__(1024) void track_update_kernel(
       t = first_id + brank;
       h = 1;
       const long o = (long)b * S + s;
-      trk_put(trk_boxes + o * 4, box);
-      trk_put(trk_vel + o * 4, zero4);
+      row_put(trk_boxes + o * 4, box);
+      row_put(trk_vel + o * 4, zero4);
       trk_meta[o * 4 + 0] = t;
       trk_meta[o * 4 + 1] = label;
       trk_meta[o * 4 + 2] = 1;
@@ -299,8 +278,8 @@ extern "C" int fod_track_update(const float* scores, const int* labels, const fl
                                 float* trk_boxes, float* trk_vel, int* trk_meta, float* trk_scores, int* next_id, int S,
                                 float iou_threshold, float birth_score, int max_misses, int class_agnostic, int motion,
                                 int* out_track, int* out_hits, int* out_slot, hipStream_t stream) {
-  FOD_REQUIRE(K >= 1 && K <= TRK_MAX, "track_update: K=%d is outside 1..%d", K, TRK_MAX);
-  FOD_REQUIRE(S >= 1 && S <= TRK_MAX, "track_update: S=%d is outside 1..%d", S, TRK_MAX);
+  FOD_REQUIRE(K >= 1 && K <= ROWS_MAX, "track_update: K=%d is outside 1..%d", K, ROWS_MAX);
+  FOD_REQUIRE(S >= 1 && S <= ROWS_MAX, "track_update: S=%d is outside 1..%d", S, ROWS_MAX);
   FOD_REQUIRE(B >= 1, "track_update: B=%d samples, at least 1 expected", B);
   FOD_REQUIRE(iou_threshold >= 0.f && iou_threshold <= 1.f, "track_update: iou_threshold=%g is outside [0, 1]",
               (double)iou_threshold);

@@ -159,7 +159,7 @@ class Plan:
     def box_map(self):
         """(sx, sy, ox, oy): output-pixel coordinates back to source-frame pixels, x_src = x * sx + ox and y_src =
         y * sy + oy -- the inverse of `annotate` for boxes inside the rectangle.  A flip gives sx < 0: the caller
-        re-orders the corners (ops.detect_select does)."""
+        re-orders the corners (detect.detect_select does)."""
         top, left, h, w = self.rect
         H, W = self.size
         if self.flip:

@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from future_od.models.set_criterion import (SetCriterion, build_matcher, device_matching_enabled, pack_targets,
                                             run_while_matching, take_unrun_while_matching)
+from future_od.native import detect
 from future_od.native import ops
 from future_od.utils.od_map import prepare_od_map_stuffs
 
@@ -149,7 +150,7 @@ class SpatioTemporalDETR(nn.Module):
     def predict(self, data, top_k=100, score_threshold=0.0, per_query=False, box_map=None, attention=False, *,
                 nms=None, nms_class_agnostic=False):
         """Detections for frames WITHOUT annotations: the core exactly as `forward` calls it, then one launch
-        (ops.detect_select) in place of the reference's post-processing chain (st_detr.py:190-234, ConditionalDETR's
+        (detect.detect_select) in place of the reference's post-processing chain (st_detr.py:190-234, ConditionalDETR's
         PostProcess, demo.ipynb:171-172,245) -- no targets, no matcher, no loss, no AP bookkeeping, no host sync.
         -> {"scores" f32 [B,K], "labels" i32 [B,K], "boxes" f32 [B,K,4] xyxy pixels, "query" i32 [B,K], "count" i32 [B]}
         on the device: per sample the `top_k` best of all (query, class) pairs -- `per_query`: of the queries, each
@@ -163,7 +164,7 @@ class SpatioTemporalDETR(nn.Module):
         per image; 'attend all at once': the ONE memory's keys are returned split into its frames, and a map sums to 1
         over all of them.  Off (the default) nothing is tapped and no launch, key or number changes.
         `nms` (None: off, and no launch, key or bit differs): an IoU threshold in [0, 1] -- ONE more launch
-        (ops.detect_nms) right after the selection, in place on its outputs and before the attention launch: greedy
+        (detect.detect_nms) right after the selection, in place on its outputs and before the attention launch: greedy
         hard suppression in row order, a row dropped iff a kept earlier row of its class (`nms_class_agnostic`: of any
         class) overlaps it with inter > nms * union.  The survivors move to the front, `count` becomes their number, and
         the dict gains "source" i32 [B,K], the row of the unsuppressed result each row came from (-1 for padding);
@@ -188,12 +189,12 @@ class SpatioTemporalDETR(nn.Module):
                 self._model.attention_tap = None
         if not (isinstance(outputs, dict) and outputs["pred_logits"].dim() == 3):
             raise ValueError("cannot interpret output on the format: %s" % type(outputs))
-        scores, labels, boxes, query, count = ops.detect_select(
+        scores, labels, boxes, query, count = detect.detect_select(
             outputs["pred_logits"].detach().float().contiguous(), outputs["pred_boxes"].detach().float().contiguous(),
             H, W, top_k, score_threshold, per_query, box_map)
         out = {"scores": scores, "labels": labels, "boxes": boxes, "query": query, "count": count}
         if nms is not None:
-            out["source"] = ops.detect_nms(scores, labels, boxes, query, count, nms, nms_class_agnostic,
+            out["source"] = detect.detect_nms(scores, labels, boxes, query, count, nms, nms_class_agnostic,
                                            out=(scores, labels, boxes, query, count, torch.empty_like(labels)))[5]
         if tap is not None:
             out["attention"] = tap.maps(self._model.detector.decoder.layers[-1].self_attend.Nhead, query)
@@ -232,7 +233,7 @@ class SpatioTemporalDETR(nn.Module):
         """class_scores (logits) [B,Lo,M,C], boxes cxcywh in (0,1) [B,Lo,M,4] -> od_map 4-tuple and the
         output dict of the reference (st_detr.py:190-234)."""
         B, L, _, H, W = images.shape
-        scores, boxes_px = ops.post_proc(class_scores.detach().float().contiguous(),
+        scores, boxes_px = detect.post_proc(class_scores.detach().float().contiguous(),
                                          boxes.detach().float().contiguous(), H, W)
         if L == boxes.shape[1]:
             idx = data["annotated_frame_idx"]

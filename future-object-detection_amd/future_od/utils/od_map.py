@@ -11,7 +11,7 @@ fod_ap_hist_finalize): constant memory, one all_reduce between ranks, COCO's 101
 import numpy as np
 import torch
 
-from future_od.native import ops
+from future_od.native import detect
 
 SIZE_CATEGORY_DELIMITERS = [(1 / 24) * (1 / 64), (1 / 4) * (1 / 12)]   # fractions of H*W
 NUM_THRESHOLDS = 10                                                   # IoU 0.50 : 0.05 : 0.95
@@ -24,7 +24,7 @@ def prepare_od_map_stuffs(pred_boxes, pred_class_scores, anno_boxes, anno_classe
     num_annos (C,4) i64 with K = min(50, M) (reference od_map.py:214-287)."""
     B, M, C = pred_class_scores.shape
     N = anno_classes.shape[-1]
-    return ops.od_map(pred_class_scores.detach().float().contiguous(), pred_boxes.detach().float().contiguous(),
+    return detect.od_map(pred_class_scores.detach().float().contiguous(), pred_boxes.detach().float().contiguous(),
                       anno_boxes.reshape(B, N, 4).float().contiguous(), anno_classes.reshape(B, N).contiguous(),
                       anno_active.reshape(B, N).contiguous(), imsize, T=NUM_THRESHOLDS)
 
@@ -72,7 +72,7 @@ DETECTION_KEYS = ("scores", "labels", "boxes", "query", "count")
 def prepare_od_map_detections(det, anno_boxes, anno_classes, anno_active, imsize, num_classes, per_class=50):
     """`prepare_od_map_stuffs` for the dict of `predict` / `GraphedPredict` (suppressed by `nms=` or not) instead of dense
     scores: the rows below `count` in their order are the ranking, class c's candidates are its first `per_class` rows,
-    the generic class's are the first row of every query (ops.detect_od_map; fod_detect_od_map in include/fod_ext.h has
+    the generic class's are the first row of every query (detect.detect_od_map; fod_detect_od_map in include/fod_ext.h has
     the exact semantics).  -> confs (T,C,B*P) f32, is_positive (T,C,B*P) bool, size_categories (C,4,B*P) bool, num_annos
     (C,4) i64 with C = num_classes + 1 and P = min(per_class, K).  One launch, nothing read back.  With every pair
     selected (top_k = M * num_classes, threshold 0) this is `prepare_od_map_stuffs` on the same predictions, bit for bit.
@@ -82,7 +82,7 @@ def prepare_od_map_detections(det, anno_boxes, anno_classes, anno_active, imsize
         raise ValueError("prepare_od_map_detections: these detections went through a box_map (boxes in the camera's "
                          "frame); the annotations are in the network's input frame")
     B, N = anno_classes.shape[0], anno_classes.shape[-1]
-    return ops.detect_od_map(*(det[k] for k in DETECTION_KEYS), anno_boxes.reshape(B, N, 4).float().contiguous(),
+    return detect.detect_od_map(*(det[k] for k in DETECTION_KEYS), anno_boxes.reshape(B, N, 4).float().contiguous(),
                              anno_classes.reshape(B, N).contiguous(), anno_active.reshape(B, N).contiguous(), imsize,
                              num_classes, per_class, T=NUM_THRESHOLDS)
 
@@ -152,11 +152,11 @@ class StreamingDetectionEvaluator(DetectionEvaluator):
     """ev = StreamingDetectionEvaluator(num_classes); for batch: ev.update(model.predict(batch, ...), batch); ev.aggregate()
 
     DetectionEvaluator in constant memory: `update` runs the bookkeeping launch into buffers it reuses and folds them into
-    integer histograms over 16257 score bins (ops.ap_hist_accum: one more launch, nothing read back, nothing kept per
+    integer histograms over 16257 score bins (detect.ap_hist_accum: one more launch, nothing read back, nothing kept per
     batch), so a set of any size can be scored and `tensors()` has nothing to return.  `aggregate` adds the states of
     all ranks with one all_reduce(SUM) per tensor when a process group with more than one rank is initialised (exact
     integers: every rank returns the bytes one process that saw all batches returns), finalises in one launch
-    (ops.ap_hist_finalize) and returns `aggregate_mean_average_precision`'s tables from the AP taken on bins, plus
+    (detect.ap_hist_finalize) and returns `aggregate_mean_average_precision`'s tables from the AP taken on bins, plus
     "coco" (the same tables from the 101-point interpolated AP), "pr_curve" ("precision" f64 and "score" f32
     [T,C,4,101], "recall" = i / 100) and "operating_point" with DetectionEvaluator's fields.  Where no two candidates of a
     (class, size) row share a bin the AP is the sorted one up to f64 rounding; otherwise a bin's candidates are counted
@@ -177,8 +177,8 @@ class StreamingDetectionEvaluator(DetectionEvaluator):
     def update_od(self, od):
         """One batch's (confs, is_positive, size_categories, num_annos) into the state."""
         if self._state is None:
-            self._state = ops.ap_hist_state(od[0].shape[0], self.num_classes + 1, od[0].device)
-        ops.ap_hist_accum(od, self._state)
+            self._state = detect.ap_hist_state(od[0].shape[0], self.num_classes + 1, od[0].device)
+        detect.ap_hist_accum(od, self._state)
         self._updates += 1
         return od
 
@@ -195,7 +195,7 @@ class StreamingDetectionEvaluator(DetectionEvaluator):
                 torch.empty((NUM_THRESHOLDS, C1, B * P), dtype=torch.float32, device=dev),
                 torch.empty((NUM_THRESHOLDS, C1, B * P), dtype=torch.bool, device=dev),
                 torch.empty((C1, 4, B * P), dtype=torch.bool, device=dev), torch.empty((C1, 4), dtype=torch.int64, device=dev))
-        od = ops.detect_od_map(*(det[k] for k in DETECTION_KEYS), data["boxes"].reshape(B, N, 4).float().contiguous(),
+        od = detect.detect_od_map(*(det[k] for k in DETECTION_KEYS), data["boxes"].reshape(B, N, 4).float().contiguous(),
                                data["classes"].reshape(B, N).contiguous(), data["active"].reshape(B, N).contiguous(),
                                data["video"].shape[-2:], self.num_classes, self.per_class, T=NUM_THRESHOLDS, out=out)
         return self.update_od(od)
@@ -213,13 +213,13 @@ class StreamingDetectionEvaluator(DetectionEvaluator):
         if self._state is None:
             if ranks == 1:
                 raise RuntimeError("StreamingDetectionEvaluator: no update yet")
-            self._state = ops.ap_hist_state(NUM_THRESHOLDS, self.num_classes + 1, "cpu" if device is None else device)
+            self._state = detect.ap_hist_state(NUM_THRESHOLDS, self.num_classes + 1, "cpu" if device is None else device)
         state = self._state
         if ranks > 1:                                       # the local state stays what this rank saw
             state = tuple(t.clone() for t in state)
             for t in state:
                 distrib.all_reduce(t, op=distrib.ReduceOp.SUM)
-        ap, ap101, pr, score, totals = (t.cpu() for t in ops.ap_hist_finalize(state))
+        ap, ap101, pr, score, totals = (t.cpu() for t in detect.ap_hist_finalize(state))
         anno = state[2].cpu()
         print("Number of annos for each class and size category is:")
         print(anno)

@@ -1,6 +1,6 @@
 """Identities across predict() calls.  `predict` ranks its rows by score, so row k of one call and row k of the next are
 unrelated; a DetectionTracker keeps, per sample, a table of tracks between the calls and gives every row of a call the
-identity of the track it continues -- one launch (ops.track_update; fod_track_update in include/fod_ext.h has the exact
+identity of the track it continues -- one launch (detect.track_update; fod_track_update in include/fod_ext.h has the exact
 semantics) on device tensors, the same definition in plain torch on CPU tensors, the same bytes.
 
 This is not the reference's prediction baseline (TrackerFuturePredictor, ops.tracker_cost / tracker_extrapolate): that
@@ -62,14 +62,14 @@ class DetectionTracker:
         """`det`: what predict() returned.  -> a NEW dict: det's entries (the same tensors, rows in the same order) plus
         "track" i32 [B,K], the identity of every row (-1: none), and "track_hits" i32 [B,K], the number of calls in which
         that track has been seen, this one included.  `det` itself is not modified; the state advances by one call."""
-        from future_od.native import capture, ops
+        from future_od.native import capture, detect
         scores = det["scores"]
         if scores.dim() != 2 or scores.shape[0] != self.batch:
             raise ValueError(f"DetectionTracker: scores {tuple(scores.shape)} of a batch of {self.batch} expected")
         self.to_device(scores.device)
         for t in self._tensors():                           # a graph being captured bakes their addresses in
             capture.hold("track state", t)
-        track, hits = ops.track_update(scores, det["labels"], det["boxes"], det["count"], self._tensors(),
+        track, hits = detect.track_update(scores, det["labels"], det["boxes"], det["count"], self._tensors(),
                                        iou_threshold=self.iou_threshold, birth_score=self.birth_score,
                                        max_misses=self.max_misses, class_agnostic=self.class_agnostic, motion=self.motion,
                                        out=(torch.empty_like(det["labels"]), torch.empty_like(det["labels"])))[:2]

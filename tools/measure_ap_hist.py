@@ -41,22 +41,22 @@ STATE_BYTES = (T * C1 * 4 * NB * 4, C1 * 4 * NB * 4 + C1 * 4 * 8)
 
 
 def setup(dev):
-    from future_od.native import ops
+    from future_od.native import detect
     logits, boxes, anno, classes, active = (t.to(dev) for t in MD.synthetic())
-    sel = ops.detect_select(logits, boxes, H, W, K)
-    od = ops.detect_od_map(*sel, anno, classes, active, (H, W), C, PER_CLASS, T=T)
-    state = ops.ap_hist_state(T, C1, dev)
-    ops.ap_hist_accum(od, state)
-    host = ops.ap_hist_state(T, C1, "cpu")
-    ops.ap_hist_accum(tuple(t.cpu() for t in od), host)
+    sel = detect.detect_select(logits, boxes, H, W, K)
+    od = detect.detect_od_map(*sel, anno, classes, active, (H, W), C, PER_CLASS, T=T)
+    state = detect.ap_hist_state(T, C1, dev)
+    detect.ap_hist_accum(od, state)
+    host = detect.ap_hist_state(T, C1, "cpu")
+    detect.ap_hist_accum(tuple(t.cpu() for t in od), host)
     assert all(torch.equal(a.cpu(), b) for a, b in zip(state, host)), "the CPU form's histograms differ"
-    got, want = ops.ap_hist_finalize(state), ops.ap_hist_finalize(host)
+    got, want = detect.ap_hist_finalize(state), detect.ap_hist_finalize(host)
     assert all(got[k].cpu().numpy().tobytes() == want[k].numpy().tobytes() for k in (2, 3, 4)), "the CPU form's curve differs"
     filled, adds = int(od[2][:, 0].sum()), int(state[1].sum()) + int(state[0].sum())
     accum_bytes = C1 * 4 * P + filled * (4 + T) + C1 * 4 * 8 + adds * 4
     final_bytes = sum(STATE_BYTES) + T * C1 * 4 * (8 + 8 + 101 * 12 + 16)
-    run = dict(detect=lambda: ops.detect_od_map(*sel, anno, classes, active, (H, W), C, PER_CLASS, T=T, out=od),
-               accum=lambda: ops.ap_hist_accum(od, state), finalize=lambda: ops.ap_hist_finalize(state))
+    run = dict(detect=lambda: detect.detect_od_map(*sel, anno, classes, active, (H, W), C, PER_CLASS, T=T, out=od),
+               accum=lambda: detect.ap_hist_accum(od, state), finalize=lambda: detect.ap_hist_finalize(state))
     names = dict(detect=f"fod_detect_od_map, K = {K} ({filled} of {C1 * P} slots filled)",
                  accum=f"fod_ap_hist_accum ({filled} filled slots, {adds} integer atomics)",
                  finalize=f"fod_ap_hist_finalize ({T * C1 * 4} rows of {NB} bins; state {STATE_BYTES[0] / 1e6:.1f} MB + "

@@ -7,7 +7,7 @@ K = 100 / 300 / 1024 rows, per_class = 50, T = 10.
     python tools/measure_detect_od_map.py --summarise DIR [--out FILE]   kernel durations of that trace, launch by launch
 
 The head is random (logits randn * 2, boxes that are jittered copies of the annotations or random), the rows are what
-fod_detect_select returns for every K, and the kernel's output is compared with the CPU form (ops.detect_od_map on host
+fod_detect_select returns for every K, and the kernel's output is compared with the CPU form (detect.detect_od_map on host
 tensors) byte for byte before anything is timed.
 Events: per configuration a block of calls is captured into a hipGraph; replays of it alternate with the same block
 launched eagerly, so there are two figures per call: inside a graph, gaps between nodes included, and eager, launch
@@ -73,23 +73,23 @@ def _out_bytes(P):
 
 
 def configurations(dev):
-    from future_od.native import ops
+    from future_od.native import detect
     logits, boxes, anno, classes, active = (t.to(dev) for t in synthetic())
-    scores, boxes_px = ops.post_proc(logits, boxes, H, W)
-    dense = ops.od_map(scores, boxes_px, anno, classes, active, (H, W))
+    scores, boxes_px = detect.post_proc(logits, boxes, H, W)
+    dense = detect.od_map(scores, boxes_px, anno, classes, active, (H, W))
     yield dict(name="fod_od_map (dense scores, 2 launches)", bytes=od_map_bytes(), kernel=KERNELS[0], out=None,
-               fn=lambda: ops.od_map(scores, boxes_px, anno, classes, active, (H, W)))
+               fn=lambda: detect.od_map(scores, boxes_px, anno, classes, active, (H, W)))
     for K in KS:
-        sel = ops.detect_select(logits, boxes, H, W, K)
+        sel = detect.detect_select(logits, boxes, H, W, K)
         assert sel[4].tolist() == [K] * B
-        out = ops.detect_od_map(*sel, anno, classes, active, (H, W), C, PER_CLASS, T=T)
-        want = ops.detect_od_map(*(t.cpu() for t in sel), anno.cpu(), classes.cpu(), active.cpu(), (H, W), C, PER_CLASS, T=T)
+        out = detect.detect_od_map(*sel, anno, classes, active, (H, W), C, PER_CLASS, T=T)
+        want = detect.detect_od_map(*(t.cpu() for t in sel), anno.cpu(), classes.cpu(), active.cpu(), (H, W), C, PER_CLASS, T=T)
         assert all(g.cpu().numpy().tobytes() == w.numpy().tobytes() for g, w in zip(out, want)), "the CPU form differs"
         filled = int(out[2][:, 0].sum())
         tp = int((out[1][0] & out[2][:, 0]).sum())
         yield dict(name=f"fod_detect_od_map, K = {K} ({filled} of {(C + 1) * B * min(PER_CLASS, K)} slots filled, {tp} positive "
                         f"at IoU 0.5; dense: {int(dense[1][0].sum())})", bytes=detect_bytes(K), kernel=KERNELS[1], out=out,
-                   fn=lambda s=sel, o=out: ops.detect_od_map(*s, anno, classes, active, (H, W), C, PER_CLASS, T=T, out=o))
+                   fn=lambda s=sel, o=out: detect.detect_od_map(*s, anno, classes, active, (H, W), C, PER_CLASS, T=T, out=o))
 
 
 def _line(name, ts, nbytes):

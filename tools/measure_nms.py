@@ -10,7 +10,7 @@ The head is synthetic, so the share of suppressed rows is set and not left to an
 groups that share a box (up to 1 % jitter), K (query, class) pairs carry high logits and everything else a low one, so
 the selection returns exactly those K rows; two of them suppress each other iff they share group and class.  The
 suppressed share of every configuration is counted from the kernel's own output, which is compared with the CPU form
-(ops.detect_nms on host tensors) byte for byte first.
+(detect.detect_nms on host tensors) byte for byte first.
 Events: a block of launches of each kernel is captured into a hipGraph and the graphs are replayed in alternation, so
 the figure is a launch inside a graph, gaps between nodes included.  Trace: every configuration launches each kernel
 eagerly --launches times, in a fixed order; the summary cuts the trace's rows for the two kernels into those runs.
@@ -64,20 +64,20 @@ def nms_bytes(K):
 
 
 def configurations(dev):
-    from future_od.native import ops
+    from future_od.native import detect
     for K in KS:
         logits, boxes = (t.to(dev) for t in synthetic_head(K))
-        sel = ops.detect_select(logits, boxes, H, W, K)
+        sel = detect.detect_select(logits, boxes, H, W, K)
         out = tuple(torch.empty_like(t) for t in sel + (sel[1],))
         for mode, thr in MODES:
-            got = ops.detect_nms(*sel, thr, False, out=out)
-            want = ops.detect_nms(*(t.cpu() for t in sel), thr, False)
+            got = detect.detect_nms(*sel, thr, False, out=out)
+            want = detect.detect_nms(*(t.cpu() for t in sel), thr, False)
             assert all(g.cpu().numpy().tobytes() == w.numpy().tobytes() for g, w in zip(got, want)), "the CPU form differs"
             kept = got[4].tolist()
             assert sel[4].tolist() == [K] * B
             yield dict(K=K, mode=mode, thr=thr, kept=kept,
-                       select=lambda l=logits, b=boxes, K=K, s=sel: ops.detect_select(l, b, H, W, K, out=s),
-                       nms=lambda s=sel, t=thr, o=out: ops.detect_nms(*s, t, False, out=o))
+                       select=lambda l=logits, b=boxes, K=K, s=sel: detect.detect_select(l, b, H, W, K, out=s),
+                       nms=lambda s=sel, t=thr, o=out: detect.detect_nms(*s, t, False, out=o))
 
 
 def _line(name, ts, nbytes):

@@ -15,7 +15,7 @@ The launch changes the state it reads, so every measured launch starts from a co
 other kernels: the summary does not count them).  The selection and the suppression run on the synthetic head of
 tools/measure_nms.py; the tracker's rows are synthetic as well, so that the three states are what they are called: the
 numbers of matched and born rows of every configuration are counted from the kernel's own output, which is compared
-with the CPU form (ops.track_update on host tensors) byte for byte first.
+with the CPU form (detect.track_update on host tensors) byte for byte first.
 The bytes a launch moves at most, and the time they alone would take at the 8 TB/s of HBM3E, stand beside each figure.
 A measurement needs the GPU."""
 import argparse
@@ -78,20 +78,20 @@ def rows_and_state(K, S, which):
 
 
 def configurations(dev):
-    from future_od.native import ops
+    from future_od.native import detect
     for K in KS:
         logits, hboxes = (t.to(dev) for t in MN.synthetic_head(K))
-        sel = ops.detect_select(logits, hboxes, MN.H, MN.W, K)
+        sel = detect.detect_select(logits, hboxes, MN.H, MN.W, K)
         nms_out = tuple(torch.empty_like(t) for t in sel + (sel[1],))
         for S in SS:
             for which in STATES:
                 rows, pristine = rows_and_state(K, S, which)
                 want_state = [t.clone() for t in pristine]
-                want = ops.track_update(*rows, want_state, **PARAMS)
+                want = detect.track_update(*rows, want_state, **PARAMS)
                 rows, pristine = tuple(t.to(dev) for t in rows), [t.to(dev) for t in pristine]
                 state = [t.clone() for t in pristine]
                 out = tuple(torch.empty_like(rows[1]) for _ in range(3))
-                got = ops.track_update(*rows, state, **PARAMS, out=out)
+                got = detect.track_update(*rows, state, **PARAMS, out=out)
                 assert all(g.cpu().numpy().tobytes() == w.numpy().tobytes() for g, w in zip(tuple(state) + got, tuple(want_state) + want)), \
                     "the CPU form differs"
                 matched, born = int((got[1] > 1).sum()), int((got[1] == 1).sum())
@@ -102,10 +102,10 @@ def configurations(dev):
                 def track(rows=rows, state=state, pristine=pristine, out=out):
                     for s, p in zip(state, pristine):
                         s.copy_(p)
-                    ops.track_update(*rows, state, **PARAMS, out=out)
+                    detect.track_update(*rows, state, **PARAMS, out=out)
                 yield dict(K=K, S=S, which=which, matched=matched, born=born, track=track,
-                           select=lambda l=logits, b=hboxes, K=K, s=sel: ops.detect_select(l, b, MN.H, MN.W, K, out=s),
-                           nms=lambda s=sel, o=nms_out: ops.detect_nms(*s, 0.5, False, out=o))
+                           select=lambda l=logits, b=hboxes, K=K, s=sel: detect.detect_select(l, b, MN.H, MN.W, K, out=s),
+                           nms=lambda s=sel, o=nms_out: detect.detect_nms(*s, 0.5, False, out=o))
 
 
 def _line(name, ts, nbytes):
