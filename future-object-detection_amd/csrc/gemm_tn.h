@@ -36,6 +36,16 @@ struct TnParams {
 constexpr int MSTEP = 32;   // gemm_tn.hip: reduction rows per step of the 128 x 128 kernel
 constexpr int MS = 64;      // gemm_tn_big.hip: reduction rows per stage
 
+// Operand extents in bytes, which the host checks against 4 GiB before they go into the buffer descriptors.  G: [M, N1], or
+// its N1 columns in segments of g_seg_cols that lie g_seg_stride elements apart (0 = plain); X: [M, K2].  (The job kernels
+// form the same extents from their table entries in place: profiles/tn_shared_pieces_isa.txt.)
+inline long g_extent(int M, long ldg, int N1, int g_seg_cols, long g_seg_stride, long esz) {
+  const long nseg = g_seg_cols > 0 ? (N1 + g_seg_cols - 1) / g_seg_cols : 1;
+  const long seg_c = g_seg_cols > 0 ? g_seg_cols : N1;
+  return ((nseg - 1) * g_seg_stride + (long)(M - 1) * ldg + seg_c) * esz;
+}
+inline long x_extent(int M, long ldx, int K2, long esz) { return ((long)(M - 1) * ldx + K2) * esz; }
+
 // Which kernel takes a weight gradient and how (tile, M-splits, block order, where the partial results go): decided by
 // route() (gemm_tn.hip) from the checked parameters -- p.det and the caller's workspace among them -- and a snapshot of
 // the knobs, and by nothing else; the launchers only launch what it says.

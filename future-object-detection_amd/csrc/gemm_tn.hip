@@ -378,14 +378,13 @@ FOD_DEVINL void gemm_tn_body(const TnParams& p, const int bid_x, const int bid_y
 
 // One named kernel per C-ABI entry point (rocprofv3 summaries then read like include/fod.h).
 // RING = 3: deeper rings (4, 6) measured within 1 % on every shape of the workload and cost an occupancy step.
-template <typename T>
-__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const TnParams p) {
-  gemm_tn_body<T, MODE_DENSE, 3>(p, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-template <typename T>
-__global__ __launch_bounds__(256, 2) void gemm_tn_det_kernel(const TnParams p) {
-  gemm_tn_body<T, MODE_DENSE, 3, true>(p, blockIdx.x, blockIdx.y, blockIdx.z);
-}
+#define FOD_TN128_KERNEL(NAME, MODE, DET)                                           \
+  template <typename T>                                                            \
+  __global__ __launch_bounds__(256, 2) void NAME(const TnParams p) {               \
+    gemm_tn_body<T, MODE, 3, DET>(p, blockIdx.x, blockIdx.y, blockIdx.z);          \
+  }
+FOD_TN128_KERNEL(gemm_tn_kernel, MODE_DENSE, false)
+FOD_TN128_KERNEL(gemm_tn_det_kernel, MODE_DENSE, true)
 
 // MANY long bf16 weight gradients of nn.Linear layers in ONE launch (fod_gemm_tn_multi_long): block b works on block
 // blk_local[b] = (split * ti + tile_i) * tj + tile_j of job blk_job[b] (< 0: nothing).  One encoder layer's weight
@@ -447,14 +446,8 @@ __global__ __launch_bounds__(256) void gemm_tn_multi_long_reduce_kernel(const fo
     *dst += acc;                                // as the atomic form: added to what the output holds
   }
 }
-template <typename T>
-__global__ __launch_bounds__(256, 2) void conv2d_wgrad_kernel(const TnParams p) {
-  gemm_tn_body<T, MODE_CONV, 3>(p, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-template <typename T>
-__global__ __launch_bounds__(256, 2) void conv2d_wgrad_det_kernel(const TnParams p) {
-  gemm_tn_body<T, MODE_CONV, 3, true>(p, blockIdx.x, blockIdx.y, blockIdx.z);
-}
+FOD_TN128_KERNEL(conv2d_wgrad_kernel, MODE_CONV, false)
+FOD_TN128_KERNEL(conv2d_wgrad_det_kernel, MODE_CONV, true)
 
 // DET (fod_colsum_acc_det): `out` is the scratch [row splits][groups * N]; row split y stores its sums there
 template <typename T, bool DET = false>
@@ -689,6 +682,12 @@ __global__ __launch_bounds__(256) void gemm_tn_multi_kernel(const fod_tn_job* __
   tn_small_body(p, tile % tj, tile / tj, smem, jobs + head + 1, j.chain);
 }
 
+// The 128 x 128 kernel's instantiations by [adds with atomics][f32][MODE]
+typedef void (*Tn128Kernel)(const TnParams);
+const Tn128Kernel TN128_KERNELS[2][2][2] = {
+    {{gemm_tn_det_kernel<__bf16>, conv2d_wgrad_det_kernel<__bf16>}, {gemm_tn_det_kernel<float>, conv2d_wgrad_det_kernel<float>}},
+    {{gemm_tn_kernel<__bf16>, conv2d_wgrad_kernel<__bf16>}, {gemm_tn_kernel<float>, conv2d_wgrad_kernel<float>}}};
+
 // Launches what route() decided for the checked parameters `p`.
 template <int MODE>
 int launch(int dtype, TnParams& p, hipStream_t stream) {
@@ -699,6 +698,7 @@ int launch(int dtype, TnParams& p, hipStream_t stream) {
     return FOD_OK;
   }
   if (r.kernel == FOD_ROUTE_TN_BIG) return launch_big(MODE, p, r, stream);
+  FOD_REQUIRE(dtype == FOD_BF16 || dtype == FOD_F32, "gemm_tn: bad dtype %d", dtype);
   const int tj = ceil_div(p.K2, 128), ti = ceil_div(p.N1, 128);
   const long part_floats = (long)p.N1 * p.K2 + (p.colsum ? p.N1 : 0);
   p.m_per_split = r.m_per_split;
@@ -708,43 +708,20 @@ int launch(int dtype, TnParams& p, hipStream_t stream) {
   p.xcd_order = r.xcd_order;
   const dim3 grid = p.xcd_order ? dim3(ti * tj * ((p.nsplit + 7) / 8 * 8)) : dim3(tj, ti, p.nsplit);
   if (p.det) {
-    if (dtype != FOD_BF16 && dtype != FOD_F32) {
-      fod_set_error("gemm_tn: bad dtype %d", dtype);
-      return FOD_ERR_ARG;
-    }
     FOD_REQUIRE_SCRATCH("gemm_tn (deterministic)", p.ws_caller, p.ws_caller_bytes,
                         p.nsplit > 1 ? (size_t)p.nsplit * part_floats * sizeof(float) : 0);
     p.part = p.ws_caller;
     p.part_stride = part_floats;
-    if (dtype == FOD_BF16) {
-      if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_det_kernel<__bf16>), grid, dim3(256), 0, stream, p);
-      else hipLaunchKernelGGL((conv2d_wgrad_det_kernel<__bf16>), grid, dim3(256), 0, stream, p);
-    } else {
-      if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_det_kernel<float>), grid, dim3(256), 0, stream, p);
-      else hipLaunchKernelGGL((conv2d_wgrad_det_kernel<float>), grid, dim3(256), 0, stream, p);
-    }
-    FOD_LAUNCH_CHECK();
-    if (p.nsplit == 1) return FOD_OK;
-    foddet::ReduceParams red{};
-    red.part = p.part; red.part_stride = part_floats; red.part_total = (long)p.nsplit * part_floats; red.nparts = p.nsplit;
-    red.out0 = p.dW; red.n0 = p.N1 * p.K2; red.cols0 = p.K2; red.ld0 = p.ldw;
-    red.out1 = p.colsum; red.n1 = p.colsum ? p.N1 : 0;
-    red.accumulate = 1;                         // as the atomic form: added to what the outputs hold (zero or a gradient)
-    return det_reduce_launch(red, 1, stream);
   }
-  if (dtype == FOD_BF16) {
-    if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_kernel<__bf16>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv2d_wgrad_kernel<__bf16>), grid, dim3(256), 0, stream, p);
-  } else if (dtype == FOD_F32) {
-    if (MODE == MODE_DENSE) hipLaunchKernelGGL((gemm_tn_kernel<float>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((conv2d_wgrad_kernel<float>), grid, dim3(256), 0, stream, p);
-  }
-  else {
-    fod_set_error("gemm_tn: bad dtype %d", dtype);
-    return FOD_ERR_ARG;
-  }
+  hipLaunchKernelGGL(TN128_KERNELS[p.det == 0][dtype == FOD_F32][MODE], grid, dim3(256), 0, stream, p);
   FOD_LAUNCH_CHECK();
-  return FOD_OK;
+  if (!p.det || p.nsplit == 1) return FOD_OK;
+  foddet::ReduceParams red{};
+  red.part = p.part; red.part_stride = part_floats; red.part_total = (long)p.nsplit * part_floats; red.nparts = p.nsplit;
+  red.out0 = p.dW; red.n0 = p.N1 * p.K2; red.cols0 = p.K2; red.ld0 = p.ldw;
+  red.out1 = p.colsum; red.n1 = p.colsum ? p.N1 : 0;
+  red.accumulate = 1;                           // as the atomic form: added to what the outputs hold (zero or a gradient)
+  return det_reduce_launch(red, 1, stream);
 }
 
 }  // namespace
@@ -895,9 +872,7 @@ extern "C" int fod_gemm_tn_grouped(int dtype, const void* G, long ldg, int g_seg
   p.colsum = colsum;
   p.accumulate = accumulate;
   p.g_seg_cols = g_seg_cols; p.g_seg_stride = g_seg_stride;
-  const long nseg = g_seg_cols > 0 ? ceil_div(N1, g_seg_cols) : 1;
-  const long seg_c = g_seg_cols > 0 ? g_seg_cols : N1;
-  const long gb = ((nseg - 1) * g_seg_stride + (long)(M - 1) * ldg + seg_c) * 2, xb = ((long)(M - 1) * ldx + K2) * 2;
+  const long gb = g_extent(M, ldg, N1, g_seg_cols, g_seg_stride, 2), xb = x_extent(M, ldx, K2, 2);
   FOD_REQUIRE(gb < 0xFFFFFFF0L - 16 && xb < 0xFFFFFFF0L - 16, "gemm_tn_grouped: operand larger than 4 GiB");
   FOD_REQUIRE(((long)N1 * ldw + K2) * 4 < 0x7FFFFFF0L, "gemm_tn_grouped: output larger than 2 GiB");
   p.g_bytes = (unsigned)gb;
@@ -970,7 +945,7 @@ int tn_dense_params(TnParams& p, int det, int dtype, const void* G, long ldg, co
   p.ws_caller = reinterpret_cast<float*>(ws);
   p.ws_caller_bytes = ws ? ws_bytes : 0;
   const long esz = dtype == FOD_BF16 ? 2 : 4;
-  const long gb = ((long)(M - 1) * ldg + N1) * esz, xb = ((long)(M - 1) * ldx + K2) * esz;
+  const long gb = g_extent(M, ldg, N1, 0, 0, esz), xb = x_extent(M, ldx, K2, esz);
   FOD_REQUIRE(gb < 0xFFFFFFF0L - 16 && xb < 0xFFFFFFF0L - 16, "gemm_tn: operand larger than 4 GiB");
   p.g_bytes = (unsigned)gb;
   p.x_bytes = (unsigned)xb;
@@ -1078,6 +1053,15 @@ extern "C" int fod_conv2d_wgrad_acc_det(int dtype, const void* dy, const void* x
 }
 
 namespace {
+template <bool DET>
+void colsum_launch(int dtype, dim3 grid, hipStream_t stream, const void* G, long ldg, int M, int N, int rpb, int group_rows,
+                   float* out) {
+  if (dtype == FOD_BF16)
+    hipLaunchKernelGGL((colsum_kernel<__bf16, DET>), grid, dim3(256), 0, stream, (const __bf16*)G, ldg, M, N, rpb, group_rows, out);
+  else
+    hipLaunchKernelGGL((colsum_kernel<float, DET>), grid, dim3(256), 0, stream, (const float*)G, ldg, M, N, rpb, group_rows, out);
+}
+
 int colsum_impl(int det, int dtype, const void* G, long ldg, int M, int N, int group_rows, float* out, void* ws,
                 size_t ws_bytes, hipStream_t stream) {
   FOD_REQUIRE(G && out && M > 0 && N > 0, "colsum: bad args");
@@ -1090,39 +1074,19 @@ int colsum_impl(int det, int dtype, const void* G, long ldg, int M, int N, int g
   if (splits < 1) splits = 1;
   const int rpb = (group_rows + splits - 1) / splits;
   const dim3 grid(ceil_div(N, 64), ceil_div(group_rows, rpb), groups);
-  if (det) {
-    if (dtype != FOD_BF16 && dtype != FOD_F32) {
-      fod_set_error("colsum: bad dtype %d", dtype);
-      return FOD_ERR_ARG;
-    }
-    const long per = (long)groups * N;
-    FOD_REQUIRE_SCRATCH("colsum_acc_det", ws, ws_bytes, (size_t)grid.y * per * sizeof(float));
-    float* part = reinterpret_cast<float*>(ws);
-    if (dtype == FOD_BF16)
-      hipLaunchKernelGGL((colsum_kernel<__bf16, true>), grid, dim3(256), 0, stream, (const __bf16*)G, ldg, M, N, rpb,
-                         group_rows, part);
-    else
-      hipLaunchKernelGGL((colsum_kernel<float, true>), grid, dim3(256), 0, stream, (const float*)G, ldg, M, N, rpb,
-                         group_rows, part);
-    FOD_LAUNCH_CHECK();
-    foddet::ReduceParams r{};
-    r.part = part; r.part_stride = per; r.part_total = (long)grid.y * per; r.nparts = (int)grid.y;
-    r.out0 = out; r.n0 = (int)per; r.cols0 = (int)per; r.ld0 = per;
-    r.accumulate = 1;
-    return det_reduce_launch(r, 1, stream);
-  }
-  if (dtype == FOD_BF16)
-    hipLaunchKernelGGL((colsum_kernel<__bf16>), grid, dim3(256), 0, stream, (const __bf16*)G, ldg, M, N, rpb,
-                       group_rows, out);
-  else if (dtype == FOD_F32)
-    hipLaunchKernelGGL((colsum_kernel<float>), grid, dim3(256), 0, stream, (const float*)G, ldg, M, N, rpb,
-                       group_rows, out);
-  else {
-    fod_set_error("colsum: bad dtype %d", dtype);
-    return FOD_ERR_ARG;
-  }
+  FOD_REQUIRE(dtype == FOD_BF16 || dtype == FOD_F32, "colsum: bad dtype %d", dtype);
+  const long per = (long)groups * N;
+  if (det) FOD_REQUIRE_SCRATCH("colsum_acc_det", ws, ws_bytes, (size_t)grid.y * per * sizeof(float));
+  float* part = reinterpret_cast<float*>(ws);
+  if (det) colsum_launch<true>(dtype, grid, stream, G, ldg, M, N, rpb, group_rows, part);
+  else colsum_launch<false>(dtype, grid, stream, G, ldg, M, N, rpb, group_rows, out);
   FOD_LAUNCH_CHECK();
-  return FOD_OK;
+  if (!det) return FOD_OK;
+  foddet::ReduceParams r{};
+  r.part = part; r.part_stride = per; r.part_total = (long)grid.y * per; r.nparts = (int)grid.y;
+  r.out0 = out; r.n0 = (int)per; r.cols0 = (int)per; r.ld0 = per;
+  r.accumulate = 1;
+  return det_reduce_launch(r, 1, stream);
 }
 }  // namespace
 

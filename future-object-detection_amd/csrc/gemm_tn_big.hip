@@ -466,16 +466,12 @@ int launch_big(int mode, const TnParams& p, const TnRoute& r, hipStream_t stream
   q.nsplit = r.nsplit; q.m_per_split = r.m_per_split;
   q.xcd_order = r.xcd_order;
   q.ws = r.uses_partials_ws ? p.ws_caller : nullptr;
-  if (mode == MODE_DENSE) {
-    if (r.bj == 256 && r.bi == 256) return launch_shape<MODE_DENSE, 256, 256>(q, stream);
-    return r.bi == 128 ? launch_shape<MODE_DENSE, 128, 256>(q, stream) : launch_shape<MODE_DENSE, 256, 128>(q, stream);
-  }
-  if (mode == MODE_CONV) {
-    if (r.bj == 256 && r.bi == 256) return launch_shape<MODE_CONV, 256, 256>(q, stream);
-    return r.bi == 128 ? launch_shape<MODE_CONV, 128, 256>(q, stream) : launch_shape<MODE_CONV, 256, 128>(q, stream);
-  }
-  fod_set_error("gemm_tn_big: unsupported mode %d", mode);
-  return FOD_ERR_ARG;
+  FOD_REQUIRE(mode == MODE_DENSE || mode == MODE_CONV, "gemm_tn_big: unsupported mode %d", mode);
+  // by [MODE][tile shape: 256 x 256, 128 x 256, 256 x 128]
+  static int (*const shapes[2][3])(const TnParams&, hipStream_t) = {
+      {launch_shape<MODE_DENSE, 256, 256>, launch_shape<MODE_DENSE, 128, 256>, launch_shape<MODE_DENSE, 256, 128>},
+      {launch_shape<MODE_CONV, 256, 256>, launch_shape<MODE_CONV, 128, 256>, launch_shape<MODE_CONV, 256, 128>}};
+  return shapes[mode][r.bj == 256 && r.bi == 256 ? 0 : r.bi == 128 ? 1 : 2](q, stream);
 }
 
 }  // namespace fodtn

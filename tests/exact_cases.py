@@ -501,7 +501,7 @@ for _s in two_smallest(TK.BIG256_CONV_CASES, conv_macs):
     _kn = dict(FOD_NT_BIG=2, FOD_NT_BIG256=2)
     _add("nt_big", _kn, "conv_fwd", _s, "bf16", dict(kernel=L.NT_BIG, tile_n=256 if _s[4] >= 256 else 128))
     _add("nt_big", _kn, "conv_dgrad", _s, "bf16", dict(kernel=L.NT_BIG, tile_n=256 if _s[3] >= 256 else 128), stride=_s[6])
-for _s in two_smallest(TK.TN_BIG_CONV_CASES, conv_macs):
+for _s in sorted(TK.TN_BIG_CONV_CASES, key=conv_macs)[:3]:      # the five-image case of one stage and the two after it
     for _splits in (0, 5):
         _add("tn_big", dict(FOD_TN_BIG=2, FOD_TN_BIG_SPLITS=_splits), "conv_wgrad", _s, "bf16", dict(kernel=L.TN_BIG, uses_partials_ws=0),
              row_scale=True)

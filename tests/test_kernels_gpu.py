@@ -122,6 +122,8 @@ CONV_CASES = [  # (Nimg, H, W, Cin, Cout, k, stride, pad)
     (3, 9, 11, 128, 72, 1, 1, 0),
     (2, 9, 12, 256, 512, 1, 2, 0),
     (1, 29, 50, 32, 40, 3, 1, 1),
+    (5, 3, 4, 16, 24, 3, 1, 1),       # 12 pixels per image: one 32-row step of the wgrad walk crosses two or three images
+    (4, 5, 3, 8, 16, 3, 2, 1),        # stride 2, 3 x 2 = 6 pixels per image
 ]
 
 
@@ -1158,7 +1160,8 @@ def test_tn_big_square_tile_conv(knobs, case, splits):
 
 
 TN_BIG_CONV_CASES = BIG_CONV_CASES + [(2, 17, 23, 8, 64, 7, 2, 3), (1, 29, 50, 32, 40, 3, 1, 1), (2, 57, 100, 256, 256, 3, 1, 1),
-                                      (3, 7, 5, 64, 128, 3, 1, 1), (2, 30, 41, 128, 256, 1, 2, 0)]
+                                      (3, 7, 5, 64, 128, 3, 1, 1), (2, 30, 41, 128, 256, 1, 2, 0),
+                                      (5, 3, 4, 16, 24, 3, 1, 1)]       # one 64-row stage covers all 60 rows of five images
 
 
 @pytest.mark.parametrize("splits", [0, 5])
